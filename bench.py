@@ -2,6 +2,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: GiB/s end-to-end (compress+decompress), 4 MiB blocks.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched under torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed to DIR/*.npy)
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
   compress    lz4f_mi355x_dev_compressFrameIndexed(..., LZ4F_MI355X_INBAND): find_matches -> layout -> emit, then the trailer
@@ -148,6 +149,32 @@ def where_am_i():
     return out
 
 
+DUMP_SEED = 1234
+DUMP_HEAD, DUMP_SAMPLE = 1 << 20, 3 << 20      # bytes per output and rank at N=1 (divided by N): 2 outputs x 4 Mi x float32 = 32 MiB in all
+
+
+def dump_outputs(d: str, frame, stream_bytes: int, back, res, rank: int, world: int, with_stream: bool) -> None:
+    """--dump-outputs: what the last timed step handed its caller that is a function of its input alone, as float32 byte values - each
+    output's first bytes (`*_head`) and a seeded sample of its positions (`*_sample`, the same positions whenever the output has the same
+    length) - and float64 sizes (`*_size`).  The decompressed bytes always; the compressed stream (the LZ4 frame and, in-band, its trailer;
+    size: stream bytes, frame bytes the decoder consumed) only `with_stream`, i.e. in the encoder's deterministic mode: in its default mode
+    the shared match search finds what the waves beside it have inserted so far, and the stream's bytes differ from run to run (DESIGN.md
+    section 4, "Deterministic parse")."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    pre = "rank%d_" % rank if world > 1 else ""
+    for i, (name, t, sizes) in enumerate((("compressed", frame, [stream_bytes, res.consumed]), ("decompressed", back, [res.size]))):
+        if name == "compressed" and not with_stream:
+            continue
+        length = min(int(sizes[0]), t.numel())
+        rng = np.random.default_rng((DUMP_SEED, rank, i))            # (one generator per output: its positions depend on its own length only)
+        pos = np.sort(rng.integers(0, length, DUMP_SAMPLE // world)) if length else np.zeros(0, dtype=np.int64)
+        np.save(os.path.join(d, pre + name + "_head.npy"), t[:min(length, DUMP_HEAD // world)].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(d, pre + name + "_sample.npy"), t[torch.from_numpy(pos).to(t.device)].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(d, pre + name + "_size.npy"), np.array(sizes, dtype=np.float64))
+
+
 def leg(fn):
     """A side leg must never take the headline down."""
     try:
@@ -171,7 +198,12 @@ def main():
     ap.add_argument("--foreign", action="store_true", help="the timed decode gets the bare LZ4 frame (no trailer): walk + self-index + indexed kernels")
     ap.add_argument("--cpu-sample-mib", type=int, default=512)
     ap.add_argument("--legs", default="all", help="comma-separated side legs to run (foreign,bck,cfg2,dense,linked,host,cck,replay,multi); what tools/prof_leg.sh profiles one at a time")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (compressed stream, decompressed bytes: "
+                                                          "first bytes and a seeded sample, at most 64 MB in all) to DIR/*.npy; the compressed stream only with "
+                                                          "LZ4F_MI355X_DETERMINISTIC set, the encoder's mode in which it repeats from run to run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # N > 1 and not yet under a launcher: start N ranks (one process per GPU) as a CHILD process and relay its output - nothing in
     # this process has touched the GPU yet (torch is not even imported).  Under a launcher WORLD_SIZE must be what --gpus says.
@@ -239,6 +271,7 @@ def main():
         eng.compress_async(src, frame, prefs, inband=inband)
         size = int(eng.result().size)
         eng.decompress_frame_async(frame, size, back)
+        return size
 
     def barrier():
         shard.barrier_all(torch.device(dev))
@@ -259,7 +292,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        stream_bytes = step()
     barrier()
     dt = time.perf_counter() - t0
     dt = shard.max_over_ranks(dt, "cpu" if share else dev)
@@ -268,6 +301,8 @@ def main():
         kt = dict(eng.get_timing())
     r2 = eng.result()
     ok = bool(r2.size == n and torch.equal(back, src))
+    if args.dump_outputs:                                     # (before the check below and the side legs overwrite frame and back)
+        dump_outputs(args.dump_outputs, frame, stream_bytes, back, r2, rank, world, "LZ4F_MI355X_DETERMINISTIC" in os.environ)
     # the last timed step's own frame decodes to the input as well
     eng.compress_async(src, frame, prefs, inband=inband); rl = eng.result(); t_c = eng.get_timing()
     back.zero_()

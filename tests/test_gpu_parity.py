@@ -1360,29 +1360,22 @@ def test_dense_payloads_in_big_independent_blocks(L):
 
 
 def _real_text(n: int) -> bytes:
-    """Real text instead of the synthetic kind: the image's own Python sources and headers, concatenated (the GPU box runs the same image)."""
-    import os
-    buf = bytearray()
-    for root in ("/usr/lib/python3/dist-packages", "/usr/lib/python3.10", "/usr/local/lib/python3.10/dist-packages", "/opt/rocm/include"):
-        for dp, dn, fn in os.walk(root):
-            for f in sorted(fn):
-                if f.endswith((".py", ".h", ".hpp", ".txt", ".md", ".rst", ".json")):
-                    try: buf += open(os.path.join(dp, f), "rb").read()
-                    except OSError: pass
-            if len(buf) >= n: break
-        if len(buf) >= n: break
-    return bytes(buf[:n])
+    """Real text instead of the synthetic kind: this project's own library sources, stored in tests/golden/project_sources.txt.xz (the C, C++,
+    HIP, Python and Haskell files under lz4_frame_conduit_amd/, oracle/, include/ and haskell/, concatenated; 0.8 MB), repeated to n bytes.
+    An LZ4 match reaches back 64 KiB at most, so the repeats are out of every encoder's sight: n bytes of it compress as n bytes of such text."""
+    import lzma
+    text = lzma.decompress(golden_file("project_sources.txt.xz"))
+    return (text * (n // len(text) + 1))[:n]
 
 
 @pytest.mark.gpu
 def test_real_text_both_directions_and_ratio(L):
-    """Real text (source code: longer matches and nearer repeats than the synthetic Zipf text, three times its ratio): what this library writes of it the oracle
+    """Real text (source code: longer matches and nearer repeats than the synthetic Zipf text, liblz4's ratio 2.39 against its 1.85): what this library writes of it the oracle
     decodes, what liblz4 writes of it this library decodes - 4 MiB and 64 KiB independent blocks, 64 KiB linked - and the size stays within REAL_TEXT_RATIO_TOL of
-    liblz4's.  That tolerance is what round 4 measured (11.5 % bigger; tools/real_text.py, NOTES_r4.md), not what is wanted: the test is there so that the number is
-    looked at and does not get worse unseen."""
-    REAL_TEXT_RATIO_TOL = 1.14
+    liblz4's.  That tolerance is what was measured on this text (9.1-9.5 % bigger; round 4 measured 11.5 % on other source text, tools/real_text.py, NOTES_r4.md)
+    with round 4's margin, not what is wanted: the test is there so that the number is looked at and does not get worse unseen."""
+    REAL_TEXT_RATIO_TOL = 1.12
     data = _real_text(24 << 20)
-    if len(data) < (8 << 20): pytest.skip("no text to speak of in this image")
     for kw in (dict(bsid=7, indep=1), dict(bsid=4, indep=1), dict(bsid=4, indep=0)):
         mine = gpu_compress_frame(L, data, prefs_of(kw))
         out, used = oracle.decompress_frame(mine, cap=len(data) + 64)
