@@ -177,7 +177,7 @@ __device__ __forceinline__ void fz_parser(FzShared<C>& sh, const uint8_t* __rest
             if (v_ml) {
                 const uint8_t* q = in + v_src + v_lit;                           // (the chain checked lit + 8 <= bytes left)
                 off = (uint32_t)q[0] | ((uint32_t)q[1] << 8);
-                bad = off == 0 || off > v_op + v_lit + hist_reach || (uint64_t)v_lit + v_ml + 5 > room;
+                bad = off == 0 || off > v_op + v_lit + hist_reach || (uint64_t)v_lit + v_ml + 5 > room || (uint64_t)v_lit + 12 > room;
             } else bad = v_lit > room;
         }
         d0 = v_src | ((off & 0xFFu) << 24);

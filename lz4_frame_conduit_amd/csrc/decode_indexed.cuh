@@ -209,6 +209,25 @@ __device__ __forceinline__ void parse_entry(const uint8_t* __restrict__ frame, u
     if (bad) atomicOr(flags, 1u);
 }
 
+// The rules that need the room (liblz4's: maxBlockSize, whatever the caller gives) on the descriptors k_parse_indexed / k_spx_parse
+// made: the block's last match starts 12 and ends 5 bytes or more before it (the rules are monotone in the output position, so the
+// last match is the one to look at).  A block that breaks them is marked failed (dst_size -1); nothing runs when the indexed kernels
+// gave up (the generic decoders, which check the rules themselves, decoded then).
+__global__ __launch_bounds__(256) void k_check_tails(BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
+                                                     const void* __restrict__ ix, const SeqDesc* __restrict__ desc, uint64_t desc_cap,
+                                                     uint32_t block_size, const uint32_t* __restrict__ flags)
+{
+    if (res->status != ST_OK || *flags) return;
+    const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n || (table[b].word >> 31)) return;
+    const IxBlock bk = ix_blocks(ix)[b];
+    if (bk.nseq < 2 || (uint64_t)bk.seq_base + bk.nseq > desc_cap) return;
+    const SeqDesc d = desc[bk.seq_base + bk.nseq - 2];
+    const uint64_t ms = (uint64_t)d.z + (d.y & 0xFFFFFFu), me = ms + (d.w & 0xFFFFFFu);
+    if (ms + 12 > block_size || me + 5 > block_size) table[b].dst_size = (uint32_t)-1;
+}
+
 __global__ __launch_bounds__(256) void k_parse_indexed(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                        const void* __restrict__ ix, uint32_t n_max,
                                                        SeqDesc* __restrict__ desc, uint32_t* __restrict__ flags, uint32_t linked, uint64_t hist0)
@@ -1129,7 +1148,7 @@ struct FzRunsIx {
 
 template <class C, class RUNS>
 __device__ __forceinline__ void fz_feeder_parse(FzShared<C>& sh, const RUNS& runs, const uint8_t* __restrict__ in, uint32_t csize, uint64_t readable,
-                                                SeqDesc* desc, uint32_t nseq, uint32_t cap, unsigned long long* prof, uint32_t round_max)
+                                                SeqDesc* desc, uint32_t nseq, uint32_t cap, unsigned long long* prof, uint32_t round_max, uint32_t room)
 {
     constexpr uint32_t OPR = FzOpr<C>::N, OMASK = OPR - 1;
     const uint32_t ROUND_MAX = (round_max >= 17u && round_max < OPR / 2) ? round_max : OPR / 2;      // (a test switch, LZ4F_MI355X_FEED_ROUND: rounds so small that every stretch of a foreign frame goes in pieces - the `part` path below)
@@ -1267,7 +1286,7 @@ __device__ __forceinline__ void fz_feeder_parse(FzShared<C>& sh, const RUNS& run
         bool bad = op != (lane == 0 ? expect : prev_end) || (uint64_t)p + lit > csize || end > cap;
         if (last) bad |= ml != 0 || direct;
         else {
-            bad |= ml < 4 || end + 5 > cap;
+            bad |= ml < 4 || end + 5 > room || dm + 12 > room;                // (liblz4's room is maxBlockSize: a match starts >= 12 and ends >= 5 bytes before it)
             const int64_t rel = (int64_t)f24 - (int64_t)FZ_SRC_BIAS;
             bad |= direct ? (rel < 0 || rel + (int64_t)ml > (int64_t)csize) : (f24 == 0 || f24 > 65535u || f24 > dm);
         }
@@ -1299,7 +1318,8 @@ __device__ __forceinline__ void fz_feeder_parse(FzShared<C>& sh, const RUNS& run
 // the workgroup of fz_decode_block<C, true>, its first wave feeding itself
 template <class C, class RUNS>
 __device__ __forceinline__ int32_t fz_decode_block_self(FzShared<C>& sh, const RUNS& runs, const uint8_t* __restrict__ in, uint32_t csize, uint64_t readable,
-                                                        uint8_t* out, uint32_t cap, const uint8_t* safe, unsigned long long* prof, SeqDesc* desc, uint32_t nseq, uint32_t round_max)
+                                                        uint8_t* out, uint32_t cap, const uint8_t* safe, unsigned long long* prof, SeqDesc* desc, uint32_t nseq, uint32_t round_max,
+                                                        uint32_t room)
 {
     const uint32_t wave = uni(threadIdx.x >> 6);
     __syncthreads();
@@ -1308,7 +1328,7 @@ __device__ __forceinline__ int32_t fz_decode_block_self(FzShared<C>& sh, const R
     __syncthreads();
     if (wave == 0) {
         __builtin_amdgcn_s_setprio(3);
-        fz_feeder_parse<C, RUNS>(sh, runs, in, csize, readable, desc, nseq, cap, prof, round_max);
+        fz_feeder_parse<C, RUNS>(sh, runs, in, csize, readable, desc, nseq, cap, prof, round_max, room);
         __builtin_amdgcn_s_setprio(0);
     }
     else fz_copier<C, true>(sh, in, out, wave - 1, safe, prof, nullptr);
@@ -1333,7 +1353,8 @@ struct FzSrcIx {
 template <class C, class RSRC>
 __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_selffed(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint8_t* dst, BlockOut* __restrict__ table,
                                                                    const ResultRec* __restrict__ res, uint32_t n_max, const void* __restrict__ ix,
-                                                                   SeqDesc* desc, uint32_t* __restrict__ flags, unsigned long long* prof, RSRC rsrc, uint32_t round_max)
+                                                                   SeqDesc* desc, uint32_t* __restrict__ flags, unsigned long long* prof, RSRC rsrc, uint32_t round_max,
+                                                                   uint32_t block_size)
 {
     __shared__ FzShared<C> sh;
     if (res->status != ST_OK || *flags || flags[IXT_FLAG]) return;           // index unusable (k_check_index): the generic kernel launched behind does the work
@@ -1368,7 +1389,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_selffed(cons
         } else {
             typename RSRC::Runs runs;
             if (rsrc.make(b, blk, csz, flags[8], runs))
-                got = fz_decode_block_self<C>(sh, runs, frame + e.src_off, csz, frame_cap - e.src_off, dst + e.dst_off, e.dst_size, frame, prof, desc + blk.seq_base, blk.nseq, round_max);
+                got = fz_decode_block_self<C>(sh, runs, frame + e.src_off, csz, frame_cap - e.src_off, dst + e.dst_off, e.dst_size, frame, prof, desc + blk.seq_base, blk.nseq, round_max, block_size);
         }
     }
     if (tid == 0) { if (got < 0) atomicOr(flags, 2u); else table[b].dst_size = (uint32_t)got; }

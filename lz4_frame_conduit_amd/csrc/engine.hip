@@ -168,7 +168,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
 {
     (void)hipSetDevice(device);
     (void)hipStreamSynchronize((hipStream_t)stream);
-    desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release();
+    desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
     d_in.release(); d_out.release();
     h_in.release(); h_out.release(); h_small.release();
@@ -666,18 +666,18 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
                         const FzSrcSpx src{(const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint))};
                         if (j.block_size <= (1u << 20))
                             hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, FzSrcSpx>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round);
+                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
                         else
                             hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, FzSrcSpx>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round);
+                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
                     } else {
                         const FzSrcIx src{(const void*)d_index, n_ix};
                         if (j.block_size <= (1u << 20))
                             hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, FzSrcIx>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round);
+                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
                         else
                             hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, FzSrcIx>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round);
+                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
                     }
                     tick(9, true);
                     indexed = true;
@@ -766,6 +766,8 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
                                        d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (uint32_t*)seqcnt.p, iprof, lk, done, group, (uint64_t)j.hist0, wait_ticks);
                 tick(9, true);
                 if (iprof && j.linked) { uint32_t y[4] = {0, 0, 0, 0}; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(y, (uint32_t*)seqcnt.p + 20, 16, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "indexed (linked): blocks that found the block in front at state 3: %u (of those, had to wait for all of it: %u); blocks with set-aside matches %u (block in front already done: %u)\n", y[0], y[1], y[2], y[3]); }
+                hipLaunchKernelGGL(k_check_tails, dim3((n_ix + 255) / 256), dim3(256), 0, st, tbl, (const ResultRec*)d_res, n_ix, (const void*)d_index,
+                                   (const SeqDesc*)desc.p, (uint64_t)ix_seq_cap, j.block_size, (const uint32_t*)seqcnt.p);
                 indexed = true;
                 ix_flags = (const uint32_t*)seqcnt.p;
                 plan |= LZ4F_MI355X_PATH_INDEXED;
@@ -829,6 +831,14 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
     }
     if (aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_join, 0)); aux_pending = false; }
     tick(7, false);
+    // liblz4 judges a block against maxBlockSize whatever room the caller leaves it.  Only a walked frame's last block can be left less
+    // (every other block sits below a provisional block's room the walk found inside the buffer), and only when the capacity is not a
+    // multiple of the block size: a last block that failed in that room is decoded again with a whole block's room, and copied out if it fits.
+    if (n_max && !j.d_table && !j.table_in_place && !j.table_direct && j.block_size && j.dst_cap % j.block_size != 0) {
+        if (tight.ensure((size_t)65536 + j.block_size + 64)) return make_err(LZ4F_ERROR_allocation_failed);
+        hipLaunchKernelGGL(k_redo_tight_block, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (uint64_t)j.dst_cap, tbl,
+                           (const ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size, (uint64_t)j.hist0, (uint8_t*)tight.p);
+    }
     const bool check_here = n_max <= 64;                              // (the finishing wave looks at a few blocks itself: a launch less)
     if (n_max && !check_here) hipLaunchKernelGGL(k_finish_check, dim3((n_max + 255) / 256), dim3(256), 0, st, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size, (uint32_t*)bad.p);
     hipLaunchKernelGGL(k_finish_decode, dim3(1), dim3(64), 0, st, j.d_dst, tbl, (ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size,

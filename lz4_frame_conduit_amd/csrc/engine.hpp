@@ -61,6 +61,7 @@ struct lz4f_mi355x_engine {
     lz4f::DevBuf spx;                                      // big independent blocks without an index: the true points of every block's check lines (decode_spx.cuh)
     lz4f::DevBuf selfix, selfcnt;                          // linked frames without an index: the one made here, and its per-block counts
     lz4f::DevBuf pdbuf;                                    // dense frames by pointer doubling: a word per output byte
+    lz4f::DevBuf tight;                                    // the last block when the caller's buffer leaves it less than a block of room (k_redo_tight_block)
     lz4f::DevBuf postab;                                   // dense frames: output position / 64 -> sequence (k_build_postab)
     lz4f::DevBuf desc, seqcnt;                             // two-kernel decode: sequence descriptors, per-block counts
     lz4f::DevBuf d_in, d_out;                              // staging for the host-pointer paths

@@ -894,6 +894,34 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG, 8) void k_decode_blocks(const ui
     }
 }
 
+// The last block of a walked frame when the caller's buffer left it less than a block of room and it failed there: liblz4 judges a
+// block against maxBlockSize whatever room the caller gives (LZ4F_decompress decodes into its own block buffer then), so it is decoded
+// again into `scratch` ([64 KiB history][block_size]) with a whole block of room, and copied out if it fits.  Its dst_size afterwards:
+// the size, -2 (it decodes, but not into the room: dstMaxSize_tooSmall) or -3 (it does not decode at all).
+__global__ __launch_bounds__(64) void k_redo_tight_block(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint8_t* dst, uint64_t dst_cap,
+                                                         BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
+                                                         uint32_t linked, uint32_t block_size, uint64_t hist0, uint8_t* __restrict__ scratch)
+{
+    if (res->status != ST_OK) return;
+    const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
+    if (n == 0) return;
+    const uint32_t b = n - 1, lane = lane_id();
+    const BlockOut e = table[b];
+    if ((int32_t)e.dst_size >= 0 || (e.word >> 31) || e.dst_off > dst_cap || dst_cap - e.dst_off >= block_size) return;
+    if (linked && b > 0 && (int32_t)table[b - 1].dst_size < 0) return;      // (an earlier block failed: that is the verdict)
+    const uint32_t csz = e.word & 0x7FFFFFFFu;
+    if (csz == 0 || csz > block_size || e.src_off + csz > frame_cap) return;
+    const uint32_t h = linked ? (uint32_t)(e.dst_off + hist0 < 65536u ? e.dst_off + hist0 : 65536u) : 0u;
+    uint8_t* const out = scratch + 65536u;
+    for (uint32_t i = lane; i < h; i += WAVE) out[(int64_t)i - h] = dst[(int64_t)e.dst_off + i - h];
+    __threadfence(); __syncthreads();
+    const int32_t got = wave_decode_block(frame + e.src_off, csz, out, block_size, h);
+    __threadfence(); __syncthreads();
+    const uint64_t room = dst_cap - e.dst_off;
+    if (got >= 0 && (uint64_t)got <= room) wave_copy_disjoint(dst + e.dst_off, out, (uint32_t)got);
+    if (lane == 0) table[b].dst_size = got < 0 ? (uint32_t)-3 : (uint64_t)got <= room ? (uint32_t)got : (uint32_t)-2;
+}
+
 // totals + status; compacts the output if a non-final block of an independent frame decoded short
 // What k_finish_decode has to know about the block table, found by a thread per block instead of one wave walking it 64
 // entries per dependent load (16384 blocks: 0.22 ms): the first failed block, whether every block already sits where its
@@ -959,7 +987,7 @@ __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __
         // (a block that did not decode into LESS room than a whole block is "the output does not fit", as the oracle's frame decoder and
         // the host paths call it: oracle/orc_lz4frame.c "room < bs ? dstMaxSize_tooSmall : GENERIC")
         const uint64_t at_bad = table[first_bad].dst_off;
-        const bool short_room = at_bad <= dst_cap && dst_cap - at_bad < block_size;
+        const bool short_room = at_bad <= dst_cap && dst_cap - at_bad < block_size && bad_kind != (uint32_t)-3;   // (-3: k_redo_tight_block gave it a whole block)
         if (lane == 0) { res->status = (bad_kind == (uint32_t)-2 || short_room) ? ST_DSTSMALL : ST_GENERIC; res->first_bad_block = first_bad; }
         return;
     }

@@ -10,7 +10,8 @@ as /usr/lib/x86_64-linux-gnu/liblz4.so.1 (v1.9.3), so this script drives it thro
 and records what it produces.  The output (tests/golden/golden.json + a few .lz4 files) is
 committed; the GPU box needs neither liblz4 nor /root/reference.
 
-Run:  python oracle/mint_golden.py         (only here, never at test time)
+Run:  python oracle/mint_golden.py            (only here, never at test time)
+      python oracle/mint_golden.py grammar    (only tests/golden/grammar.json and the HC frames)
 """
 from __future__ import annotations
 
@@ -55,6 +56,8 @@ for name, res, args in [
     ("LZ4F_freeDecompressionContext", c_size_t, [c_void_p]),
     ("LZ4F_getFrameInfo", c_size_t, [c_void_p, ctypes.POINTER(FrameInfo), c_void_p, ctypes.POINTER(c_size_t)]),
     ("LZ4F_decompress", c_size_t, [c_void_p, c_void_p, ctypes.POINTER(c_size_t), c_void_p, ctypes.POINTER(c_size_t), c_void_p]),
+    ("LZ4F_compressFrame", c_size_t, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(Prefs)]),
+    ("LZ4F_compressFrameBound", c_size_t, [c_size_t, ctypes.POINTER(Prefs)]),
     ("LZ4_compress_default", ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int]),
     ("LZ4_versionNumber", ctypes.c_int, []),
 ]:
@@ -315,5 +318,86 @@ def main():
           len(G["frames"]), "frames,", len(G["malformed"]), "malformed cases")
 
 
+def lz4f_decompress_once(frame: bytes, dst_cap: int):
+    """ONE LZ4F_decompress call with the whole frame and dst_cap bytes of room: (error | None, out, consumed, hint)."""
+    ctx = c_void_p()
+    chk(L.LZ4F_createDecompressionContext(ctypes.byref(ctx), 100))
+    try:
+        dst = ctypes.create_string_buffer(max(dst_cap, 1))
+        ds, ss = c_size_t(dst_cap), c_size_t(len(frame))
+        r = L.LZ4F_decompress(ctx, dst, ctypes.byref(ds), frame, ctypes.byref(ss), None)
+        if L.LZ4F_isError(r):
+            return L.LZ4F_getErrorName(r).decode(), None, ss.value, None
+        return None, dst.raw[:ds.value], ss.value, r
+    finally:
+        L.LZ4F_freeDecompressionContext(ctx)
+
+
+def lz4f_decompress_pieces(frame: bytes, seed: int):
+    """LZ4F_decompress fed 1..300 bytes of frame and 1..500 bytes of room per call: (error | None, out, consumed)."""
+    rng = np.random.default_rng(seed)
+    ctx = c_void_p()
+    chk(L.LZ4F_createDecompressionContext(ctypes.byref(ctx), 100))
+    try:
+        out, pos = bytearray(), 0
+        src = ctypes.create_string_buffer(frame, len(frame))
+        dst = ctypes.create_string_buffer(512)
+        while True:
+            sn, dn = int(rng.integers(1, 301)), int(rng.integers(1, 501))
+            ss, ds = c_size_t(min(sn, len(frame) - pos)), c_size_t(dn)
+            r = L.LZ4F_decompress(ctx, dst, ctypes.byref(ds), ctypes.byref(src, pos), ctypes.byref(ss), None)
+            if L.LZ4F_isError(r):
+                return L.LZ4F_getErrorName(r).decode(), None, pos
+            out += dst.raw[:ds.value]; pos += ss.value
+            if r == 0:
+                return None, bytes(out), pos
+            if pos >= len(frame) and ds.value == 0:
+                return "TRUNCATED", None, pos
+    finally:
+        L.LZ4F_freeDecompressionContext(ctx)
+
+
+def verdicts(name: str, frame: bytes, content: int) -> dict:
+    """liblz4's verdicts on one frame: one call with room = content, and fed in small pieces."""
+    import zlib
+    e, out, used, hint = lz4f_decompress_once(frame, content)
+    once = {"error": e if e is not None or hint == 0 else "INCOMPLETE(hint=%d)" % hint,
+            "out_sha256": sha(out) if e is None and hint == 0 else None, "consumed": used}
+    e, out, used = lz4f_decompress_pieces(frame, zlib.crc32(name.encode()))
+    pieces = {"error": e, "out_sha256": sha(out) if out is not None else None, "consumed": used}
+    return {"frame_sha256": sha(frame), "frame_len": len(frame), "content": content, "once": once, "pieces": pieces}
+
+
+HC_FRAMES = {"hc9_indep256k_bck": (9, dict(bsid=5, indep=1, bck=1)), "hc12_indep256k_bck": (12, dict(bsid=5, indep=1, bck=1)),
+             "hc9_linked64k": (9, dict(bsid=4, indep=0)), "hc12_linked64k": (12, dict(bsid=4, indep=0))}
+
+
+def mint_grammar():
+    """tests/golden/grammar.json: liblz4's verdict on every frame of tests/lz4_grammar.py, and liblz4 HC frames of the
+    project's own sources (zero-literal sequences, 4-byte matches and far offsets in bulk) as files beside it."""
+    import lzma
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lz4_grammar
+    G = {"liblz4_version": L.LZ4_versionNumber(), "numpy": np.__version__, "cases": {}, "hc": {}}
+    for name, frame, meta in lz4_grammar.corpus():
+        G["cases"][name] = verdicts(name, frame, meta["content"])
+    text = lzma.decompress(open(os.path.join(OUT, "project_sources.txt.xz"), "rb").read())
+    for name, (level, kw) in HC_FRAMES.items():
+        p = mkprefs(**kw); p.compressionLevel = level
+        cap = chk(L.LZ4F_compressFrameBound(len(text), ctypes.byref(p)))
+        buf = ctypes.create_string_buffer(cap)
+        n = chk(L.LZ4F_compressFrame(buf, cap, text, len(text), ctypes.byref(p)))
+        fr = buf.raw[:n]
+        open(os.path.join(OUT, name + ".lz4"), "wb").write(fr)
+        v = verdicts(name, fr, len(text))
+        assert v["once"]["out_sha256"] == sha(text) == v["pieces"]["out_sha256"], name
+        G["hc"][name] = dict(v, level=level, prefs=kw, file=name + ".lz4", input_sha256=sha(text))
+    with open(os.path.join(OUT, "grammar.json"), "w") as f:
+        json.dump(G, f, indent=1, sort_keys=True)
+    print("wrote", os.path.join(OUT, "grammar.json"), len(G["cases"]), "cases,", len(G["hc"]), "HC frames")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] != ["grammar"]:
+        main()
+    mint_grammar()

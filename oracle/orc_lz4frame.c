@@ -265,10 +265,25 @@ size_t orc_decompress_frame(const uint8_t* src, size_t n, uint8_t* dst, size_t c
             if (cap - op < csz) return err(ORC_ERR_dstMaxSize_tooSmall);
             memcpy(dst + op, src + pos, csz); produced = csz;
         } else {
-            size_t const room = cap - op < bs ? cap - op : bs;
+            /* liblz4's verdict: a block is judged against room = maxBlockSize whatever the caller's capacity; the capacity
+               only bounds the writes.  Less than a block of room left: decode into a block-sized buffer (with the history
+               in front for a linked frame) and copy out what fits -- LZ4F_decompress's tmpOut.  liblz4 1.9.3 names a block
+               that fails to decode ERROR_GENERIC when it decodes straight into dst and ERROR_decompressionFailed when it
+               decodes into tmpOut; so does this. */
             size_t const dict = (fi.blockMode == 0) ? (op < KB64 ? op : KB64) : 0;
-            int const r = orc_lz4_decompress_safe(src + pos, dst + op, (int)csz, (int)room, dict);
-            if (r < 0) return err(room < bs ? ORC_ERR_dstMaxSize_tooSmall : ORC_ERR_GENERIC);
+            int r;
+            if (cap - op >= bs) r = orc_lz4_decompress_safe(src + pos, dst + op, (int)csz, (int)bs, dict);
+            else {
+                uint8_t* const tmp = (uint8_t*)malloc(dict + bs);
+                if (!tmp) return err(ORC_ERR_allocation_failed);
+                memcpy(tmp, dst + op - dict, dict);
+                r = orc_lz4_decompress_safe(src + pos, tmp + dict, (int)csz, (int)bs, dict);
+                if (r >= 0 && (size_t)r <= cap - op) memcpy(dst + op, tmp + dict, (size_t)r);
+                free(tmp);
+                if (r < 0) return err(ORC_ERR_decompressionFailed);
+                if ((size_t)r > cap - op) return err(ORC_ERR_dstMaxSize_tooSmall);
+            }
+            if (r < 0) return err(ORC_ERR_GENERIC);
             produced = (size_t)r;
         }
         if (fi.contentChecksumFlag) orc_xxh32_update(&xxh, dst + op, produced);

@@ -12,6 +12,7 @@ import pytest
 import oracle
 from conftest import golden_file
 from lz4_frame_conduit_amd import _ffi, conduit, datagen
+from lz4_grammar import lz4_seq
 
 pytestmark = pytest.mark.gpu
 
@@ -1240,20 +1241,7 @@ def test_foreign_big_independent_blocks_stretch_parallel(L):
     assert not diff, diff[:5]
 
 
-def _lz4_seq(lit: bytes, mlen: int, off: int) -> bytes:
-    """One LZ4 sequence (token, literal length bytes, literals, offset, match length bytes); mlen == 0: the block's last, literals only."""
-    def ext(v):
-        out = bytearray()
-        while v >= 255: out.append(255); v -= 255
-        out.append(v); return bytes(out)
-    ll, ml = len(lit), (mlen - 4 if mlen else 0)
-    b = bytearray([(min(ll, 15) << 4) | min(ml, 15)])
-    if ll >= 15: b += ext(ll - 15)
-    b += lit
-    if mlen:
-        b += bytes([off & 255, off >> 8])
-        if ml >= 15: b += ext(ml - 15)
-    return bytes(b)
+_lz4_seq = lz4_seq                  # (tests/lz4_grammar.py)
 
 
 def _dense_block(n_out: int, seed: int, specials: bool):
