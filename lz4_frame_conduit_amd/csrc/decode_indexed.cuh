@@ -73,6 +73,32 @@ __global__ void k_check_index(const void* __restrict__ ix, uint64_t ix_size, uin
     if (!ok) atomicOr(flags, 1u);
 }
 
+// The index's block table, judged for the whole grid before any kernel behind writes a descriptor or an output byte: a lane per
+// block.  The descriptor ranges [seq_base, seq_base + nseq) and the entry ranges must tile [0, total) of the header exactly - the
+// first at 0, each where the one before ends, the last at the total - so every descriptor lies inside the workspace k_check_index
+// sized and belongs to one block only.  Stored blocks claim nothing, compressed blocks at least one sequence and one entry.  The
+// copy kernels check their own block's links as well; those verdicts come too late to stop a neighbour's writes (a table that
+// breaks one link and shifts every block behind it would send those workgroups' descriptors past the workspace).
+__global__ __launch_bounds__(256) void k_check_blocks(const void* __restrict__ ix, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
+                                                      uint32_t n_max, uint32_t* __restrict__ flags)
+{
+    if (res->status != ST_OK || *flags) return;                          // (k_check_index refused the header: nothing behind reads the table)
+    const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    const uint64_t n_seqs = flags[9], n_entries = flags[8];
+    const IxBlock* blocks = ix_blocks(ix);
+    const IxBlock bk = blocks[b];
+    const bool stored = (table[b].word >> 31) != 0;
+    bool wrong = stored ? (bk.nseq != 0 || bk.nentries != 0) : (bk.nseq == 0 || bk.nentries == 0);
+    const uint64_t seq_end = (uint64_t)bk.seq_base + bk.nseq, ent_end = (uint64_t)bk.entry_base + bk.nentries;
+    wrong |= seq_end > n_seqs || ent_end > n_entries;
+    if (b == 0) wrong |= bk.seq_base != 0 || bk.entry_base != 0;
+    if (b + 1 < n) { const IxBlock nb = blocks[b + 1]; wrong |= nb.seq_base != seq_end || nb.entry_base != ent_end; }
+    else wrong |= seq_end != n_seqs || ent_end != n_entries;
+    if (wrong) atomicOr(flags, 1u);
+}
+
 // `my_nseq` sequences of the payload in[0, csize) from `pos` on (output position `op`): their descriptors -> out[0 .. my_nseq).
 // Input-side rules only.  Returns true when something is wrong; `pos` is left where the walk ended (the caller checks that it
 // is where the next run starts).  `is_tail`: the run holds the block's last sequence.  `out_front`: output bytes in front of the
@@ -1045,7 +1071,9 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
             got = fz_decode_block<C, true>(sh, frame + e.src_off, csz, dst + e.dst_off, e.dst_size, e.dst_off + hist0, frame, prof, desc + blk.seq_base, blk.nseq,
                                            dsrc ? dsrc + blk.seq_base : nullptr, e.src_off, g > 0 ? done + (g - 1) : nullptr, own_front, b == b0);
         }
-        if (got < 0) failed = true;
+        // the blocks sit where the table puts them (a trailer's table: every block but the last full).  A block that decoded to less than
+        // the distance to the next one (a flushed block of liblz4's) would leave a gap: the generic linked decoder takes the frame
+        if (got < 0 || (b + 1 < n && e.dst_off + (uint32_t)got != table[b + 1].dst_off)) failed = true;
         else { if (tid == 0) table[b].dst_size = (uint32_t)got; last_size = (uint32_t)got; own_front = own_front + last_size < (1u << 30) ? own_front + last_size : (1u << 30); }
     }
     __syncthreads();

@@ -654,6 +654,9 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
                 tick(8, false);
                 hipLaunchKernelGGL(k_check_index, dim3(1), dim3(64), 0, st, (const void*)d_index, (uint64_t)index_size, n_ix, cpb, chunk,
                                    (uint64_t)ix_seq_cap, (uint32_t*)seqcnt.p, (const ResultRec*)d_res);
+                // the whole block table, before any kernel behind writes (the index is input)
+                hipLaunchKernelGGL(k_check_blocks, dim3((n_ix + 255) / 256), dim3(256), 0, st, (const void*)d_index, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix,
+                                   (uint32_t*)seqcnt.p);
                 uint32_t n_lanes = ix_entries_hint > n_ix ? ix_entries_hint : n_ix;           // (grid-stride inside: a hint is enough)
                 // Independent blocks that are not dense (no tracer on offer): ONE kernel - the copy workgroup's first wave parses its block's
                 // runs and resolves direct matches while the copiers move bytes (decode_indexed.cuh: k_copy_selffed)

@@ -72,6 +72,7 @@ class Frame:
         self.rng = rng
         self.short_mid = False                          # a block shorter than maxBlockSize that is not the last
         self._last_short = False
+        self.planted = []                               # per block: its sequences as written (in_off, out_pos, lit, mlen, off); None: stored or raw
 
     def header(self) -> bytes:
         flg = (1 << 6) | ((0 if self.linked else 1) << 5) | (int(self.bck) << 4) | (int(self.cck) << 2)
@@ -89,10 +90,12 @@ class Frame:
         return Block(self)
 
     def stored(self, data: bytes, word_size: int | None = None):
+        self.planted.append(None)
         self._emit((len(data) if word_size is None else word_size) | 0x80000000, data, len(data))
         self.out += data
 
-    def raw_block(self, payload: bytes, produced: int, word: int | None = None):
+    def raw_block(self, payload: bytes, produced: int, word: int | None = None, seqs=None):
+        self.planted.append(seqs)
         self._emit(len(payload) if word is None else word, payload, produced)
 
     def bytes(self) -> bytes:
@@ -106,6 +109,7 @@ class Block:
 
     def __init__(self, fr: Frame):
         self.fr, self.start, self.body = fr, len(fr.out), bytearray()
+        self.seqs = []                                  # (payload offset of the token, output position, literals, match length, offset)
 
     @property
     def op(self) -> int:
@@ -121,6 +125,7 @@ class Block:
 
     def s(self, lit, mlen: int, off: int):
         lit = self.lits(lit) if isinstance(lit, int) else lit
+        if self.seqs is not None: self.seqs.append((len(self.body), self.op, len(lit), mlen, off))
         self.body += lz4_seq(lit, mlen, off)
         out = self.fr.out
         out += lit
@@ -135,17 +140,19 @@ class Block:
         return self
 
     def raw(self, b: bytes):
+        self.seqs = None                                # (hand-made bytes: no planted list for this block)
         self.body += b
         return self
 
     def end(self, lit=0, word: int | None = None):
         lit = self.lits(lit) if isinstance(lit, int) else lit
+        if self.seqs is not None: self.seqs.append((len(self.body), self.op, len(lit), 0, 0))
         self.body += lz4_seq(lit, 0, 0)
         self.fr.out += lit
         self.close(word)
 
     def close(self, word: int | None = None):
-        self.fr.raw_block(bytes(self.body), self.op, word)
+        self.fr.raw_block(bytes(self.body), self.op, word, self.seqs if word is None else None)
 
     # ---- fillers: sequences up to `target` output bytes of this block
     def sparse(self, target: int):
@@ -385,9 +392,10 @@ def _frames():
 
 
 def corpus():
-    """[(name, frame bytes, meta)] - meta: bs, linked, short_mid, content (bytes the frame is meant to decode to)."""
+    """[(name, frame bytes, meta)] - meta: bs, linked, short_mid, content (bytes the frame is meant to decode to), planted (per
+    block: the sequences as written, None for stored and hand-made blocks)."""
     out = []
     for name, fr in _frames():
         fb = fr.bytes()
-        out.append((name, fb, dict(bs=fr.bs, linked=fr.linked, short_mid=fr.short_mid, content=len(fr.out))))
+        out.append((name, fb, dict(bs=fr.bs, linked=fr.linked, short_mid=fr.short_mid, content=len(fr.out), planted=fr.planted)))
     return out

@@ -665,6 +665,10 @@ def test_indexed_decode_same_bytes_as_generic(L, monkeypatch, selffeed):
             eng.decompress_blocks_async(frame, r.size, back, table, nb, p.frameInfo, index)
             r2 = eng.result()
             assert r2.size == src.numel() and torch.equal(back, src), (name, kw)
+            # a usable index with sequences ("tiny": one stored block, nothing to index), where the indexed kernels run ('f' mode): used
+            if hd[0] == 0x3258494C and hd[3] > 0 and (bsid >= 5 or not indep):
+                path = int(r2.flags) >> 12
+                assert path & PATH["indexed"] and not path & PATH["dropped"], (name, kw, hex(path))
             back.zero_()
             eng.decompress_blocks_async(frame, r.size, back, table, nb, p.frameInfo)
             r3 = eng.result()
