@@ -65,7 +65,8 @@ typedef struct {
 /* CTypes.hsc:202-232 (Preferences): 56 bytes; offsets 0,32,36,40,44 */
 typedef struct {
     LZ4F_frameInfo_t frameInfo;
-    int      compressionLevel;   /* only level <= 2 ("fast") exists here; the reference pins 0 (Conduit.hsc:260) */
+    int      compressionLevel;   /* <= 2: the fast encoder; 3..12: high compression (hash-chain search, lazy parse; equal input ->
+                                    equal bytes); > 12 is 12.  favorDecSpeed is accepted and ignored.  The reference pins 0 (Conduit.hsc:260) */
     unsigned autoFlush;
     unsigned favorDecSpeed;
     unsigned reserved[3];

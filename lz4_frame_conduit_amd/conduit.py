@@ -26,12 +26,14 @@ def lz4DefaultPreferences() -> Preferences:           # Conduit.hsc:248-263
 
 
 def make_preferences(blockSizeID=LZ4F_default, blockMode=LZ4F_blockLinked, contentChecksum=0, blockChecksum=0,
-                     contentSize=0, dictID=0, autoFlush=0) -> Preferences:
+                     contentSize=0, dictID=0, autoFlush=0, compressionLevel=0) -> Preferences:
+    """compressionLevel: <= 2 the fast encoder; 3-12 the high-compression levels (smaller frames, slower); above 12 is 12."""
     p = Preferences()
     p.frameInfo.blockSizeID, p.frameInfo.blockMode = blockSizeID, blockMode
     p.frameInfo.contentChecksumFlag, p.frameInfo.blockChecksumFlag = contentChecksum, blockChecksum
     p.frameInfo.contentSize, p.frameInfo.dictID = contentSize, dictID
     p.autoFlush = autoFlush
+    p.compressionLevel = compressionLevel
     return p
 
 

@@ -212,7 +212,6 @@ void compressBatched(size_t batchBytes, const LZ4F_preferences_t* prefsIn, const
 {
     LZ4F_preferences_t prefs; memset(&prefs, 0, sizeof(prefs));
     if (prefsIn) prefs = *prefsIn;
-    if (prefs.compressionLevel > 2) handleLz4Error(make_err(LZ4F_ERROR_compressionLevel_invalid));
     if (prefs.frameInfo.blockSizeID == 0) prefs.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(prefs.frameInfo.blockSizeID);
     if (!bs) handleLz4Error(make_err(LZ4F_ERROR_maxBlockSize_invalid));
@@ -237,7 +236,7 @@ void compressBatched(size_t batchBytes, const LZ4F_preferences_t* prefsIn, const
         const size_t cap = n + (n / bs + 2) * 8 + 64;
         out.ensure(cap);
         size_t w = 0;
-        handleLz4Error(pipe_compress_blocks(in.p + HIST, n, (uint32_t)bs, linked, bck, out.p, out.cap, &w, hist));
+        handleLz4Error(pipe_compress_blocks(in.p + HIST, n, (uint32_t)bs, linked, bck, out.p, out.cap, &w, hist, prefs.compressionLevel));
         if (blockList && !bl.add_blocks(out.p, w, framePos, bck)) handleLz4Error(make_err(LZ4F_ERROR_GENERIC));
         framePos += w;
         if (w) yield(Slice{out.p, w});

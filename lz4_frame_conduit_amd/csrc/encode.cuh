@@ -54,6 +54,8 @@ struct EncGeom {
     uint32_t seed_stride;        // pass E1: a run's 64 KiB of history go into the table at every seed_stride-th position
     uint32_t tiles_per_wg;       // pass E1: consecutive chunks a workgroup takes
     uint32_t e1_solo;            // (development) pass E1: bit 0 - only the workgroup's first wave parses (the sequential parse, for comparing ratios); bit 1 - nothing is parsed (the cost of everything else)
+    uint32_t hc_attempts;        // levels 3-12 (encode_hc.cuh): chain candidates a position's search looks at (0: level <= 2, pass E1 of this file)
+    uint32_t hc_lazy;            // levels 3-12: positions the lazy parse looks ahead (1 or 2)
 };
 
 // The record workspace: [control: bump pointer, tiles that found the pool empty | u32 per chunk: where its list starts | the pool].

@@ -1,0 +1,255 @@
+// encode_hc.cuh -- pass E1 for compression levels 3-12 (LZ4HC's levels): a hash-chain match finder with a lazy parse.
+//
+// One workgroup (16 waves) per 64 KiB chunk, which fills the chunk's ChunkInfo and record list exactly as pass E1 of encode.cuh and
+// the deterministic finder of encode_solo.cuh do: passes S and E2, the raw fallback, checksums and the sequence index do not know the
+// difference.  Matches reach up to 64 KiB back (into the block's earlier chunks, and across block starts when linked), end at the
+// chunk's end, and keep Appendix A.2's end-of-block rules.
+//
+// LDS ("High-compression levels"):
+//   chain  65536 + 1920 x u16   chain[q % HC_RING] = distance from q back to the previous position whose 4 bytes hash alike (0: none)
+//   head    8 K x u16    16 KiB   per hash: the low 16 bits of the last position inserted
+//   res  3 x 960 x u32   11.25 KiB per position of the last three batches: the best match found (length, offset, bytes it extends back)
+// The 128 KiB input window stays in memory (L2): it does not fit beside the chain, and a candidate is checked with one 4-byte load.
+//
+// The window [chunk start - 64 KiB, chunk end) is walked in batches of HC_T = 960 positions.  In iteration i, all behind one barrier:
+//   wave 0      inserts batch i into head/chain (in position order: the lanes of a group of 64 find the lane before them with the same
+//               hash by ballots), then parses what the searchers have finished (batches <= i-2) into records;
+//   waves 1-15  search batch i-1, a lane per position: the chain is walked for at most `attempts` candidates, and the longest match
+//               (the nearest among equals) is kept.
+// The builder writes the chain slots of batch i, which are the slots of positions HC_RING before it: the ring is two batches longer
+// than 64 KiB, so those are out of reach of every position the searchers look at (full reach: 65535 bytes).  No wave ever reads what
+// another writes in the same iteration, so the records are a function of the input, its history and the level alone: nothing depends
+// on timing or on the pool.
+#pragma once
+#include "encode.cuh"
+
+namespace lz4f {
+
+constexpr uint32_t HC_WAVES = 16, HC_T = 64 * (HC_WAVES - 1), HC_HASH_LOG = 13, HC_RING = 65536 + 2 * HC_T;
+constexpr uint32_t HC_CAP = 258;          // longest match length a search records (8 bits: length - 3); the parse extends longer ones
+constexpr uint32_t HC_BACK_CAP = 255;     // bytes a search records that its match extends backwards (8 bits)
+constexpr uint32_t HC_LOOK = 2;           // positions the lazy parse looks ahead
+
+// Level -> search attempts per position and lazy depth (1: one position ahead, 2: also two ahead).  Chosen by measured frame size
+// against liblz4 1.9.3 at the same level (DESIGN.md section 4 has the sweep): 32 attempts with the one-ahead parse already meet level 3
+// (real text x1.000-1.002, Zipf text x0.99); from level 6 the two-ahead parse, and attempts up to where more stop paying: on real text
+// 256 -> 512 -> 2048 -> 8192 attempts gave x1.009 -> 1.007 -> 1.005 -> 1.0046 of liblz4's level-6 size at 1.0x, 1.3x, 3.3x, 11x the time.
+// Levels above 12 are level 12.
+struct HcLevel { uint32_t attempts, lazy; };
+__host__ __device__ inline HcLevel hc_level(int level)
+{
+    const uint32_t att[10] = {32, 48, 64, 256, 384, 512, 1024, 2048, 4096, 8192};
+    if (level < 3) level = 3;
+    if (level > 12) level = 12;
+    return HcLevel{att[level - 3], level >= 6 ? 2u : 1u};
+}
+
+struct alignas(16) HcShared {
+    uint16_t chain[HC_RING];
+    uint16_t head[1u << HC_HASH_LOG];
+    uint32_t res[3][HC_T];
+};
+static_assert(sizeof(HcShared) <= 163840, "one workgroup per CU");
+static_assert(HC_RING >= 65535 + 2 * HC_T, "the builder's slots are out of the searchers' reach");
+
+__device__ __forceinline__ uint32_t hc_hash(uint32_t v) { return (v * 2654435761u) >> (32 - HC_HASH_LOG); }
+__device__ __forceinline__ uint32_t hc_len(uint32_t r) { return r ? (r >> 24) + 3 : 0; }
+__device__ __forceinline__ uint32_t hc_off(uint32_t r) { return r & 0xFFFFu; }
+__device__ __forceinline__ uint32_t hc_back(uint32_t r) { return (r >> 16) & 0xFFu; }
+
+// grid: one workgroup of 64 * HC_WAVES threads per chunk; g.hc_attempts / g.hc_lazy from hc_level()
+__global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t* __restrict__ src, EncGeom g,
+                                                                  ChunkInfo* __restrict__ info, uint64_t* __restrict__ recs)
+{
+    __shared__ HcShared sh;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
+    const uint32_t chunk = blockIdx.x;
+    if (chunk >= g.n_chunks) return;
+
+    const uint32_t blk = chunk / g.chunks_per_block, cib = chunk % g.chunks_per_block;
+    const uint64_t bstart = g.first_off + (uint64_t)blk * g.block_size;
+    const uint64_t bend_abs = (bstart + g.block_size < g.src_size) ? bstart + g.block_size : g.src_size;
+    const uint64_t cs_abs = bstart + (uint64_t)cib * g.chunk_size;
+    ChunkInfo* ci = info + chunk;
+    if (cs_abs >= bend_abs) {               // chunk beyond a short last block
+        if (tid == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = 0; ci->body_size = 0; }
+        return;
+    }
+    const uint64_t ce_abs = (cs_abs + g.chunk_size < bend_abs) ? cs_abs + g.chunk_size : bend_abs;
+    const uint64_t low_abs = g.linked ? 0 : bstart;                  // matches may not start before this
+    const uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
+    const uint8_t* base = src + (cs_abs - back);                     // position 0 of the window
+    const uint8_t* rd_end = src + g.src_size;                        // nothing is read at or beyond this
+    const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
+    const uint32_t bend = back + (uint32_t)(bend_abs - cs_abs);
+    // (a place of its own in the pool for this chunk's list: the engine sizes the pool for the worst case at these levels)
+    const uint64_t rec_at = (uint64_t)chunk * g.max_rec_per_chunk;
+    const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
+    uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
+    if (tid == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
+
+    // a match may start at p iff cs <= p <= last_start, and may end at end_lim (as in encode_solo.cuh)
+    const uint32_t blen = (uint32_t)(bend_abs - bstart), clen = ce - cs;
+    bool searchable = blen >= MFLIMIT + 1 && clen >= MINMATCH && rec_room;
+    uint32_t last_start = 0, end_lim = 0;
+    if (searchable) {
+        last_start = (ce - MINMATCH < bend - MFLIMIT) ? ce - MINMATCH : bend - MFLIMIT;
+        end_lim = (ce < bend - LASTLIT) ? ce : bend - LASTLIT;
+        searchable = last_start >= cs;
+    }
+    if (!searchable) {
+        if (tid == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = ce - cs; ci->body_size = 0; }
+        return;
+    }
+    const uint32_t attempts = g.hc_attempts ? g.hc_attempts : 1u, lazy = g.hc_lazy;
+
+    for (uint32_t k = tid; k < (1u << HC_HASH_LOG) / 2; k += 64 * HC_WAVES) ((uint32_t*)sh.head)[k] = 0;
+    __syncthreads();
+
+    const uint32_t insert_end = last_start + 1;                      // positions that can be a candidate (< some p <= last_start)
+    const uint32_t nbatch = (insert_end + HC_T - 1) / HC_T;
+    const uint64_t lt_mask = (1ull << lane) - 1;
+
+    // parse state (wave 0; wave-uniform)
+    uint32_t p = cs, anchor = cs, nrec = 0, first_lit = 0, body = 0;
+
+    for (uint32_t it = 0; it <= nbatch + 1; it++) {
+        if (wave == 0) {
+            // ---- build: insert batch `it` in position order ----
+            if (it < nbatch) {
+                constexpr uint32_t G = HC_T / 64;
+                uint32_t vv[G];
+#pragma unroll
+                for (uint32_t k = 0; k < G; k++) { const uint32_t pos = it * HC_T + k * 64 + lane; vv[k] = pos < insert_end ? ld32(base + pos) : 0u; }
+#pragma unroll 1
+                for (uint32_t k = 0; k < G; k++) {
+                    const uint32_t pos0 = it * HC_T + k * 64;
+                    if (pos0 >= insert_end) break;
+                    const uint32_t pos = pos0 + lane;
+                    const bool valid = pos < insert_end;
+                    const uint32_t h = hc_hash(vv[k]);
+                    // the lane before me with my hash, and whether I am the last with it
+                    uint64_t act = __ballot(valid);
+                    uint32_t prev_lane = 64;
+                    bool is_last = false;
+                    while (act) {
+                        const uint32_t L = (uint32_t)__builtin_ctzll(act);
+                        const uint32_t hl = __builtin_amdgcn_readlane(h, L);
+                        const bool mine = valid && h == hl;
+                        const uint64_t m = __ballot(mine);
+                        if (mine) {
+                            const uint64_t below = m & lt_mask;
+                            prev_lane = below ? 63u - (uint32_t)__builtin_clzll(below) : 64u;
+                            is_last = (m >> lane) == 1ull;
+                        }
+                        act &= ~m;
+                    }
+                    const uint32_t hd = valid ? sh.head[h] : 0u;
+                    if (valid) {
+                        const uint32_t d = prev_lane < 64 ? lane - prev_lane : ((pos - hd) & 0xFFFFu);
+                        sh.chain[pos % HC_RING] = (uint16_t)d;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    if (valid && is_last) sh.head[h] = (uint16_t)pos;
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+            // ---- parse what is searched: positions < known_end have results ----
+            const bool fin = it == nbatch + 1;
+            const uint32_t known_end = fin ? 0xFFFFFFFFu : (it >= 1 ? (it - 1) * HC_T : 0u);
+            const uint32_t res_end = last_start + 1;                     // results beyond: no match
+            while (p <= last_start && (fin || p + HC_LOOK < known_end) && nrec < g.max_rec_per_chunk) {
+                const uint32_t w0 = p;
+                const uint32_t x = w0 + lane;
+                uint32_t v = 0;
+                if (x < res_end && (fin || x < known_end)) v = sh.res[(x / HC_T) % 3][x % HC_T];
+                // positions p in this window whose look-ahead is in the window and known
+                uint32_t wend = w0 + 64 - HC_LOOK;
+                if (!fin && known_end - HC_LOOK < wend) wend = known_end - HC_LOOK;
+                while (p < wend && nrec < g.max_rec_per_chunk) {
+                    const uint64_t bal = __ballot(v != 0 && x >= p && x < wend);
+                    if (!bal) { p = wend; break; }
+                    p = w0 + (uint32_t)__builtin_ctzll(bal);
+                    uint32_t c = __builtin_amdgcn_readlane(v, p - w0);
+                    bool moved = false;
+                    while (hc_len(c) < HC_CAP) {
+                        const uint32_t c1 = __builtin_amdgcn_readlane(v, p + 1 - w0);
+                        if (hc_len(c1) > hc_len(c)) { p += 1; c = c1; moved = true; }
+                        else if (lazy >= 2 && hc_len(__builtin_amdgcn_readlane(v, p + 2 - w0)) > hc_len(c) + 1) { p += 2; c = __builtin_amdgcn_readlane(v, p - w0); moved = true; }
+                        else break;
+                        if (p >= wend) break;
+                    }
+                    if (moved && p >= wend) break;                       // (its look-ahead is beyond the window: decided again after the reload)
+                    uint32_t mlen = hc_len(c);
+                    const uint32_t off = hc_off(c);
+                    uint32_t bk = hc_back(c);
+                    if (bk > p - anchor) bk = p - anchor;
+                    uint32_t mp = p - bk;
+                    if (mlen >= HC_CAP) {
+                        // a long match: go on from its recorded end, 512 bytes per round (wave-wide, like encode_solo.cuh)
+                        while (true) {
+                            const uint32_t b0 = p + mlen + lane * 8;
+                            uint64_t y0 = 0;
+                            if (b0 < end_lim) y0 = ld64_guard(base + b0, rd_end) ^ ld64_guard(base + (b0 - off), rd_end);
+                            uint32_t h0 = 0;
+                            if (b0 < end_lim) { h0 = y0 ? (uint32_t)(__builtin_ctzll(y0) >> 3) : 8; const uint32_t r = end_lim - b0; if (h0 > r) h0 = r; }
+                            const uint64_t s0 = __ballot(h0 < 8);
+                            if (s0) { const uint32_t f = (uint32_t)__builtin_ctzll(s0); mlen += f * 8 + __builtin_amdgcn_readlane(h0, f); break; }
+                            mlen += WAVE * 8;
+                        }
+                    }
+                    mlen += bk;
+                    const uint32_t lit = mp - anchor;
+                    if (lane == 0) rec[nrec] = pack_rec(lit, mlen, off);
+                    if (nrec == 0) first_lit = lit;
+                    body += seq_size(lit, mlen);
+                    nrec++;
+                    anchor = p = mp + mlen;
+                }
+            }
+        } else if (it >= 1 && it <= nbatch) {
+            // ---- search batch it-1: a lane per position ----
+            const uint32_t pos = (it - 1) * HC_T + (tid - 64);
+            uint32_t r = 0;
+            if (pos >= cs && pos <= last_start) {
+                const uint32_t qmin = pos >= 65535u ? pos - 65535u : 0u;
+                uint32_t maxlen = end_lim - pos;
+                if (maxlen > HC_CAP) maxlen = HC_CAP;
+                const uint32_t cur = ld32(base + pos);
+                uint32_t best = 0, boff = 0, q = pos, tail = 0;
+                for (uint32_t n = 0; n < attempts; n++) {
+                    const uint32_t d = sh.chain[q % HC_RING];
+                    if (d == 0 || d > q - qmin) break;
+                    q -= d;
+                    if (ld32(base + q) != cur) continue;
+                    if (best >= MINMATCH && ld32(base + q + best - 3) != tail) continue;
+                    uint32_t len = MINMATCH;
+                    while (len < maxlen) {
+                        const uint64_t y = ld64_guard(base + pos + len, rd_end) ^ ld64_guard(base + q + len, rd_end);
+                        if (y) { len += (uint32_t)(__builtin_ctzll(y) >> 3); break; }
+                        len += 8;
+                    }
+                    if (len > maxlen) len = maxlen;
+                    if (len > best) {
+                        best = len; boff = pos - q;
+                        if (best >= maxlen) break;
+                        tail = ld32(base + pos + best - 3);
+                    }
+                }
+                if (best >= MINMATCH) {
+                    // bytes the match extends backwards (bounded by the chunk's start and the window's)
+                    const uint32_t qb = pos - boff;
+                    uint32_t room = pos - cs; if (qb < room) room = qb; if (room > HC_BACK_CAP) room = HC_BACK_CAP;
+                    uint32_t bk = 0;
+                    while (bk < room && base[pos - 1 - bk] == base[qb - 1 - bk]) bk++;
+                    r = ((best - 3) << 24) | (bk << 16) | boff;
+                }
+                sh.res[(pos / HC_T) % 3][pos % HC_T] = r;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) { ci->nrec = nrec; ci->first_lit = first_lit; ci->tail_lit = ce - anchor; ci->body_size = body; }
+}
+
+}  // namespace lz4f

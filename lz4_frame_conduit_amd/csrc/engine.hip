@@ -96,6 +96,8 @@ void lz4f_mi355x_engine::Switches::read()
     wait_ticks = 0; if (const char* v = getenv("LZ4F_MI355X_WAIT_TICKS")) { unsigned long long a = 0; if (sscanf(v, "%llu", &a) == 1) wait_ticks = a; }
     dblk_lds = 0; if (const char* v = getenv("LZ4F_MI355X_DBLK_LDS")) { const int k = atoi(v); if (k > 0 && k <= 150) dblk_lds = (unsigned)k << 10; }      // (development: fewer wave-per-block decoders per CU)
     recs_per_tile = 0; if (const char* v = getenv("LZ4F_MI355X_RECS_PER_TILE")) { const int k = atoi(v); if (k >= 1 && k <= 16385) recs_per_tile = (unsigned)k; }
+    hc_attempts = 0; if (const char* v = getenv("LZ4F_MI355X_HC_ATTEMPTS")) { const int k = atoi(v); if (k >= 1 && k <= 65536) hc_attempts = (unsigned)k; }      // (development: levels 3-12 search this many candidates per position)
+    hc_lazy = 0; if (const char* v = getenv("LZ4F_MI355X_HC_LAZY")) { const int k = atoi(v); if (k >= 1 && k <= 2) hc_lazy = (unsigned)k; }
     seed = 2; if (const char* v = getenv("LZ4F_MI355X_SEED")) { unsigned a = 0; if (sscanf(v, "%u", &a) == 1 && a >= 1 && a <= 64) seed = a; }
 }
 namespace lz4f {
@@ -279,11 +281,18 @@ size_t lz4f_mi355x_engine::launch_compress(const CompressJob& j, uint8_t* d_dst,
     g.header_size = j.header_size; memcpy(g.header, j.header, j.header_size);
     g.max_rec_per_chunk = g.chunk_size / 4 + 1;
     g.seed_stride = sw.seed;
+    const bool hc = j.level >= 3;
+    if (hc) {
+        const HcLevel hl = hc_level(j.level);
+        g.hc_attempts = sw.hc_attempts ? sw.hc_attempts : hl.attempts;
+        g.hc_lazy = sw.hc_lazy ? sw.hc_lazy : hl.lazy;
+    }
 
     if (info.ensure((size_t)(g.n_chunks + 1) * sizeof(ChunkInfo))) return make_err(LZ4F_ERROR_allocation_failed);
     // (deterministic mode: the worst case for every tile - which tiles a short pool turns away is a matter of which workgroup's merge
     // gets to the bump pointer first, and "equal input, equal bytes" must not hang on that: 2 bytes of workspace per input byte)
-    g.rec_pool = rec_pool_records(g.n_chunks, g.max_rec_per_chunk, (sw.e1_solo & 1u) ? 16385u : sw.recs_per_tile);
+    // (levels 3-12 likewise: their output is a function of the input alone, so a chunk's list has a place of its own, encode_hc.cuh)
+    g.rec_pool = rec_pool_records(g.n_chunks, g.max_rec_per_chunk, ((sw.e1_solo & 1u) || hc) ? 16385u : sw.recs_per_tile);
     if (recs.ensure((size_t)(rec_pool_at(g.n_chunks) + g.rec_pool) * 8)) return make_err(LZ4F_ERROR_allocation_failed);
     if (blk_bytes.ensure((size_t)(g.n_blocks + 1) * 4)) return make_err(LZ4F_ERROR_allocation_failed);
     if (!d_table) { if (table.ensure((size_t)(g.n_blocks + 1) * sizeof(BlockOut))) return make_err(LZ4F_ERROR_allocation_failed); d_table = (lz4f_mi355x_block*)table.p; }
@@ -319,7 +328,10 @@ size_t lz4f_mi355x_engine::launch_compress(const CompressJob& j, uint8_t* d_dst,
             recs_ctl_clean = nullptr;
             // deterministic mode: a wave per chunk with a table of its own (encode_solo.cuh) - nothing shared, nothing that depends on timing.
             // (e1_solo bit 2: the shared kernel with one wave per workgroup parsing, the mode's form until round 4 - kept for comparison)
-            if ((sw.e1_solo & 1u) && !(sw.e1_solo & 4u))
+            // levels 3-12: the hash-chain finder, a workgroup per chunk (encode_hc.cuh) - deterministic too.
+            if (hc)
+                hipLaunchKernelGGL(k_find_matches_hc, dim3(g.n_chunks), dim3(64 * HC_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
+            else if ((sw.e1_solo & 1u) && !(sw.e1_solo & 4u))
                 hipLaunchKernelGGL((k_find_matches_solo<1>), dim3(g.n_chunks), dim3(64), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
             else
             hipLaunchKernelGGL(k_find_matches, dim3(n_wg), dim3(64 * E1_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p, (uint64_t*)e1_scratch.p);
@@ -929,7 +941,7 @@ static hipError_t staged_d2h(void* dst, void* pinned, const void* d_src, size_t 
 }
 
 size_t lz4f_mi355x_engine::slab_compress(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len, uint32_t block_size, bool linked,
-                                         bool block_checksum, bool src_pinned, size_t* size)
+                                         bool block_checksum, bool src_pinned, size_t* size, int level)
 {
     *size = 0;
     if (n == 0) return 0;
@@ -954,7 +966,7 @@ size_t lz4f_mi355x_engine::slab_compress(const uint8_t* src, size_t n, const uin
     }
     CompressJob j; memset(&j, 0, sizeof(j));
     j.d_src = (const uint8_t*)d_in.p; j.src_size = total; j.first_off = hist_len; j.block_size = block_size;
-    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0;
+    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0; j.level = level;
     size_t r = launch_compress(j, (uint8_t*)d_out.p, out_cap, (lz4f_mi355x_result*)res.p, nullptr);
     if (is_err(r)) return r;
     ResultRec* hr = (ResultRec*)((uint8_t*)h_small.p + 65536 + 64);
@@ -966,7 +978,7 @@ size_t lz4f_mi355x_engine::slab_compress(const uint8_t* src, size_t n, const uin
 }
 
 size_t lz4f_mi355x_engine::compress_block_pinned(const uint8_t* pin_src, size_t hist_len, size_t n, uint32_t block_size, bool linked, bool block_checksum,
-                                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size)
+                                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size, int level)
 {
     // (Kernels reading the staging buffer through the link themselves - no copies at all - were tried first: 510 us per 64 KiB block
     // against 190 us with copies.  A kernel's scattered 16-byte reads over PCIe are not what a DMA engine's are.)
@@ -983,7 +995,7 @@ size_t lz4f_mi355x_engine::compress_block_pinned(const uint8_t* pin_src, size_t 
     HIP_TRY(hipMemcpyAsync(d_in.p, pin_src, total, hipMemcpyHostToDevice, st));
     CompressJob j; memset(&j, 0, sizeof(j));
     j.d_src = (const uint8_t*)d_in.p; j.src_size = total; j.first_off = hist_len; j.block_size = block_size;
-    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0;
+    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0; j.level = level;
     lz4f_mi355x_result* d_res = (lz4f_mi355x_result*)((uint8_t*)d_out.p + res_at);
     size_t r = launch_compress(j, (uint8_t*)d_out.p, out_cap, d_res, nullptr);
     if (is_err(r)) return r;
@@ -1010,11 +1022,11 @@ size_t lz4f_mi355x_engine::slab_fetch(uint8_t* dst, size_t size, size_t d_off, b
 }
 
 size_t lz4f_mi355x_engine::compress_blocks_host(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len,
-                                                uint32_t block_size, bool linked, bool block_checksum, uint8_t* dst, size_t dst_cap, size_t* written)
+                                                uint32_t block_size, bool linked, bool block_checksum, uint8_t* dst, size_t dst_cap, size_t* written, int level)
 {
     *written = 0;
     size_t size = 0;
-    size_t r = slab_compress(src, n, hist, hist_len, block_size, linked, block_checksum, false, &size);
+    size_t r = slab_compress(src, n, hist, hist_len, block_size, linked, block_checksum, false, &size, level);
     if (is_err(r)) return r;
     if (size > dst_cap) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
     r = slab_fetch(dst, size, 0, false);
@@ -1302,13 +1314,13 @@ size_t lz4f_mi355x_dev_compressFrame(lz4f_mi355x_engine* e, void* d_dst, size_t 
     if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    if (p.compressionLevel > 2) { set_last_error("only the fast encoder (level <= 2) exists"); return make_err(LZ4F_ERROR_compressionLevel_invalid); }
     if (p.frameInfo.contentSize && p.frameInfo.contentSize != srcSize) return make_err(LZ4F_ERROR_frameSize_wrong);
     lz4f_mi355x_engine::CompressJob j; memset(&j, 0, sizeof(j));
     j.d_src = (const uint8_t*)d_src; j.src_size = srcSize; j.first_off = 0; j.block_size = (uint32_t)bs;
     j.linked = p.frameInfo.blockMode == LZ4F_blockLinked; j.block_checksum = p.frameInfo.blockChecksumFlag != 0; j.endmark = true;
     j.content_checksum = p.frameInfo.contentChecksumFlag != 0;
     j.header_size = (uint32_t)write_frame_header(j.header, p);
+    j.level = p.compressionLevel;
     return e->launch_compress(j, (uint8_t*)d_dst, dstCapacity, d_result, d_table);
 }
 
@@ -1339,13 +1351,13 @@ size_t lz4f_mi355x_dev_compressFrameIndexed(lz4f_mi355x_engine* e, void* d_dst, 
     if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    if (p.compressionLevel > 2) { set_last_error("only the fast encoder (level <= 2) exists"); return make_err(LZ4F_ERROR_compressionLevel_invalid); }
     if (p.frameInfo.contentSize && p.frameInfo.contentSize != srcSize) return make_err(LZ4F_ERROR_frameSize_wrong);
     lz4f_mi355x_engine::CompressJob j; memset(&j, 0, sizeof(j));
     j.d_src = (const uint8_t*)d_src; j.src_size = srcSize; j.first_off = 0; j.block_size = (uint32_t)bs;
     j.linked = p.frameInfo.blockMode == LZ4F_blockLinked; j.block_checksum = p.frameInfo.blockChecksumFlag != 0; j.endmark = true;
     j.content_checksum = p.frameInfo.contentChecksumFlag != 0;
     j.header_size = (uint32_t)write_frame_header(j.header, p);
+    j.level = p.compressionLevel;
     return e->launch_compress(j, (uint8_t*)d_dst, dstCapacity, d_result, d_table, d_index, inband ? LZ4F_MI355X_INBAND : (d_index ? indexCapacity : 0));
 }
 

@@ -73,7 +73,7 @@ struct lz4f_mi355x_engine {
         unsigned dense_mode;           // dense payloads in big independent blocks (LZ4F_MI355X_DENSE_MODE): 0 by block count, 1 workgroup per block (decode_relay.cuh), 2 wave per block
         unsigned group_kib;            // (development) bytes of consecutive small blocks of a linked frame a workgroup of the indexed copy kernel takes
         unsigned feed_round;           // (test switch) sequences per parse round of the self-feeding copy kernel's first wave
-        int chain_gate; char decode_mode; unsigned e1_run, e1_solo, seed, dblk_lds, recs_per_tile; unsigned long long wait_ticks;
+        int chain_gate; char decode_mode; unsigned e1_run, e1_solo, seed, dblk_lds, recs_per_tile, hc_attempts, hc_lazy; unsigned long long wait_ticks;
         void read();
     } sw;
     void*  recs_ctl_clean = nullptr;                       // == recs.p while the record pool's control words are known to be zero (or about to be: the last call's scan)
@@ -94,6 +94,7 @@ struct lz4f_mi355x_engine {
         uint32_t block_size; bool linked; bool block_checksum; bool endmark;
         bool content_checksum;                                   // (with endmark) XXH32 of the whole input behind the EndMark: k_xxh32_content
         uint8_t header[20]; uint32_t header_size;
+        int level;                                               // compressionLevel: <= 2 pass E1 (encode.cuh / encode_solo.cuh), 3-12 the hash-chain finder (encode_hc.cuh), > 12 as 12
     };
     // returns 0 or an LZ4F error; d_res/d_table may be null (internal buffers are used)
     size_t launch_compress(const CompressJob& j, uint8_t* d_dst, uint64_t dst_cap, lz4f_mi355x_result* d_res, lz4f_mi355x_block* d_table,
@@ -117,18 +118,18 @@ struct lz4f_mi355x_engine {
     // Encode `n` bytes at src (host) as frame blocks of block_size (last may be short); `hist` bytes of
     // history (host) precede them when linked.  Appends [size word][payload][checksum] per block to out.
     size_t compress_blocks_host(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len,
-                                uint32_t block_size, bool linked, bool block_checksum, uint8_t* dst, size_t dst_cap, size_t* written);
+                                uint32_t block_size, bool linked, bool block_checksum, uint8_t* dst, size_t dst_cap, size_t* written, int level = 0);
     // The same in two halves, for the pipelined bulk calls (pipeline.hip): upload + kernels + result (the blocks stay in d_out),
     // then the download.  `*_pinned`: the host buffer is page-locked, no staging copy.
     size_t slab_compress(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len, uint32_t block_size, bool linked, bool block_checksum,
-                         bool src_pinned, size_t* size);
+                         bool src_pinned, size_t* size, int level = 0);
     size_t slab_fetch(uint8_t* dst, size_t size, size_t d_off, bool dst_pinned);
     // One block (or a short run of them) out of page-locked host memory and back into it, no copy calls: the kernels read the input
     // (hist_len bytes of history, then n bytes) and write the block(s) and the result record through the link themselves.  What the
     // LZ4F_* streaming functions do per completed block (frame_host.cpp): upload, download and one of the two synchronisations of the
     // staged path are gone.  Both buffers from lz4f::PinBuf (hipHostMalloc).
     size_t compress_block_pinned(const uint8_t* pin_src, size_t hist_len, size_t n, uint32_t block_size, bool linked, bool block_checksum,
-                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size);
+                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size, int level = 0);
     size_t slab_decode(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries, const lz4f::ParsedHeader& ph,
                        const uint8_t* hist, size_t hist_len, bool src_pinned, size_t* got, uint8_t* fetch_to = nullptr, size_t fetch_room = 0);
     // Decode one compressed block payload (host; followed by its 4-byte checksum when bck) with `hist_len`
@@ -168,7 +169,7 @@ void   set_bulk_devices(int n);
 int    logical_devices();             // visible devices, or LZ4F_MI355X_LOGICAL_DEVICES when that is larger (test switch, pipeline.hip)
 // hist_before: valid input bytes in front of src (a linked frame's blocks reach 64 KiB back)
 size_t pipe_compress_blocks(const uint8_t* src, size_t n, uint32_t block_size, bool linked, bool bck, uint8_t* dst, size_t cap, size_t* written,
-                            size_t hist_before = 0);
+                            size_t hist_before = 0, int level = 0);
 // what a frame decoded batch by batch carries from one batch of blocks to the next (pipeline.hip)
 struct FrameCarry { Xxh32State cck; uint64_t out_total = 0; std::vector<uint8_t> hist; FrameCarry() { cck.reset(0); } };
 size_t pipe_decompress_frame(const uint8_t* frame, size_t n, const ParsedHeader& ph, uint8_t* flat, size_t flat_cap,

@@ -12,6 +12,7 @@
 #include "decode_linked.cuh"
 #include "encode.cuh"
 #include "encode_solo.cuh"
+#include "encode_hc.cuh"
 #include "decode_indexed.cuh"
 #include "decode_spx.cuh"
 

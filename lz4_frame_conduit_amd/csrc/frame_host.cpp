@@ -203,7 +203,8 @@ static size_t encode_blocks(LZ4F_cctx_s* c, uint8_t* dst, size_t cap, const uint
     if (is_err(r)) return r;
     size_t written = 0;
     r = eng->compress_blocks_host(src, n, c->hist_at(), c->hist_len, (uint32_t)c->block_size,
-                                  c->prefs.frameInfo.blockMode == LZ4F_blockLinked, c->prefs.frameInfo.blockChecksumFlag != 0, dst, cap, &written);
+                                  c->prefs.frameInfo.blockMode == LZ4F_blockLinked, c->prefs.frameInfo.blockChecksumFlag != 0, dst, cap, &written,
+                                  c->prefs.compressionLevel);
     if (is_err(r)) return r;
     push_history(c, src, n);
     return written;
@@ -222,7 +223,7 @@ static size_t encode_staged(LZ4F_cctx_s* c, uint8_t* dst, size_t cap, size_t n)
     uint8_t* out = (uint8_t*)c->pin_out.p;
     size_t size = 0;
     r = eng->compress_block_pinned(c->hist_at(), c->hist_len, n, (uint32_t)c->block_size, c->prefs.frameInfo.blockMode == LZ4F_blockLinked,
-                                   c->prefs.frameInfo.blockChecksumFlag != 0, out, out_cap + 192, nullptr, &size);
+                                   c->prefs.frameInfo.blockChecksumFlag != 0, out, out_cap + 192, nullptr, &size, c->prefs.compressionLevel);
     if (is_err(r)) return r;
     if (size > cap) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
     memcpy(dst, out, size);
@@ -260,11 +261,6 @@ size_t LZ4F_compressBegin(LZ4F_cctx* c, void* dstBuffer, size_t dstCapacity, con
     if (!c) return make_err(LZ4F_ERROR_GENERIC);
     if (dstCapacity < LZ4F_HEADER_SIZE_MAX) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
     if (prefsPtr) c->prefs = *prefsPtr; else memset(&c->prefs, 0, sizeof(c->prefs));
-    if (c->prefs.compressionLevel > 2) {
-        // levels >= 3 select LZ4HC upstream; unreachable from the reference (level fixed at 0, Conduit.hsc:260)
-        set_last_error("compressionLevel %d: only the fast encoder exists in liblz4f_mi355x", c->prefs.compressionLevel);
-        return make_err(LZ4F_ERROR_compressionLevel_invalid);
-    }
     if (c->prefs.frameInfo.blockSizeID == 0) c->prefs.frameInfo.blockSizeID = LZ4F_max64KB;
     c->block_size = block_size_of(c->prefs.frameInfo.blockSizeID);
     if (!c->block_size) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
@@ -722,7 +718,6 @@ size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src,
     // EndMark / content checksum.  Same bytes as the streaming API gives for the same input fed in whole blocks.
     LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
     if (prefs) p = *prefs;
-    if (p.compressionLevel > 2) { set_last_error("compressionLevel %d: only the fast encoder exists in liblz4f_mi355x", p.compressionLevel); return make_err(LZ4F_ERROR_compressionLevel_invalid); }
     if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
@@ -740,7 +735,7 @@ size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src,
     size_t r;
     try {
         r = pipe_compress_blocks((const uint8_t*)src, srcSize, (uint32_t)bs, p.frameInfo.blockMode == LZ4F_blockLinked, p.frameInfo.blockChecksumFlag != 0,
-                                 d + used, dstCapacity - used, &written);
+                                 d + used, dstCapacity - used, &written, 0, p.compressionLevel);
     } catch (const std::exception& e) { set_last_error("compressFrame: %s", e.what()); r = make_err(LZ4F_ERROR_allocation_failed); }
     if (want_cck) hasher.join();
     if (is_err(r)) return r;

@@ -4,7 +4,8 @@
 // -BI / -BD (independent / linked blocks), --block-checksum, --content-checksum, --batch MiB (gather that much input per
 // GPU call; 0 = the reference's 16 KiB-slice conduit verbatim).  Frames are standard LZ4 frames: interchangeable with
 // the `lz4` CLI in both directions.  --index: the frame's block list follows it as a skippable frame (lz4f_mi355x_appendBlockList's
-// format; other readers skip it, the device decoder finds the blocks through it).
+// format; other readers skip it, the device decoder finds the blocks through it).  -1 .. -12 (compression level, as `lz4` spells it:
+// 3 and above are the high-compression levels, more than 12 is 12) and --best (= -12).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +18,7 @@ static void usage(FILE* f)
 {
     fputs("Usage: mi355x-lz4c [INPUT_FILE] [OUTPUT-FILE] [-d|--decompress] [-B4|-B5|-B6|-B7] [-BI|-BD]\n"
           "                   [--block-checksum] [--content-checksum] [--batch MiB] [--index]\n"
+          "                   [-1 .. -12|--best]\n"
           "  Compress or decompress .lz4 files\n", f);
 }
 
@@ -52,6 +54,9 @@ int main(int argc, char** argv)
         else if (a == "--block-checksum") prefs.frameInfo.blockChecksumFlag = LZ4F_blockChecksumEnabled;
         else if (a == "--content-checksum") prefs.frameInfo.contentChecksumFlag = LZ4F_contentChecksumEnabled;
         else if (a == "--index") listed = true;
+        else if (a == "--best") prefs.compressionLevel = 12;
+        else if (a.size() >= 2 && a.size() <= 3 && a[0] == '-' && a[1] >= '1' && a[1] <= '9' && (a.size() == 2 || (a[2] >= '0' && a[2] <= '9')))
+            prefs.compressionLevel = atoi(a.c_str() + 1);
         else if (a == "--batch" && i + 1 < argc) batch = (size_t)strtoull(argv[++i], nullptr, 10) << 20;
         else if (a == "-" || a[0] != '-') pos.push_back(a);
         else { usage(stderr); return 2; }

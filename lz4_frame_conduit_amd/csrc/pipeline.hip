@@ -86,7 +86,8 @@ struct Slots {
 }  // namespace
 
 // ---- compress: the blocks (size word, payload, checksum) of `n` input bytes -> dst -------------------------------------
-size_t pipe_compress_blocks(const uint8_t* src, size_t n, uint32_t block_size, bool linked, bool bck, uint8_t* dst, size_t cap, size_t* written, size_t hist_before)
+size_t pipe_compress_blocks(const uint8_t* src, size_t n, uint32_t block_size, bool linked, bool bck, uint8_t* dst, size_t cap, size_t* written, size_t hist_before,
+                            int level)
 {
     *written = 0;
     if (n == 0) return 0;
@@ -107,7 +108,7 @@ size_t pipe_compress_blocks(const uint8_t* src, size_t n, uint32_t block_size, b
             const size_t hl = linked ? std::min(off + hist_before, (size_t)65536) : 0;      // (history: the input in front of the slab)
             size_t size = 0;
             const auto t0 = std::chrono::steady_clock::now();
-            size_t rr = e->slab_compress(src + off, len, src + off - hl, hl, block_size, linked, bck, src_pinned, &size);
+            size_t rr = e->slab_compress(src + off, len, src + off - hl, hl, block_size, linked, bck, src_pinned, &size, level);
             if (is_err(rr)) { errs[slot] = last_error(); turns.fail(rr); return; }
             const auto t1 = std::chrono::steady_clock::now();
             if (!turns.enter(k)) return;

@@ -79,7 +79,9 @@ class Engine:
 
     def compress_async(self, src: torch.Tensor, dst: torch.Tensor, prefs: Preferences, table: "torch.Tensor | None" = None,
                        index: "torch.Tensor | None" = None, inband: bool = False):
-        """Enqueue src -> one frame in dst.  Returns nothing; call result() after a sync.
+        """Enqueue src -> one frame in dst.  prefs.compressionLevel picks the encoder: <= 2 the fast one, 3-12 the
+        high-compression levels (hash-chain search, lazy parse; equal input -> equal bytes at any setting), above 12 is 12.
+        Returns nothing; call result() after a sync.
         With `index` (new_index) the compressor also leaves its sequence index there for decompress_blocks_async.
         With `inband` the index and the block list go into the stream itself (a skippable frame behind the LZ4 frame, counted in
         result().size): decompress_frame_async finds them there."""
