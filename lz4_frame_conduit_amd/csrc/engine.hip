@@ -395,16 +395,454 @@ size_t lz4f_mi355x_engine::launch_compress(const CompressJob& j, uint8_t* d_dst,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// decode: a plan made from the call alone, then one function per stage (launch_decompress, at the end, runs them in order)
+lz4f_mi355x_engine::DecodePlan lz4f_mi355x_engine::decode_plan(const DecompressJob& j, const Switches& sw, uint32_t cus)
+{
+    DecodePlan p;
+    p.given = j.d_table || j.table_in_place || j.table_direct;
+    p.n_max = p.given ? j.n_blocks : j.max_blocks;
+    p.begin_small = p.given && p.n_max <= 256;                       // (the streaming API's one block per call: one launch for the record, the verdict words and the table check)
+    const bool hinted = j.hint_list && j.hint_n <= p.n_max;
+    // frames of many small blocks: the size words are found in parallel (frame_dev.cuh); k_walk_frame behind it returns at
+    // once when that has delivered, and walks the list itself otherwise (big blocks: a few hundred hops, and one in 2^9
+    // byte positions would be a candidate)
+    if (p.given) p.walk = DecodePlan::WALK_NONE;
+    else if (hinted) p.walk = DecodePlan::WALK_TRAILER;
+    else if (j.block_size <= (256u << 10) && j.frame_cap >= (1u << 20) && !sw.serial_walk) p.walk = DecodePlan::WALK_PARALLEL;
+    else if (j.block_size > (256u << 10) && j.frame_cap >= (size_t)192 * j.block_size && !sw.serial_walk) p.walk = DecodePlan::WALK_SEEDED;      // (~0.15 ms whatever the frame: pays from ~330 blocks of half their size on)
+    else p.walk = DecodePlan::WALK_SERIAL;
+    // large blocks / linked frames: fused parse+copy workgroups ('f'); small independent blocks: one wave per block ('1')
+    p.mode = sw.decode_mode ? sw.decode_mode : (j.linked || j.block_size >= (256u << 10)) ? 'f' : '1';
+    // (an index out of the frame's trailer brings its counts in the footer - no read - and its frame is one call's work: every block but the last is full,
+    // so the table the list check writes has every block's place in the output, which is what a linked frame's indexed decode needs; if a trailer lies about
+    // that the descriptors do not tile the blocks and the generic kernels take the frame)
+    p.ix_by_trailer = j.d_index && j.ix_seqs && hinted;
+    // no index to go by: a linked frame's is made by a lane per block, big independent blocks' from stitched stretches (dec_self_index)
+    p.self_index = !sw.no_selfindex && (j.linked ? j.hist0 <= 65536 && p.n_max >= 2 : j.block_size >= (256u << 10) && j.block_size <= (4u << 20) && !sw.no_spx);
+    // (an index out of the frame's trailer is laid out for the block count the trailer names; the table and the generic
+    // kernels keep the caller's upper bound - if the walk finds another count, the index is dropped on the device)
+    p.n_ix = hinted ? j.hint_n : p.n_max;
+    // a linked frame is one chain: one workgroup with the 64 KiB window in LDS; frames with short (flushed) blocks
+    // set the flag and are decoded by the generic kernel launched right behind (it returns at once otherwise)
+    // (one block of a linked frame - what the streaming functions hand over per call: the window kernel is built for whole frames
+    // and takes 180-210 us for a single 64 KiB block; the fused workgroup takes it directly)
+    p.windowed = j.linked && j.dst_cap < 0xFFF00000ull && !sw.no_window && !(p.n_max == 1 && p.given);
+    // more blocks than the machine has 8-wave workgroup slots: the 4-wave shape keeps twice as many in flight
+    p.small = !j.linked && j.block_size <= (1u << 20);
+    // Few big blocks: a wave per block leaves the machine idle and waits out every trip to memory (13-15 GiB/s for a GiB in 4 MiB blocks);
+    // a workgroup per block with the block's window in LDS and its waves taking the payload in turns (decode_relay.cuh) is three times
+    // as fast per block - but it has a CU to itself, so from ~3 blocks per CU on the waves win again (8 GiB in 4 MiB blocks: 90 GiB/s).
+    p.relay = j.block_size > 65536u && sw.dense_mode != 2 && (sw.dense_mode == 1 || p.n_max <= 3u * cus);
+    // (linked frames of small blocks: a workgroup takes a group of consecutive blocks - see k_copy_indexed)
+    // (a group is 1 MiB of blocks where that fills the machine - 1024 workgroups of the 4-wave shape are half of its wave slots - and less for
+    // smaller frames: LZ4F_MI355X_GROUP_KIB sets it)
+    const uint32_t group_bytes = sw.group_kib ? sw.group_kib << 10 : ((uint64_t)p.n_ix * j.block_size <= (2ull << 30) ? (512u << 10) : (1u << 20));      // (1 GiB: 512 KiB 0.509 ms, 1 MiB 0.541, 256 KiB 0.788, 2 MiB 0.778)
+    p.group = (j.linked && j.block_size < group_bytes && !sw.no_groups) ? group_bytes / j.block_size : 1u;
+    // (how long a group of a linked frame waits for the one in front: half a second plus 20 ticks of the 100 MHz clock per
+    // output byte - 5 MB/s, a fifth of the slowest chain measured (text, linked, 27 MB/s); LZ4F_MI355X_WAIT_TICKS overrides)
+    p.wait_ticks = sw.wait_ticks ? sw.wait_ticks : 50000000ull + 20ull * p.n_ix * j.block_size;
+    return p;
+}
+lz4f_mi355x_engine::IxRoute lz4f_mi355x_engine::ix_route(const DecompressJob& j, const Switches& sw, uint32_t n_ix, uint32_t ix_seqs)
+{
+    IxRoute r;
+    const uint64_t span = (uint64_t)n_ix * j.block_size;            // (the last block may be short)
+    // (pointer doubling does ~12 GiB/s on text whatever the framing; hop by hop it is 1.3 GiB/s, which only pays where
+    // there is no block-level parallelism - linked frames; independent blocks then stay with the copier workgroups, 4.8 GiB/s)
+    r.doubling = ((uint64_t)ix_seqs * 48 > span || sw.trace_always) && span <= IXP_MAX_SPAN && !sw.no_doubling;      // (short sequences: worth the tracer's scratch)
+    // Independent blocks that are not dense (no tracer on offer): ONE kernel - the copy workgroup's first wave parses its block's
+    // runs and resolves direct matches while the copiers move bytes (decode_indexed.cuh: k_copy_selffed)
+    r.selffed = !j.linked && !sw.no_selffeed && !sw.no_resolve && !sw.trace_always && !r.doubling;
+    const bool trace_can = !sw.no_trace && !sw.no_resolve && (j.block_size & 63u) == 0;
+    r.gate = !trace_can ? 0u : sw.trace_always ? 2u : (j.linked || r.doubling) ? 1u : 0u;
+    return r;
+}
+// developer aid (LZ4F_MI355X_PROF): wait for the stream, then copy n bytes of the device's counters back
+static bool prof_read(hipStream_t st, void* to, const void* from, size_t n) { return hipStreamSynchronize(st) == hipSuccess && hipMemcpy(to, from, n, hipMemcpyDeviceToHost) == hipSuccess; }
+
+// Stage 1: the block table - the caller's, checked, or found by walking the frame's size words - and the finishing kernels' verdict words.
+size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut** tbl_out, uint32_t* path)
+{
+    hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max;
+    // a caller-supplied table is worked on in a copy (decode overwrites dst_size); table_direct: the engine's own staging copy, used where it lies
+    BlockOut* tbl = (BlockOut*)j.table_direct;
+    if (!tbl) { if (table.ensure((size_t)(n_max + 1) * sizeof(BlockOut))) return make_err(LZ4F_ERROR_allocation_failed); tbl = (BlockOut*)table.p; }
+    if (p.given) {
+        if (!j.table_in_place && !j.table_direct)
+            HIP_TRY(hipMemcpyAsync(tbl, j.d_table, (size_t)n_max * sizeof(BlockOut), hipMemcpyDeviceToDevice, st));
+        if (p.begin_small)
+            hipLaunchKernelGGL(k_begin_table_small, dim3(1), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
+                               j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, res, (uint32_t*)bad.p);
+        else {
+            hipLaunchKernelGGL(k_init_result, dim3(1), dim3(64), 0, st, res, n_max, 0u);
+            if (n_max) hipLaunchKernelGGL(k_check_table, dim3(std::min<uint32_t>((n_max + 255) / 256, 1024u)), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
+                                          j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, res);
+        }
+        *path |= LZ4F_MI355X_PATH_TABLE_GIVEN;
+    } else {
+        tick(4, false);
+        // the list walks: each finds where the size words should be in its own way, then the same two kernels check the list link by link
+        const size_t list_cap = (size_t)n_max + 1024;                     // (the parallel and the seeded walk's list)
+        uint32_t lgrid = std::min<uint32_t>((uint32_t)((list_cap + 255) / 256), 4096u);
+        WalkState* ws = nullptr; const uint64_t* list = nullptr;
+        if (p.walk == DecodePlan::WALK_TRAILER) {
+            // the frame's own trailer says where the size words are: checked link by link like the parallel walk's candidates
+            if (walkbuf.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
+            ws = (WalkState*)walkbuf.p;
+            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws, j.hint_n);
+            list = j.hint_list;
+            lgrid = std::min<uint32_t>((j.hint_n + 255) / 256, 4096u);
+            *path |= LZ4F_MI355X_PATH_TRAILER;
+        } else if (p.walk == DecodePlan::WALK_PARALLEL) {
+            const uint32_t n_chunks = (uint32_t)((j.frame_cap + WK_CHUNK - 1) / WK_CHUNK);
+            const size_t at_chunks = 256, at_list = at_chunks + (size_t)n_chunks * sizeof(WalkChunk), at_list2 = at_list + list_cap * 8, at_mark = at_list2 + list_cap * 8;
+            if (walkbuf.ensure(at_mark + list_cap * 4)) return make_err(LZ4F_ERROR_allocation_failed);
+            ws = (WalkState*)walkbuf.p;
+            WalkChunk* ch = (WalkChunk*)((uint8_t*)walkbuf.p + at_chunks);
+            uint64_t* list1 = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
+            uint64_t* list2 = (uint64_t*)((uint8_t*)walkbuf.p + at_list2);
+            uint32_t* mark = (uint32_t*)((uint8_t*)walkbuf.p + at_mark);
+            HIP_TRY(hipMemsetAsync(mark, 0, list_cap * 4, st));
+            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
+            hipLaunchKernelGGL(k_walk_cand, dim3(n_chunks), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, ch);
+            hipLaunchKernelGGL(k_walk_order, dim3(1), dim3(1024), 0, st, ch, n_chunks, ws, list1, (uint32_t)list_cap);
+            hipLaunchKernelGGL(k_walk_mark, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, (const uint64_t*)list1, mark);
+            hipLaunchKernelGGL(k_walk_filter, dim3(1), dim3(1024), 0, st, ws, (const uint64_t*)list1, (const uint32_t*)mark, list2);
+            list = list2;
+            *path |= LZ4F_MI355X_PATH_PARALLEL_WALK;
+        } else if (p.walk == DecodePlan::WALK_SEEDED) {
+            // big blocks: seeds found in parallel, a lane per seed walking to the next one (frame_dev.cuh); the list is checked link by
+            // link like the small blocks' candidates, and k_walk_frame behind walks the frame itself if it is not the chain
+            const size_t at_seeds = 256, at_list = at_seeds + (WK_SEEDS + 1) * 8;
+            if (walkbuf.ensure(at_list + list_cap * 8)) return make_err(LZ4F_ERROR_allocation_failed);
+            ws = (WalkState*)walkbuf.p;
+            unsigned long long* seeds = (unsigned long long*)((uint8_t*)walkbuf.p + at_seeds);
+            HIP_TRY(hipMemsetAsync(seeds, 0xFF, (WK_SEEDS + 1) * 8, st));
+            uint64_t* list1 = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
+            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
+            hipLaunchKernelGGL(k_walk_seeds, dim3(WK_SEEDS * wk_seed_pieces(j.block_size)), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, seeds);
+            hipLaunchKernelGGL(k_walk_chains, dim3(1), dim3(WK_SEEDS), 0, st, j.d_frame, j.frame_cap, ws, (const unsigned long long*)seeds, list1, (uint32_t)std::min<size_t>(list_cap, 0xFFFFFFFFu));
+            list = list1;
+            *path |= LZ4F_MI355X_PATH_PARALLEL_WALK;
+        }
+        if (list) {
+            hipLaunchKernelGGL(k_walk_link, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, list, tbl, n_max);
+            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, list, n_max, res);
+            WalkState h;
+            if (sw.prof && p.walk == DecodePlan::WALK_PARALLEL && prof_read(st, &h, ws, sizeof(h))) fprintf(stderr, "parallel walk: done %u overflow %u candidates %u first_end %u first_break %u (header ok %u, hsize %u, block %u)\n", h.done, h.overflow, h.total, h.first_end, h.first_break, h.head_ok, h.hsize, h.bs);
+            if (sw.prof && p.walk == DecodePlan::WALK_SEEDED && prof_read(st, &h, ws, sizeof(h))) fprintf(stderr, "seeded walk: done %u overflow %u entries %u first_end %u first_break %u\n", h.done, h.overflow, h.total, h.first_end, h.first_break);
+        }
+        hipLaunchKernelGGL(k_walk_frame, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, tbl, n_max, res, list ? (const uint32_t*)&ws->done : nullptr);
+        tick(4, true);
+    }
+    if (!p.begin_small) {                                              // (k_begin_table_small set them)
+        HIP_TRY(hipMemsetAsync(bad.p, 0xFF, 8, st));                 // [0] block-checksum verdict, [1] first failed block
+        HIP_TRY(hipMemsetAsync((uint8_t*)bad.p + 8, 0, 24, st));    // [2] "something has to move", [4..5] sum of sizes (k_finish_check)
+    }
+    *tbl_out = tbl;
+    return 0;
+}
+
+// Stage 2: the block checksums.  The verification only reads the payloads, and so do the decode kernels: it runs beside them on the
+// engine's second stream (forked here, joined in front of k_finish_check, which reads its verdict).  A 4 MiB block is one serial chain
+// for one wave (~2 ms) whatever else the GPU does, so side by side the two cost max(2.0, decode) instead of the sum.  The one-wave
+// workgroups then ask for 12 KiB of LDS instead of 36 (they would not fit beside four decode workgroups per CU).
+size_t lz4f_mi355x_engine::dec_checksums(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl)
+{
+    constexpr int W = 4;
+    hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max;
+    const bool beside = !sw.no_overlap && aux_ready();
+    hipStream_t xs = beside ? (hipStream_t)aux_stream : st;
+    if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_fork, st)); HIP_TRY(hipStreamWaitEvent(xs, (hipEvent_t)ev_fork, 0)); }
+    tick(5, false, xs);
+    if (n_max < XXH_LANE4_BELOW)
+        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(n_max), dim3(64), beside ? (12u << 10) : XXH_SPREAD_LDS, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (uint32_t*)bad.p);
+    else
+        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (uint32_t*)bad.p);
+    tick(5, true, xs);
+    if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_join, xs)); aux_pending = true; }
+    return 0;
+}
+
+// Stage 3: the sequence index - the one that came with the call, or one made here.  ix->d stays null when the indexed kernels do not run.
+size_t lz4f_mi355x_engine::dec_index(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, IndexSrc* ix, uint32_t* path)
+{
+    if (p.mode != 'f' || sw.no_index) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    IndexSrc x{p.ix_by_trailer ? IndexSrc::TRAILER : IndexSrc::GIVEN, j.d_index, j.index_size, j.ix_seqs, j.ix_entries};
+    // How many sequences and entries the index holds comes with THIS call (the trailer's footer, the self-index scan, or one
+    // read of the index header for the explicit-index entry point): it sizes the descriptor workspace and decides whether a
+    // dense frame's scratch is worth having.  Nothing is carried over from earlier calls; the device checks the real header
+    // against the workspace (k_check_index) and hands the call to the generic decoder if it does not fit.
+    // A linked frame is one match chain without a usable index (seconds instead of milliseconds on dense data), so for
+    // those a header that is not the index's drops it (a host synchronisation, ~30 us): the compressor marks an index
+    // unusable when the stream had more sequences than it had room for, and then one is made here instead.
+    if (j.d_index && j.index_size >= sizeof(IxHeader) && !p.ix_by_trailer && (j.linked || !j.ix_seqs)) {
+        IxHeader hd; memset(&hd, 0, sizeof(hd));
+        HIP_TRY(hipMemcpyAsync(&hd, j.d_index, sizeof(hd), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (hd.magic == IX_MAGIC && hd.stride == IX_STRIDE) { x.seqs = hd.total_seqs; x.entries = hd.total_entries; x.from = IndexSrc::HEADER; }
+        else if (j.linked) x = IndexSrc();
+    }
+    if (!x.d && p.self_index)
+        if (size_t e = dec_self_index(j, p, res, tbl, !j.linked, &x)) return e;
+    const bool self = x.from == IndexSrc::SELF_LINKED || x.from == IndexSrc::SPX;
+    if (self) *path |= LZ4F_MI355X_PATH_SELF_INDEX;
+    // (linked frames: only with a table that has every block's output position - the compressor's, or the one just made)
+    if (!x.d || x.size < sizeof(IxHeader) || (j.linked && !self && !((p.given || p.ix_by_trailer) && j.hist0 <= 65536))) return 0;
+    if ((uint64_t)x.seqs > (uint64_t)x.entries * (IX_STRIDE + 1) || x.entries > (x.size - sizeof(IxHeader)) / sizeof(IxEntry)) x.seqs = 0;      // (not a count this index can hold)
+    *ix = x;
+    return 0;
+}
+
+// A frame without an index (a foreign one: the reference's default output, `lz4 -c`, LZ4F_compressFrame): the index is made here, and the same
+// kernels as with the compressor's index take the frame.  A linked frame's: a lane per block walks the payload (parsing needs no history).  Big
+// independent blocks' (spx_walk): lanes that start at guessed tokens cut the blocks into stretches, stitched where they meet (decode_spx.cuh).
+// A scan places the blocks; its totals, read back (a host synchronisation), size the index.  Dense payloads (k_density_probe) and anything
+// odd leave the frame to the generic decoders.
+size_t lz4f_mi355x_engine::dec_self_index(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, bool spx_walk, IndexSrc* ix)
+{
+    hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max, cpb = j.block_size / pick_chunk_size(j.block_size);
+    const size_t fixed = ix_entries_at(n_max, cpb), spx_at = (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint);
+    if (selfcnt.ensure((size_t)n_max * 8 + 64) || seqcnt.ensure(256 + (size_t)n_max * (8 + 8 * IXL_PUB)) || selfix.ensure(fixed + 64) || density.ensure(64) ||
+        (spx_walk && spx.ensure((size_t)n_max * ((SPX_MAXPT + 1) * sizeof(SpxPoint) + 4) + 64)))
+        return make_err(LZ4F_ERROR_allocation_failed);
+    uint32_t* cnt = (uint32_t*)selfcnt.p; uint32_t* osz = cnt + n_max;
+    HIP_TRY(hipMemsetAsync(seqcnt.p, 0, spx_walk ? 256 : 64, st));
+    hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, res, n_max, (uint32_t*)density.p);
+    if (spx_walk)
+        hipLaunchKernelGGL(k_spx_index, dim3(n_max), dim3(SPX_MAXSEG), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, res, n_max, cnt, osz,
+                           (SpxPoint*)spx.p, (uint32_t*)((uint8_t*)spx.p + spx_at), (uint32_t*)seqcnt.p, sw.no_density_probe ? (const uint32_t*)nullptr : (const uint32_t*)density.p + 1);
+    else {
+        hipLaunchKernelGGL((k_selfindex_walk_wave<0, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
+                           res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
+        hipLaunchKernelGGL(k_selfindex_walk<0>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
+                           res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
+    }
+    uint32_t tot[10];
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(k_selfindex_scan, dim3(1), dim3(1024), 0, st, tbl, res, n_max, (const uint32_t*)cnt, (const uint32_t*)osz,
+                           selfix.p, cpb, (uint64_t)j.dst_cap, j.block_size, (uint32_t*)seqcnt.p, spx_walk ? 1u : 0u);
+        if (pass == 1) break;
+        HIP_TRY(hipMemcpyAsync(tot, seqcnt.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (spx_walk && sw.prof) fprintf(stderr, "spx: flags %u, %u sequences in %u blocks, %u stretches walked by the stitching thread\n", tot[0], tot[9], n_max, tot[2]);
+#ifdef SPX_PROF
+        if (spx_walk) { uint32_t y[8]; if (hipMemcpy(y, (uint32_t*)seqcnt.p + 48, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx lanes: hit the hop cap %u, without a start %u, started at their segment's first byte %u, ran into something %u; most sequences in one lane %u\n", y[0], y[1], y[2], y[3], y[4]); }
+        if (spx_walk) { uint32_t z[8]; if (hipMemcpy(z, (uint32_t*)seqcnt.p + 40, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx cycles: guess max %u avg %u, walk max %u avg %u, stitch max %u avg %u, workgroup max %u (waves %u)\n", z[0], (unsigned)(((unsigned long long)z[4] << 8) / (2 * n_max)), z[1], (unsigned)(((unsigned long long)z[5] << 8) / (2 * n_max)), z[2], (unsigned)(((unsigned long long)z[6] << 8) / n_max), z[3], 2 * n_max); }
+#endif
+        if (tot[0] != 0 || tot[9] == 0) break;
+        const void* before = selfix.p;
+        if (selfix.ensure(fixed + (size_t)tot[8] * sizeof(IxEntry) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
+        if (selfix.p == before) break;                                   // (same buffer: the block table is already in it)
+    }
+    if (tot[0] != 0 || tot[9] == 0) return 0;
+    if (!spx_walk) {                                                     // (the linked frame's walkers again, filling the index in)
+        hipLaunchKernelGGL((k_selfindex_walk_wave<1, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
+                           res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
+        hipLaunchKernelGGL(k_selfindex_walk<1>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
+                           res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
+    }
+    *ix = IndexSrc{spx_walk ? IndexSrc::SPX : IndexSrc::SELF_LINKED, selfix.p, fixed + (size_t)tot[8] * sizeof(IxEntry), tot[9], tot[8]};
+    return 0;
+}
+
+// Stage 4: the indexed decode.  Descriptors from the sequence index: a lane per entry parses, a lane per sequence resolves direct
+// matches, a workgroup per block copies - or, for independent blocks that are not dense, one kernel does all three.
+// *ix_flags: the indexed kernels' "gave up" word, when they were launched.
+size_t lz4f_mi355x_engine::dec_indexed(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, const IndexSrc& ix, const uint32_t** ix_flags, uint32_t* path)
+{
+    if (!ix.d) return 0;
+    hipStream_t st = (hipStream_t)stream; void* d_index = ix.d;
+    const uint32_t chunk = pick_chunk_size(j.block_size), cpb = j.block_size / chunk, n_ix = p.n_ix;
+    if ((size_t)ix.seqs + 4096 > ix_seq_cap) ix_seq_cap = (size_t)ix.seqs + ix.seqs / 4 + 4096;
+    if (!ix.seqs) return 0;
+    const size_t dsrc_at = (ix_seq_cap + 64) * sizeof(SeqDesc);
+    if (desc.ensure(dsrc_at + (ix_seq_cap + 64) * 4) || seqcnt.ensure(256 + (size_t)p.n_max * (8 + 8 * IXL_PUB))) return make_err(LZ4F_ERROR_allocation_failed);
+    HIP_TRY(hipMemsetAsync(seqcnt.p, 0, 256 + (j.linked ? (size_t)p.n_max * 8 : 0), st));      // flags (+ per block of a linked frame: the "done" word and the count of published ranges)
+    unsigned long long* iprof = (unsigned long long*)(sw.prof ? prof_buf() : nullptr);
+    tick(8, false);
+    hipLaunchKernelGGL(k_check_index, dim3(1), dim3(64), 0, st, (const void*)d_index, (uint64_t)ix.size, n_ix, cpb, chunk,
+                       (uint64_t)ix_seq_cap, (uint32_t*)seqcnt.p, (const ResultRec*)res);
+    // the whole block table, before any kernel behind writes (the index is input)
+    hipLaunchKernelGGL(k_check_blocks, dim3((n_ix + 255) / 256), dim3(256), 0, st, (const void*)d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
+                       (uint32_t*)seqcnt.p);
+    const IxRoute r = ix_route(j, sw, n_ix, ix.seqs);
+    *ix_flags = (const uint32_t*)seqcnt.p;
+    *path |= LZ4F_MI355X_PATH_INDEXED;
+    if (r.selffed) {
+        tick(8, true); tick(9, false);
+        // k_copy_selffed in the workgroup shape of the block size, with the block's runs from the index or from the stitched stretches
+        auto selffed = [&](auto src) {
+            using S = decltype(src);
+            if (j.block_size <= (1u << 20))
+                hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, S>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)res, n_ix,
+                                   (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
+            else
+                hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, S>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)res, n_ix,
+                                   (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
+        };
+        if (ix.from == IndexSrc::SPX) selffed(FzSrcSpx{(const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)p.n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint))});
+        else selffed(FzSrcIx{(const void*)d_index, n_ix});
+        tick(9, true);
+        return 0;
+    }
+    // the chain: parse, resolve direct matches, trace dense frames, copy, check the tails
+    uint32_t* done = (uint32_t*)seqcnt.p + 64;
+    const uint32_t lk = j.linked ? 1u | (uint32_t)sw.chain_gate << 1 : 0u;      // (bits 1..: chain gate, see k_copy_indexed)
+    const uint32_t n_lanes = ix.entries > n_ix ? ix.entries : n_ix;     // (grid-stride inside: a hint is enough)
+    if (ix.from == IndexSrc::SPX)                                                 // (no entries: the stretches between the blocks' check lines)
+        hipLaunchKernelGGL(k_spx_parse, dim3(n_ix), dim3(128), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
+                           d_index, (const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)p.n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint)),
+                           (SeqDesc*)desc.p, (uint32_t*)seqcnt.p);
+    else
+        hipLaunchKernelGGL(k_parse_indexed, dim3((n_lanes + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap,
+                           (const BlockOut*)tbl, d_index, n_ix, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, lk, (uint64_t)j.hist0);
+    const uint64_t trace_span = (uint64_t)n_ix * j.block_size;            // (the last block may be short)
+    const uint32_t res_gy = j.block_size >= (1u << 19) ? j.block_size >> 18 : 1u;
+    uint32_t gate = r.gate;
+    if (gate && postab.ensure((size_t)(trace_span >> 6) * 4 + 512 + ((size_t)(trace_span >> IXT_REGION_LOG) + 4) * 4)) gate = 0;      // (no memory for the position table: the copiers do it)
+    if (gate && r.doubling)                                        // (dense by the sequence density: no need to resolve anything)
+        hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 1u, 1u);
+    uint32_t* dsrc = sw.no_resolve ? nullptr : (uint32_t*)((uint8_t*)desc.p + dsrc_at);
+    if (dsrc)
+        hipLaunchKernelGGL(k_resolve_direct, dim3(n_ix, res_gy), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, (const SeqDesc*)desc.p,
+                           dsrc, (uint32_t*)seqcnt.p, (iprof ? 1u : 0u) | (gate ? 2u : 0u), lk);
+    if (iprof) {                                                   // developer aid: how many matches are direct
+        uint32_t c[8]; if (prof_read(st, c, seqcnt.p, 32)) fprintf(stderr, "indexed: flags %u, matches direct after parse %u, resolved %u, left to the chain %u\n", c[0], c[4], c[5], c[6]);
+        uint32_t x[6] = {0, 0, 0, 0, 0, 0}; if (hipMemcpy(x, (uint32_t*)seqcnt.p + 10, 24, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "indexed (linked): %u matches stay on the chain, %u of them reach into the block in front (%u blocks); not resolved because: beyond one block %u, source straddles two runs %u, run-length source %u, hop limit %u\n", x[0], x[1], n_ix, x[2], x[3], x[4], x[5]);
+    }
+    // dense frames (text): no chain at all, every output byte traced to its literal (see k_trace_copy)
+    hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 0u, res_gy);
+    if (gate) {
+        hipLaunchKernelGGL(k_build_postab, dim3(n_ix, res_gy), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
+                           (const SeqDesc*)desc.p, (uint32_t*)postab.p, (uint32_t*)seqcnt.p);
+        const uint64_t n_thr = (trace_span + IXT_TB - 1) / IXT_TB;
+        // if the last index seen here was of a dense stream (the device decides about THIS one, but the
+        // scratch - 4 bytes per output byte - and 18 launches are the host's to spend): one hop per byte, then pointer doubling
+        const uint32_t pd_grid = (uint32_t)((trace_span / 4 + 255) / 256), pd_ngrp = pd_grid * 4u;      // (k_pd_round: a wave per 256 bytes)
+        const size_t pd_grp_at = (((size_t)trace_span * 4 + 255) & ~(size_t)255) + (((IXP_ROUNDS + 1) * IXP_STRIPES * 4 + 255) & ~(size_t)255);
+        if (r.doubling && !pdbuf.ensure(pd_grp_at + 2 * (size_t)pd_ngrp + 256)) {
+            *path |= LZ4F_MI355X_PATH_DOUBLING;
+            uint32_t* remaining = (uint32_t*)((uint8_t*)pdbuf.p + (((size_t)trace_span * 4 + 255) & ~(size_t)255));
+            if (hipMemsetAsync(remaining, 0, (IXP_ROUNDS + 1) * IXP_STRIPES * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
+            hipLaunchKernelGGL(k_pd_init, dim3((uint32_t)((n_thr + 255) / 256)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
+                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
+                               lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, (uint32_t*)pdbuf.p, remaining);
+            for (uint32_t rd = 1; rd <= IXP_ROUNDS; rd++)
+                hipLaunchKernelGGL(k_pd_round, dim3(pd_grid), dim3(256), 0, st, j.d_dst, (uint32_t*)pdbuf.p, (const BlockOut*)tbl,
+                                   (const ResultRec*)res, n_ix, rd, remaining, (uint32_t*)seqcnt.p, (uint8_t*)pdbuf.p + pd_grp_at, pd_ngrp);
+            hipLaunchKernelGGL(k_pd_verdict, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, (const uint32_t*)remaining);
+            if (iprof) { static uint32_t t[(IXP_ROUNDS + 1) * IXP_STRIPES]; if (prof_read(st, t, remaining, sizeof(t))) { fprintf(stderr, "doubling: bytes open after each round:"); for (uint32_t rd = 0; rd <= IXP_ROUNDS; rd++) { uint64_t sum = 0; for (uint32_t q = 0; q < IXP_STRIPES; q++) sum += t[rd * IXP_STRIPES + q]; fprintf(stderr, " %llu", (unsigned long long)sum); } fprintf(stderr, "\n"); } }
+        } else {
+            *path |= LZ4F_MI355X_PATH_TRACE_HOPS;
+            uint32_t* region_cnt = (uint32_t*)((uint8_t*)postab.p + (((size_t)(trace_span >> 6) * 4 + 255) & ~(size_t)255));
+            if (hipMemsetAsync(region_cnt, 0, ((size_t)(trace_span >> IXT_REGION_LOG) + 2) * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
+            const uint32_t tc_wg = (uint32_t)((n_thr + 255) / 256);
+            hipLaunchKernelGGL(k_trace_copy, dim3(std::min<uint32_t>(tc_wg, 8192u)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
+                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
+                               lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, region_cnt, iprof ? 1u : 0u, tc_wg);
+            uint32_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (iprof && prof_read(st, t, (uint32_t*)seqcnt.p + 24, 32) && t[0]) fprintf(stderr, "traced: %llu turns for %u pieces (%u read from the output), deepest thread %u turns\n", (unsigned long long)t[2] | ((unsigned long long)t[3] << 32), t[4], t[5], t[6]);
+        }
+    }
+    tick(8, true); tick(9, false);
+    auto copy = [&](auto cfg) {
+        using C = decltype(cfg);
+        hipLaunchKernelGGL(k_copy_indexed<C>, dim3((n_ix + p.group - 1) / p.group), dim3(64 * C::WAVES), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)res, n_ix,
+                           d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (uint32_t*)seqcnt.p, iprof, lk, done, p.group, (uint64_t)j.hist0, p.wait_ticks);
+    };
+    if (j.block_size <= (1u << 20)) copy(FzCfg<4>()); else copy(FzCfg<8>());
+    tick(9, true);
+    uint32_t y[4] = {0, 0, 0, 0};
+    if (iprof && j.linked && prof_read(st, y, (uint32_t*)seqcnt.p + 20, 16)) fprintf(stderr, "indexed (linked): blocks that found the block in front at state 3: %u (of those, had to wait for all of it: %u); blocks with set-aside matches %u (block in front already done: %u)\n", y[0], y[1], y[2], y[3]);
+    hipLaunchKernelGGL(k_check_tails, dim3((n_ix + 255) / 256), dim3(256), 0, st, tbl, (const ResultRec*)res, n_ix, d_index,
+                       (const SeqDesc*)desc.p, (uint64_t)ix_seq_cap, j.block_size, (const uint32_t*)seqcnt.p);
+    return 0;
+}
+
+// Stage 5: the generic decoders.  Each runs only if the one in front gave up: only_if is the indexed kernels' flags word (null: none
+// ran), then the window kernel's fallback word, then the density probe's verdict.
+size_t lz4f_mi355x_engine::dec_generic(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, const uint32_t* only_if, uint32_t* path)
+{
+    constexpr int W = 4;
+    hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max;
+    if (p.mode == 'f') {
+        unsigned long long* prof = (unsigned long long*)(sw.prof ? prof_buf() : nullptr);
+        const bool indexed = only_if != nullptr;
+        if (p.windowed) {
+            *path |= LZ4F_MI355X_PATH_WINDOW;
+            if (!indexed && seqcnt.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
+            uint32_t* fb = (uint32_t*)seqcnt.p + (indexed ? 16 : 0);                  // (word 0 is the indexed kernels' flag)
+            hipLaunchKernelGGL(k_decode_linked, dim3(1), dim3(64 * LK_WAVES), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
+                               (const ResultRec*)res, n_max, j.block_size, j.hist0, fb, only_if);
+            only_if = fb;
+            uint32_t dbg[3] = {0, 0, 0};                                  // developer aid: why the windowed kernel stopped, if it did
+            if (sw.prof && prof_read(st, dbg, fb, 12)) fprintf(stderr, "k_decode_linked: fallback %u why %u block %u\n", dbg[0], dbg[1], dbg[2]);
+        }
+        *path |= LZ4F_MI355X_PATH_FUSED;
+        // big independent blocks and no index to go by: a look at the payload decides between the fused workgroups and - dense data -
+        // the wave-per-block decoder (k_density_probe); both are launched, one of them returns at once
+        if (!indexed && !j.linked && !sw.no_density_probe) {
+            if (density.ensure(64)) return make_err(LZ4F_ERROR_allocation_failed);
+            hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)res, n_max, (uint32_t*)density.p);
+            if (p.relay) {
+                *path |= LZ4F_MI355X_PATH_WORKGROUP_PER_BLOCK;
+                hipLaunchKernelGGL((k_decode_blocks_relay<RELAY_W, RELAY_S>), dim3(n_max), dim3(64 * (RELAY_W + RELAY_S + 3)), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)res, n_max, (uint64_t)j.frame_cap,
+                                   (const uint32_t*)density.p);
+            } else
+                hipLaunchKernelGGL((k_decode_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl, (const ResultRec*)res,
+                                   n_max, 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap, (const uint32_t*)density.p);
+            only_if = (const uint32_t*)density.p + 1;
+            *path |= LZ4F_MI355X_PATH_WAVE_PER_BLOCK;
+        }
+        auto fused = [&](auto cfg) {                                   // (a linked frame: one workgroup, in the 8-wave shape)
+            using C = decltype(cfg);
+            hipLaunchKernelGGL(k_decode_blocks_fused<C>, dim3(j.linked ? 1u : n_max), dim3(64 * C::WAVES), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
+                               (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, j.hist0, prof, only_if);
+        };
+        if (p.small) fused(FzCfg<4>()); else fused(FzCfg<8>());
+    } else {
+        *path |= LZ4F_MI355X_PATH_WAVE_PER_BLOCK;
+        hipLaunchKernelGGL((k_decode_blocks<W>), dim3(j.linked ? 1u : (n_max + W - 1) / W), dim3(64 * W), sw.dblk_lds, st, j.d_frame, j.d_dst, j.dst_cap, tbl, (const ResultRec*)res,
+                           n_max, j.linked ? 1u : 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap);
+    }
+    return 0;
+}
+
+// Stage 6: what every call ends with - the tight last block, the verdicts, the result record and the content checksum.
+size_t lz4f_mi355x_engine::dec_finish(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, const uint32_t* ix_flags, uint32_t path)
+{
+    hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max;
+    tick(7, false);
+    // liblz4 judges a block against maxBlockSize whatever room the caller leaves it.  Only a walked frame's last block can be left less
+    // (every other block sits below a provisional block's room the walk found inside the buffer), and only when the capacity is not a
+    // multiple of the block size: a last block that failed in that room is decoded again with a whole block's room, and copied out if it fits.
+    if (n_max && !p.given && j.block_size && j.dst_cap % j.block_size != 0) {
+        if (tight.ensure((size_t)65536 + j.block_size + 64)) return make_err(LZ4F_ERROR_allocation_failed);
+        hipLaunchKernelGGL(k_redo_tight_block, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (uint64_t)j.dst_cap, tbl,
+                           (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, (uint64_t)j.hist0, (uint8_t*)tight.p);
+    }
+    const bool check_here = n_max <= 64;                              // (the finishing wave looks at a few blocks itself: a launch less)
+    if (n_max && !check_here) hipLaunchKernelGGL(k_finish_check, dim3((n_max + 255) / 256), dim3(256), 0, st, (const BlockOut*)tbl, (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, (uint32_t*)bad.p);
+    hipLaunchKernelGGL(k_finish_decode, dim3(1), dim3(64), 0, st, j.d_dst, tbl, res, n_max, j.linked ? 1u : 0u, j.block_size,
+                       (const uint32_t*)bad.p, j.block_checksum ? 1u : 0u, path, ix_flags, check_here ? 1u : 0u, (uint64_t)j.dst_cap);
+    if (j.content_checksum && !p.given && !sw.no_content_check)      // (a whole frame was walked: res->consumed is behind its checksum word)
+        hipLaunchKernelGGL(k_xxh32_content, dim3(1), dim3(64), 0, st, (const uint8_t*)j.d_dst, 0ull, (uint8_t*)j.d_frame, res, 1u);
+    tick(7, true);
+    return 0;
+}
+
 size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x_result* d_res)
 {
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     if (!d_res) { if (res.ensure(sizeof(ResultRec))) return make_err(LZ4F_ERROR_allocation_failed); d_res = (lz4f_mi355x_result*)res.p; }
     if (bad.ensure(64)) return make_err(LZ4F_ERROR_allocation_failed);
-    BlockOut* tbl;
-    uint32_t n_max;
-    bool bad_set = false;                                            // the finishing kernels' verdict words are initialised by a kernel already launched
-    uint32_t plan = 0;                                               // LZ4F_MI355X_PATH_*: reported in result.flags
+    ResultRec* r = (ResultRec*)d_res;
+    const DecodePlan p = decode_plan(j, sw, device_cus(device));
+    uint32_t path = 0;                                               // LZ4F_MI355X_PATH_*: reported in result.flags
     for (int i = 4; i < 10; i++) ev_used[i] = false;
     ev_used[11] = false;
     if (aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_join, 0)); aux_pending = false; }      // (a call that left early: its forked work first)
@@ -415,452 +853,20 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
         ~AuxJoin() { if (e->aux_pending && hipStreamWaitEvent(st, (hipEvent_t)e->ev_join, 0) == hipSuccess) e->aux_pending = false; }
     } aux_join{this, st};
     tick(11, false);
-    if (j.d_table || j.table_in_place || j.table_direct) {
-        // caller-supplied table: work on a copy (decode overwrites dst_size); table_direct: the engine's own staging copy, used where it lies
-        n_max = j.n_blocks;
-        if (j.table_direct) tbl = (BlockOut*)j.table_direct;
-        else {
-            if (table.ensure((size_t)(n_max + 1) * sizeof(BlockOut))) return make_err(LZ4F_ERROR_allocation_failed);
-            tbl = (BlockOut*)table.p;
-        }
-        if (!j.table_in_place && !j.table_direct)
-            HIP_TRY(hipMemcpyAsync(tbl, j.d_table, (size_t)n_max * sizeof(BlockOut), hipMemcpyDeviceToDevice, st));
-        if (n_max <= 256) {                                          // (a few blocks - the streaming API's one per call: one launch for the record, the verdict words and the table check)
-            hipLaunchKernelGGL(k_begin_table_small, dim3(1), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
-                               j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, (ResultRec*)d_res, (uint32_t*)bad.p);
-            bad_set = true;
-        } else {
-        hipLaunchKernelGGL(k_init_result, dim3(1), dim3(64), 0, st, (ResultRec*)d_res, n_max, 0u);
-        if (n_max) hipLaunchKernelGGL(k_check_table, dim3(std::min<uint32_t>((n_max + 255) / 256, 1024u)), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
-                                      j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, (ResultRec*)d_res);
-        }
-        plan |= LZ4F_MI355X_PATH_TABLE_GIVEN;
-    } else {
-        n_max = j.max_blocks;
-        if (table.ensure((size_t)(n_max + 1) * sizeof(BlockOut))) return make_err(LZ4F_ERROR_allocation_failed);
-        tbl = (BlockOut*)table.p;
-        tick(4, false);
-        // frames of many small blocks: the size words are found in parallel (frame_dev.cuh); k_walk_frame behind it returns at
-        // once when that has delivered, and walks the list itself otherwise (big blocks: a few hundred hops, and one in 2^9
-        // byte positions would be a candidate)
-        const uint32_t* walked = nullptr;
-        if (j.hint_list && j.hint_n <= n_max) {
-            // the frame's own trailer says where the size words are: checked link by link like the parallel walk's candidates
-            if (walkbuf.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
-            WalkState* ws = (WalkState*)walkbuf.p;
-            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws, j.hint_n);
-            hipLaunchKernelGGL(k_walk_link, dim3(std::min<uint32_t>((j.hint_n + 255) / 256, 4096u)), dim3(256), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, j.hint_list, tbl, n_max);
-            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, j.hint_list, n_max, (ResultRec*)d_res);
-            walked = &ws->done;
-            plan |= LZ4F_MI355X_PATH_TRAILER;
-        } else
-        if (j.block_size <= (256u << 10) && j.frame_cap >= (1u << 20) && !sw.serial_walk) {
-            const uint32_t n_chunks = (uint32_t)((j.frame_cap + WK_CHUNK - 1) / WK_CHUNK);
-            const size_t list_cap = (size_t)n_max + 1024;
-            const size_t at_chunks = 256, at_list = at_chunks + (size_t)n_chunks * sizeof(WalkChunk), at_list2 = at_list + list_cap * 8, at_mark = at_list2 + list_cap * 8;
-            if (walkbuf.ensure(at_mark + list_cap * 4)) return make_err(LZ4F_ERROR_allocation_failed);
-            WalkState* ws = (WalkState*)walkbuf.p;
-            WalkChunk* ch = (WalkChunk*)((uint8_t*)walkbuf.p + at_chunks);
-            uint64_t* list = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
-            uint64_t* list2 = (uint64_t*)((uint8_t*)walkbuf.p + at_list2);
-            uint32_t* mark = (uint32_t*)((uint8_t*)walkbuf.p + at_mark);
-            const uint32_t lgrid = std::min<uint32_t>((uint32_t)((list_cap + 255) / 256), 4096u);
-            HIP_TRY(hipMemsetAsync(mark, 0, list_cap * 4, st));
-            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
-            hipLaunchKernelGGL(k_walk_cand, dim3(n_chunks), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, ch);
-            hipLaunchKernelGGL(k_walk_order, dim3(1), dim3(1024), 0, st, ch, n_chunks, ws, list, (uint32_t)list_cap);
-            hipLaunchKernelGGL(k_walk_mark, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, (const uint64_t*)list, mark);
-            hipLaunchKernelGGL(k_walk_filter, dim3(1), dim3(1024), 0, st, ws, (const uint64_t*)list, (const uint32_t*)mark, list2);
-            hipLaunchKernelGGL(k_walk_link, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, (const uint64_t*)list2, tbl, n_max);
-            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, (const uint64_t*)list2, n_max, (ResultRec*)d_res);
-            walked = &ws->done;
-            plan |= LZ4F_MI355X_PATH_PARALLEL_WALK;
-            if (sw.prof) { WalkState h; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&h, ws, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "parallel walk: done %u overflow %u candidates %u first_end %u first_break %u (header ok %u, hsize %u, block %u)\n", h.done, h.overflow, h.total, h.first_end, h.first_break, h.head_ok, h.hsize, h.bs); }
-        }
-        else if (j.block_size > (256u << 10) && j.frame_cap >= (size_t)192 * j.block_size && !sw.serial_walk) {      // (~0.15 ms whatever the frame: pays from ~330 blocks of half their size on)
-            // big blocks: seeds found in parallel, a lane per seed walking to the next one (frame_dev.cuh); the list is checked link by
-            // link like the small blocks' candidates, and k_walk_frame behind walks the frame itself if it is not the chain
-            const size_t list_cap = (size_t)n_max + 1024;
-            const size_t at_seeds = 256, at_list = at_seeds + (WK_SEEDS + 1) * 8;
-            if (walkbuf.ensure(at_list + list_cap * 8)) return make_err(LZ4F_ERROR_allocation_failed);
-            WalkState* ws = (WalkState*)walkbuf.p;
-            unsigned long long* seeds = (unsigned long long*)((uint8_t*)walkbuf.p + at_seeds);
-            HIP_TRY(hipMemsetAsync(seeds, 0xFF, (WK_SEEDS + 1) * 8, st));
-            uint64_t* list = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
-            const uint32_t lgrid = std::min<uint32_t>((uint32_t)((list_cap + 255) / 256), 4096u);
-            hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
-            hipLaunchKernelGGL(k_walk_seeds, dim3(WK_SEEDS * wk_seed_pieces(j.block_size)), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, seeds);
-            hipLaunchKernelGGL(k_walk_chains, dim3(1), dim3(WK_SEEDS), 0, st, j.d_frame, j.frame_cap, ws, (const unsigned long long*)seeds, list, (uint32_t)std::min<size_t>(list_cap, 0xFFFFFFFFu));
-            hipLaunchKernelGGL(k_walk_link, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, (const uint64_t*)list, tbl, n_max);
-            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, (const uint64_t*)list, n_max, (ResultRec*)d_res);
-            walked = &ws->done;
-            plan |= LZ4F_MI355X_PATH_PARALLEL_WALK;
-            if (sw.prof) { WalkState h; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&h, ws, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "seeded walk: done %u overflow %u entries %u first_end %u first_break %u\n", h.done, h.overflow, h.total, h.first_end, h.first_break); }
-        }
-        hipLaunchKernelGGL(k_walk_frame, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, tbl, n_max, (ResultRec*)d_res, walked);
-        tick(4, true);
-    }
-    if (!bad_set) {
-        HIP_TRY(hipMemsetAsync(bad.p, 0xFF, 8, st));                 // [0] block-checksum verdict, [1] first failed block
-        HIP_TRY(hipMemsetAsync((uint8_t*)bad.p + 8, 0, 24, st));    // [2] "something has to move", [4..5] sum of sizes (k_finish_check)
-    }
-    constexpr int W = 4;
-    const uint32_t grid = j.linked ? 1u : (n_max + W - 1) / W;
+    BlockOut* tbl;
+    if (size_t e = dec_table(j, p, r, &tbl, &path)) return e;
     const uint32_t* ix_flags = nullptr;                              // the indexed kernels' "gave up" word, if they were launched
-    if (n_max) {
-        if (j.block_checksum) {
-            // The verification only reads the payloads, and so do the decode kernels: it runs beside them on the engine's second stream
-            // (forked here, joined in front of k_finish_check, which reads its verdict).  A 4 MiB block is one serial chain for one wave
-            // (~2 ms) whatever else the GPU does, so side by side the two cost max(2.0, decode) instead of the sum.  The one-wave
-            // workgroups then ask for 12 KiB of LDS instead of 36 (they would not fit beside four decode workgroups per CU).
-            const bool beside = !sw.no_overlap && aux_ready();
-            hipStream_t xs = beside ? (hipStream_t)aux_stream : st;
-            if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_fork, st)); HIP_TRY(hipStreamWaitEvent(xs, (hipEvent_t)ev_fork, 0)); }
-            tick(5, false, xs);
-            if (n_max < XXH_LANE4_BELOW)
-                hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(n_max), dim3(64), beside ? (12u << 10) : XXH_SPREAD_LDS, xs, (uint8_t*)j.d_frame, tbl, (const ResultRec*)d_res, n_max, 1u, (uint32_t*)bad.p);
-            else
-            hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, xs, (uint8_t*)j.d_frame, tbl,
-                               (const ResultRec*)d_res, n_max, 1u, (uint32_t*)bad.p);
-            tick(5, true, xs);
-            if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_join, xs)); aux_pending = true; }
-        }
+    if (p.n_max) {
+        if (j.block_checksum) { if (size_t e = dec_checksums(j, p, r, tbl)) return e; }
         tick(6, false);
-        // large blocks / linked frames: fused parse+copy workgroups ('f'); small independent blocks: one wave per block ('1')
-        char mode = (j.linked || j.block_size >= (256u << 10)) ? 'f' : '1';
-        if (sw.decode_mode) mode = sw.decode_mode;
-        bool indexed = false;
-        void* d_index = j.d_index; size_t index_size = j.index_size;
-        bool self_indexed = false;
-        uint32_t self_seqs = 0, self_entries = 0;
-        // A linked frame is one match chain without a usable index (seconds instead of milliseconds on dense data), so for
-        // those the header of the index that came along is read NOW (a host synchronisation, ~30 us): the compressor marks an
-        // index unusable when the stream had more sequences than it had room for, and then one is made here instead.
-        IxHeader hd_now; memset(&hd_now, 0, sizeof(hd_now));
-        bool have_now = false;
-        // (an index out of the frame's trailer brings its counts in the footer - no read - and its frame is one call's work: every block but the last is full,
-        // so the table the list check writes has every block's place in the output, which is what a linked frame's indexed decode needs; if a trailer lies about
-        // that the descriptors do not tile the blocks and the generic kernels take the frame)
-        const bool ix_by_trailer = j.d_index && j.ix_seqs && j.hint_list && j.hint_n <= n_max;
-        if (mode == 'f' && j.linked && j.d_index && j.index_size >= sizeof(IxHeader) && !sw.no_index && !ix_by_trailer) {
-            HIP_TRY(hipMemcpyAsync(&hd_now, j.d_index, sizeof(hd_now), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            have_now = true;
-            if (hd_now.magic != IX_MAGIC || hd_now.stride != IX_STRIDE) { d_index = nullptr; index_size = 0; have_now = false; }
-        }
-        if (mode == 'f' && j.linked && !d_index && j.hist0 <= 65536 && n_max >= 2 && !sw.no_index && !sw.no_selfindex) {
-            // A linked frame without an index (a foreign one: the reference's default output): make the index here - a lane per block
-            // walks the payload (parsing needs no history), a scan places the blocks - and take the same kernels as with the
-            // compressor's index.  Two host synchronisations (the totals size the buffers); anything odd leaves the frame to the
-            // window kernel, as before.
-            const uint32_t cpb = j.block_size / pick_chunk_size(j.block_size);
-            const size_t fixed = ix_entries_at(n_max, cpb);
-            if (selfcnt.ensure((size_t)n_max * 8 + 64) || seqcnt.ensure(256 + (size_t)n_max * (8 + 8 * IXL_PUB)) || selfix.ensure(fixed + 64))
-                return make_err(LZ4F_ERROR_allocation_failed);
-            uint32_t* cnt = (uint32_t*)selfcnt.p; uint32_t* osz = cnt + n_max;
-            HIP_TRY(hipMemsetAsync(seqcnt.p, 0, 64, st));
-            if (density.ensure(64)) return make_err(LZ4F_ERROR_allocation_failed);
-            hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, (uint32_t*)density.p);
-            hipLaunchKernelGGL((k_selfindex_walk_wave<0, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                               (const ResultRec*)d_res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
-            hipLaunchKernelGGL(k_selfindex_walk<0>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                               (const ResultRec*)d_res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
-            uint32_t tot[10];
-            for (int pass = 0; pass < 2; pass++) {
-                hipLaunchKernelGGL(k_selfindex_scan, dim3(1), dim3(1024), 0, st, tbl, (const ResultRec*)d_res, n_max, (const uint32_t*)cnt, (const uint32_t*)osz,
-                                   selfix.p, cpb, (uint64_t)j.dst_cap, j.block_size, (uint32_t*)seqcnt.p);
-                if (pass == 1) break;
-                HIP_TRY(hipMemcpyAsync(tot, seqcnt.p, sizeof(tot), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (tot[0] != 0 || tot[9] == 0) break;
-                const void* before = selfix.p;
-                if (selfix.ensure(fixed + (size_t)tot[8] * sizeof(IxEntry) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-                if (selfix.p == before) break;                                   // (same buffer: the block table is already in it)
-            }
-            if (tot[0] == 0 && tot[9] != 0) {
-                hipLaunchKernelGGL((k_selfindex_walk_wave<1, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                                   (const ResultRec*)d_res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
-                hipLaunchKernelGGL(k_selfindex_walk<1>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                                   (const ResultRec*)d_res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
-                d_index = selfix.p; index_size = fixed + (size_t)tot[8] * sizeof(IxEntry);
-                self_indexed = true;
-                plan |= LZ4F_MI355X_PATH_SELF_INDEX;
-                self_seqs = tot[9]; self_entries = tot[8];
-            }
-        }
-        bool spx_mode = false;
-        if (mode == 'f' && !j.linked && !d_index && j.block_size >= (256u << 10) && j.block_size <= (4u << 20) && !sw.no_index && !sw.no_selfindex && !sw.no_spx) {
-            // A frame of big independent blocks without an index (a foreign one: `lz4 -c`, LZ4F_compressFrame): the blocks are cut into
-            // stretches by lanes that start at guessed tokens and are stitched where they meet (decode_spx.cuh); the stretches are
-            // parsed in parallel, then the indexed kernels.  One host synchronisation (the totals size the descriptor workspace);
-            // dense payloads (k_density_probe) and anything odd stay with the generic decoders.
-            const uint32_t cpb = j.block_size / pick_chunk_size(j.block_size);
-            const size_t fixed = ix_entries_at(n_max, cpb);
-            if (selfcnt.ensure((size_t)n_max * 8 + 64) || seqcnt.ensure(256 + (size_t)n_max * (8 + 8 * IXL_PUB)) || selfix.ensure(fixed + 64) || density.ensure(64) ||
-                spx.ensure((size_t)n_max * ((SPX_MAXPT + 1) * sizeof(SpxPoint) + 4) + 64))
-                return make_err(LZ4F_ERROR_allocation_failed);
-            uint32_t* cnt = (uint32_t*)selfcnt.p; uint32_t* osz = cnt + n_max;
-            SpxPoint* spt = (SpxPoint*)spx.p; uint32_t* snr = (uint32_t*)((uint8_t*)spx.p + (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint));
-            HIP_TRY(hipMemsetAsync(seqcnt.p, 0, 256, st));
-            hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, (uint32_t*)density.p);
-            hipLaunchKernelGGL(k_spx_index, dim3(n_max), dim3(SPX_MAXSEG), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, cnt, osz,
-                               spt, snr, (uint32_t*)seqcnt.p, sw.no_density_probe ? (const uint32_t*)nullptr : (const uint32_t*)density.p + 1);
-            uint32_t tot[10];
-            for (int pass = 0; pass < 2; pass++) {
-                hipLaunchKernelGGL(k_selfindex_scan, dim3(1), dim3(1024), 0, st, tbl, (const ResultRec*)d_res, n_max, (const uint32_t*)cnt, (const uint32_t*)osz,
-                                   selfix.p, cpb, (uint64_t)j.dst_cap, j.block_size, (uint32_t*)seqcnt.p, 1u);
-                if (pass == 1) break;
-                HIP_TRY(hipMemcpyAsync(tot, seqcnt.p, sizeof(tot), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (sw.prof) fprintf(stderr, "spx: flags %u, %u sequences in %u blocks, %u stretches walked by the stitching thread\n", tot[0], tot[9], n_max, tot[2]);
-#ifdef SPX_PROF
-                { uint32_t y[8]; if (hipMemcpy(y, (uint32_t*)seqcnt.p + 48, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx lanes: hit the hop cap %u, without a start %u, started at their segment's first byte %u, ran into something %u; most sequences in one lane %u\n", y[0], y[1], y[2], y[3], y[4]); }
-                { uint32_t z[8]; if (hipMemcpy(z, (uint32_t*)seqcnt.p + 40, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx cycles: guess max %u avg %u, walk max %u avg %u, stitch max %u avg %u, workgroup max %u (waves %u)\n", z[0], (unsigned)(((unsigned long long)z[4] << 8) / (2 * n_max)), z[1], (unsigned)(((unsigned long long)z[5] << 8) / (2 * n_max)), z[2], (unsigned)(((unsigned long long)z[6] << 8) / n_max), z[3], 2 * n_max); }
-#endif
-                if (tot[0] != 0 || tot[9] == 0) break;
-                const void* before = selfix.p;
-                if (selfix.ensure(fixed + (size_t)tot[8] * sizeof(IxEntry) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-                if (selfix.p == before) break;                                   // (same buffer: the block table is already in it)
-            }
-            if (tot[0] == 0 && tot[9] != 0) {
-                d_index = selfix.p; index_size = fixed + (size_t)tot[8] * sizeof(IxEntry);
-                self_indexed = true; spx_mode = true;
-                plan |= LZ4F_MI355X_PATH_SELF_INDEX;
-                self_seqs = tot[9]; self_entries = tot[8];
-            }
-        }
-        // (linked frames: only with a table that has every block's output position - the compressor's, or the one just made)
-        if (mode == 'f' && d_index && index_size >= sizeof(IxHeader) && (!j.linked || self_indexed || ((j.d_table || j.table_in_place || j.table_direct || ix_by_trailer) && j.hist0 <= 65536)) &&
-            !sw.no_index) {
-            // Descriptors from the compressor's sequence index: a lane per entry parses, a lane per sequence resolves direct
-            // matches, a workgroup per block copies.
-            const uint32_t chunk = pick_chunk_size(j.block_size), cpb = j.block_size / chunk;
-            // (an index out of the frame's trailer is laid out for the block count the trailer names; the table and the generic
-            // kernels keep the caller's upper bound - if the walk finds another count, the index is dropped on the device)
-            const uint32_t n_ix = (j.hint_list && j.hint_n <= n_max) ? j.hint_n : n_max;
-            // How many sequences and entries the index holds comes with THIS call (the trailer's footer, the self-index scan, or one
-            // read of the index header for the explicit-index entry point): it sizes the descriptor workspace and decides whether a
-            // dense frame's scratch is worth having.  Nothing is carried over from earlier calls; the device checks the real header
-            // against the workspace (k_check_index) and hands the call to the generic decoder if it does not fit.
-            uint32_t ix_seqs = j.ix_seqs, ix_entries = j.ix_entries;
-            if (self_indexed) { ix_seqs = self_seqs; ix_entries = self_entries; }
-            else if (have_now) { ix_seqs = hd_now.total_seqs; ix_entries = hd_now.total_entries; }
-            else if (!ix_seqs) {
-                IxHeader hd; memset(&hd, 0, sizeof(hd));
-                HIP_TRY(hipMemcpyAsync(&hd, d_index, sizeof(hd), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (hd.magic == IX_MAGIC && hd.stride == IX_STRIDE) { ix_seqs = hd.total_seqs; ix_entries = hd.total_entries; }
-            }
-            if ((uint64_t)ix_seqs > (uint64_t)ix_entries * (IX_STRIDE + 1) || ix_entries > (index_size - sizeof(IxHeader)) / sizeof(IxEntry)) ix_seqs = 0;      // (not a count this index can hold)
-            const bool ix_dense = (uint64_t)ix_seqs * 48 > (uint64_t)n_ix * j.block_size;      // short sequences: worth the tracer's scratch, see below
-            const uint32_t ix_entries_hint = ix_entries;
-            if ((size_t)ix_seqs + 4096 > ix_seq_cap) ix_seq_cap = (size_t)ix_seqs + ix_seqs / 4 + 4096;
-            if (ix_seqs) {
-                const size_t dsrc_at = (ix_seq_cap + 64) * sizeof(SeqDesc);
-                if (desc.ensure(dsrc_at + (ix_seq_cap + 64) * 4) || seqcnt.ensure(256 + (size_t)n_max * (8 + 8 * IXL_PUB))) return make_err(LZ4F_ERROR_allocation_failed);
-                HIP_TRY(hipMemsetAsync(seqcnt.p, 0, 256 + (j.linked ? (size_t)n_max * 8 : 0), st));      // flags (+ per block of a linked frame: the "done" word and the count of published ranges)
-                uint32_t* done = (uint32_t*)seqcnt.p + 64;
-                uint32_t lk = j.linked ? 1u : 0u;                                  // (bits 1..: chain gate, see k_copy_indexed)
-                if (j.linked && sw.chain_gate) lk |= (uint32_t)sw.chain_gate << 1;
-                unsigned long long* iprof = (unsigned long long*)(sw.prof ? prof_buf() : nullptr);
-                tick(8, false);
-                hipLaunchKernelGGL(k_check_index, dim3(1), dim3(64), 0, st, (const void*)d_index, (uint64_t)index_size, n_ix, cpb, chunk,
-                                   (uint64_t)ix_seq_cap, (uint32_t*)seqcnt.p, (const ResultRec*)d_res);
-                // the whole block table, before any kernel behind writes (the index is input)
-                hipLaunchKernelGGL(k_check_blocks, dim3((n_ix + 255) / 256), dim3(256), 0, st, (const void*)d_index, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix,
-                                   (uint32_t*)seqcnt.p);
-                uint32_t n_lanes = ix_entries_hint > n_ix ? ix_entries_hint : n_ix;           // (grid-stride inside: a hint is enough)
-                // Independent blocks that are not dense (no tracer on offer): ONE kernel - the copy workgroup's first wave parses its block's
-                // runs and resolves direct matches while the copiers move bytes (decode_indexed.cuh: k_copy_selffed)
-                const bool can_double0 = ((uint64_t)ix_seqs * 48 > (uint64_t)n_ix * j.block_size || sw.trace_always) && (uint64_t)n_ix * j.block_size <= IXP_MAX_SPAN && !sw.no_doubling;
-                const bool selffeed = !j.linked && !sw.no_selffeed && !sw.no_resolve && !sw.trace_always && !can_double0;
-                if (selffeed) {
-                    tick(8, true);
-                    tick(9, false);
-                    if (spx_mode) {
-                        const FzSrcSpx src{(const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint))};
-                        if (j.block_size <= (1u << 20))
-                            hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, FzSrcSpx>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
-                        else
-                            hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, FzSrcSpx>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
-                    } else {
-                        const FzSrcIx src{(const void*)d_index, n_ix};
-                        if (j.block_size <= (1u << 20))
-                            hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, FzSrcIx>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
-                        else
-                            hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, FzSrcIx>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                               (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
-                    }
-                    tick(9, true);
-                    indexed = true;
-                    ix_flags = (const uint32_t*)seqcnt.p;
-                    plan |= LZ4F_MI355X_PATH_INDEXED;
-                } else {
-                if (spx_mode)                                                                 // (no entries: the stretches between the blocks' check lines)
-                    hipLaunchKernelGGL(k_spx_parse, dim3(n_ix), dim3(128), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix,
-                                       (const void*)d_index, (const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint)),
-                                       (SeqDesc*)desc.p, (uint32_t*)seqcnt.p);
-                else
-                hipLaunchKernelGGL(k_parse_indexed, dim3((n_lanes + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap,
-                                   (const BlockOut*)tbl, (const void*)d_index, n_ix, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, lk, (uint64_t)j.hist0);
-                const uint64_t trace_span = (uint64_t)n_ix * j.block_size;            // (the last block may be short)
-                const bool trace_can = !sw.no_trace && !sw.no_resolve && (j.block_size & 63u) == 0;
-                // (pointer doubling does ~12 GiB/s on text whatever the framing; hop by hop it is 1.3 GiB/s, which only pays where
-                // there is no block-level parallelism - linked frames; independent blocks then stay with the copier workgroups, 4.8 GiB/s)
-                const bool can_double = (ix_dense || sw.trace_always) && trace_span <= IXP_MAX_SPAN && !sw.no_doubling;
-                uint32_t gate = !trace_can ? 0u : sw.trace_always ? 2u : (j.linked || can_double) ? 1u : 0u;
-                if (gate && postab.ensure((size_t)(trace_span >> 6) * 4 + 512 + ((size_t)(trace_span >> IXT_REGION_LOG) + 4) * 4)) gate = 0;      // (no memory for the position table: the copiers do it)
-                if (gate && can_double)                                        // (dense by the sequence density: no need to resolve anything)
-                    hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix, 1u, 1u);
-                uint32_t* dsrc = (uint32_t*)((uint8_t*)desc.p + dsrc_at);
-                if (sw.no_resolve) dsrc = nullptr;
-                else
-                    hipLaunchKernelGGL(k_resolve_direct, dim3(n_ix, j.block_size >= (1u << 19) ? j.block_size >> 18 : 1u), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix, (const SeqDesc*)desc.p,
-                                       dsrc, (uint32_t*)seqcnt.p, (iprof ? 1u : 0u) | (gate ? 2u : 0u), lk);
-                if (iprof) {                                                   // developer aid: how many matches are direct
-                    uint32_t c[8];
-                    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(c, seqcnt.p, 32, hipMemcpyDeviceToHost) == hipSuccess)
-                        fprintf(stderr, "indexed: flags %u, matches direct after parse %u, resolved %u, left to the chain %u\n", c[0], c[4], c[5], c[6]);
-                    uint32_t x[6] = {0, 0, 0, 0, 0, 0}; if (hipMemcpy(x, (uint32_t*)seqcnt.p + 10, 24, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "indexed (linked): %u matches stay on the chain, %u of them reach into the block in front (%u blocks); not resolved because: beyond one block %u, source straddles two runs %u, run-length source %u, hop limit %u\n", x[0], x[1], n_ix, x[2], x[3], x[4], x[5]);
-                }
-                // dense frames (text): no chain at all, every output byte traced to its literal (see k_trace_copy)
-                {
-                    hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix, 0u, j.block_size >= (1u << 19) ? j.block_size >> 18 : 1u);
-                    if (gate) {
-                        hipLaunchKernelGGL(k_build_postab, dim3(n_ix, j.block_size >= (1u << 19) ? j.block_size >> 18 : 1u), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)d_res, n_ix,
-                                           (const SeqDesc*)desc.p, (uint32_t*)postab.p, (uint32_t*)seqcnt.p);
-                        const uint64_t n_thr = (trace_span + IXT_TB - 1) / IXT_TB;
-                        // if the last index seen here was of a dense stream (the device decides about THIS one, but the
-                        // scratch - 4 bytes per output byte - and 18 launches are the host's to spend): one hop per byte, then pointer doubling
-                        const uint32_t pd_grid = (uint32_t)((trace_span / 4 + 255) / 256), pd_ngrp = pd_grid * 4u;      // (k_pd_round: a wave per 256 bytes)
-                        const size_t pd_grp_at = (((size_t)trace_span * 4 + 255) & ~(size_t)255) + (((IXP_ROUNDS + 1) * IXP_STRIPES * 4 + 255) & ~(size_t)255);
-                        const bool doubling = can_double && !pdbuf.ensure(pd_grp_at + 2 * (size_t)pd_ngrp + 256);
-                        if (doubling) {
-                            plan |= LZ4F_MI355X_PATH_DOUBLING;
-                            uint32_t* remaining = (uint32_t*)((uint8_t*)pdbuf.p + (((size_t)trace_span * 4 + 255) & ~(size_t)255));
-                            if (hipMemsetAsync(remaining, 0, (IXP_ROUNDS + 1) * IXP_STRIPES * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
-                            hipLaunchKernelGGL(k_pd_init, dim3((uint32_t)((n_thr + 255) / 256)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
-                                               (const ResultRec*)d_res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
-                                               lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, (uint32_t*)pdbuf.p, remaining);
-                            for (uint32_t r = 1; r <= IXP_ROUNDS; r++)
-                                hipLaunchKernelGGL(k_pd_round, dim3(pd_grid), dim3(256), 0, st, j.d_dst, (uint32_t*)pdbuf.p, (const BlockOut*)tbl,
-                                                   (const ResultRec*)d_res, n_ix, r, remaining, (uint32_t*)seqcnt.p, (uint8_t*)pdbuf.p + pd_grp_at, pd_ngrp);
-                            hipLaunchKernelGGL(k_pd_verdict, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, (const uint32_t*)remaining);
-                            if (iprof) { static uint32_t t[(IXP_ROUNDS + 1) * IXP_STRIPES]; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(t, remaining, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess) { fprintf(stderr, "doubling: bytes open after each round:"); for (uint32_t r = 0; r <= IXP_ROUNDS; r++) { uint64_t sum = 0; for (uint32_t q = 0; q < IXP_STRIPES; q++) sum += t[r * IXP_STRIPES + q]; fprintf(stderr, " %llu", (unsigned long long)sum); } fprintf(stderr, "\n"); } }
-                        } else {
-                        plan |= LZ4F_MI355X_PATH_TRACE_HOPS;
-                        uint32_t* region_cnt = (uint32_t*)((uint8_t*)postab.p + (((size_t)(trace_span >> 6) * 4 + 255) & ~(size_t)255));
-                        if (hipMemsetAsync(region_cnt, 0, ((size_t)(trace_span >> IXT_REGION_LOG) + 2) * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
-                        const uint32_t tc_wg = (uint32_t)((n_thr + 255) / 256);
-                        hipLaunchKernelGGL(k_trace_copy, dim3(std::min<uint32_t>(tc_wg, 8192u)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
-                                           (const ResultRec*)d_res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
-                                           lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, region_cnt, iprof ? 1u : 0u, tc_wg);
-                        if (iprof) { uint32_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(t, (uint32_t*)seqcnt.p + 24, 32, hipMemcpyDeviceToHost) == hipSuccess && t[0]) fprintf(stderr, "traced: %llu turns for %u pieces (%u read from the output), deepest thread %u turns\n", (unsigned long long)t[2] | ((unsigned long long)t[3] << 32), t[4], t[5], t[6]); }
-                        }
-                    }
-                }
-                tick(8, true);
-                tick(9, false);
-                // (linked frames of small blocks: a workgroup takes a group of consecutive blocks - see k_copy_indexed)
-                // (a group is 1 MiB of blocks where that fills the machine - 1024 workgroups of the 4-wave shape are half of its wave slots - and less for
-                // smaller frames: LZ4F_MI355X_GROUP_KIB sets it)
-                const uint32_t group_bytes = sw.group_kib ? sw.group_kib << 10 : ((uint64_t)n_ix * j.block_size <= (2ull << 30) ? (512u << 10) : (1u << 20));      // (1 GiB: 512 KiB 0.509 ms, 1 MiB 0.541, 256 KiB 0.788, 2 MiB 0.778)
-                const uint32_t group = (j.linked && j.block_size < group_bytes && !sw.no_groups) ? group_bytes / j.block_size : 1u;
-                const uint32_t n_wg = (n_ix + group - 1) / group;
-                // (how long a group of a linked frame waits for the one in front: half a second plus 20 ticks of the 100 MHz clock per
-                // output byte - 5 MB/s, a fifth of the slowest chain measured (text, linked, 27 MB/s); LZ4F_MI355X_WAIT_TICKS overrides)
-                const uint64_t wait_ticks = sw.wait_ticks ? sw.wait_ticks : 50000000ull + 20ull * n_ix * j.block_size;
-                if (j.block_size <= (1u << 20))
-                    hipLaunchKernelGGL(k_copy_indexed<FzCfg<4>>, dim3(n_wg), dim3(64 * 4), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                       d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (uint32_t*)seqcnt.p, iprof, lk, done, group, (uint64_t)j.hist0, wait_ticks);
-                else
-                    hipLaunchKernelGGL(k_copy_indexed<FzCfg<8>>, dim3(n_wg), dim3(64 * 8), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)d_res, n_ix,
-                                       d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (uint32_t*)seqcnt.p, iprof, lk, done, group, (uint64_t)j.hist0, wait_ticks);
-                tick(9, true);
-                if (iprof && j.linked) { uint32_t y[4] = {0, 0, 0, 0}; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(y, (uint32_t*)seqcnt.p + 20, 16, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "indexed (linked): blocks that found the block in front at state 3: %u (of those, had to wait for all of it: %u); blocks with set-aside matches %u (block in front already done: %u)\n", y[0], y[1], y[2], y[3]); }
-                hipLaunchKernelGGL(k_check_tails, dim3((n_ix + 255) / 256), dim3(256), 0, st, tbl, (const ResultRec*)d_res, n_ix, (const void*)d_index,
-                                   (const SeqDesc*)desc.p, (uint64_t)ix_seq_cap, j.block_size, (const uint32_t*)seqcnt.p);
-                indexed = true;
-                ix_flags = (const uint32_t*)seqcnt.p;
-                plan |= LZ4F_MI355X_PATH_INDEXED;
-                }
-            }
-        }
-        if (mode == 'f') {
-            unsigned long long* prof = (unsigned long long*)(sw.prof ? prof_buf() : nullptr);
-            // more blocks than the machine has 8-wave workgroup slots: the 4-wave shape keeps twice as many in flight
-            const bool small = !j.linked && j.block_size <= (1u << 20);
-            // a linked frame is one chain: one workgroup with the 64 KiB window in LDS; frames with short (flushed) blocks
-            // set the flag and are decoded by the generic kernel launched right behind (it returns at once otherwise)
-            // (one block of a linked frame - what the streaming functions hand over per call: the window kernel is built for whole frames
-            // and takes 180-210 us for a single 64 KiB block; the fused workgroup takes it directly)
-            const bool windowed = j.linked && j.dst_cap < 0xFFF00000ull && !sw.no_window && !(n_max == 1 && (j.d_table || j.table_in_place || j.table_direct));
-            const uint32_t* only_if = indexed ? (const uint32_t*)seqcnt.p : nullptr;      // behind the indexed kernels the generic ones only run if they gave up
-            if (windowed) {
-                plan |= LZ4F_MI355X_PATH_WINDOW;
-                if (!indexed && seqcnt.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
-                uint32_t* fb = (uint32_t*)seqcnt.p + (indexed ? 16 : 0);                  // (word 0 is the indexed kernels' flag)
-                hipLaunchKernelGGL(k_decode_linked, dim3(1), dim3(64 * LK_WAVES), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
-                                   (const ResultRec*)d_res, n_max, j.block_size, j.hist0, fb, only_if);
-                only_if = fb;
-                if (sw.prof) {                              // developer aid: why the windowed kernel stopped, if it did
-                    uint32_t dbg[3] = {0, 0, 0};
-                    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(dbg, fb, 12, hipMemcpyDeviceToHost) == hipSuccess)
-                        fprintf(stderr, "k_decode_linked: fallback %u why %u block %u\n", dbg[0], dbg[1], dbg[2]);
-                }
-            }
-            plan |= LZ4F_MI355X_PATH_FUSED;
-            // big independent blocks and no index to go by: a look at the payload decides between the fused workgroups and - dense data -
-            // the wave-per-block decoder (k_density_probe); both are launched, one of them returns at once
-            if (!indexed && !j.linked && !sw.no_density_probe) {
-                if (density.ensure(64)) return make_err(LZ4F_ERROR_allocation_failed);
-                hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, (uint32_t*)density.p);
-                // Few big blocks: a wave per block leaves the machine idle and waits out every trip to memory (13-15 GiB/s for a GiB in 4 MiB blocks);
-                // a workgroup per block with the block's window in LDS and its waves taking the payload in turns (decode_relay.cuh) is three times
-                // as fast per block - but it has a CU to itself, so from ~3 blocks per CU on the waves win again (8 GiB in 4 MiB blocks: 90 GiB/s).
-                if (j.block_size > 65536u && sw.dense_mode != 2 && (sw.dense_mode == 1 || n_max <= 3u * device_cus(device))) {
-                    plan |= LZ4F_MI355X_PATH_WORKGROUP_PER_BLOCK;
-                    hipLaunchKernelGGL((k_decode_blocks_relay<RELAY_W, RELAY_S>), dim3(n_max), dim3(64 * (RELAY_W + RELAY_S + 3)), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)d_res, n_max, (uint64_t)j.frame_cap,
-                                       (const uint32_t*)density.p);
-                } else
-                hipLaunchKernelGGL((k_decode_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl, (const ResultRec*)d_res,
-                                   n_max, 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap, (const uint32_t*)density.p);
-                only_if = (const uint32_t*)density.p + 1;
-                plan |= LZ4F_MI355X_PATH_WAVE_PER_BLOCK;
-            }
-            if (small)
-                hipLaunchKernelGGL(k_decode_blocks_fused<FzCfg<4>>, dim3(n_max), dim3(64 * 4), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
-                                   (const ResultRec*)d_res, n_max, 0u, j.block_size, j.hist0, prof, only_if);
-            else
-                hipLaunchKernelGGL(k_decode_blocks_fused<FzCfg<8>>, dim3(j.linked ? 1u : n_max), dim3(64 * 8), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
-                                   (const ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size, j.hist0, prof, only_if);
-        } else {
-            plan |= LZ4F_MI355X_PATH_WAVE_PER_BLOCK;
-            hipLaunchKernelGGL((k_decode_blocks<W>), dim3(grid), dim3(64 * W), sw.dblk_lds, st, j.d_frame, j.d_dst, j.dst_cap, tbl, (const ResultRec*)d_res,
-                               n_max, j.linked ? 1u : 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap);
-        }
+        IndexSrc ix;
+        if (size_t e = dec_index(j, p, r, tbl, &ix, &path)) return e;
+        if (size_t e = dec_indexed(j, p, r, tbl, ix, &ix_flags, &path)) return e;
+        if (size_t e = dec_generic(j, p, r, tbl, ix_flags, &path)) return e;
         tick(6, true);
     }
     if (aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)ev_join, 0)); aux_pending = false; }
-    tick(7, false);
-    // liblz4 judges a block against maxBlockSize whatever room the caller leaves it.  Only a walked frame's last block can be left less
-    // (every other block sits below a provisional block's room the walk found inside the buffer), and only when the capacity is not a
-    // multiple of the block size: a last block that failed in that room is decoded again with a whole block's room, and copied out if it fits.
-    if (n_max && !j.d_table && !j.table_in_place && !j.table_direct && j.block_size && j.dst_cap % j.block_size != 0) {
-        if (tight.ensure((size_t)65536 + j.block_size + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-        hipLaunchKernelGGL(k_redo_tight_block, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (uint64_t)j.dst_cap, tbl,
-                           (const ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size, (uint64_t)j.hist0, (uint8_t*)tight.p);
-    }
-    const bool check_here = n_max <= 64;                              // (the finishing wave looks at a few blocks itself: a launch less)
-    if (n_max && !check_here) hipLaunchKernelGGL(k_finish_check, dim3((n_max + 255) / 256), dim3(256), 0, st, (const BlockOut*)tbl, (const ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size, (uint32_t*)bad.p);
-    hipLaunchKernelGGL(k_finish_decode, dim3(1), dim3(64), 0, st, j.d_dst, tbl, (ResultRec*)d_res, n_max, j.linked ? 1u : 0u, j.block_size,
-                       (const uint32_t*)bad.p, j.block_checksum ? 1u : 0u, plan, ix_flags, check_here ? 1u : 0u, (uint64_t)j.dst_cap);
-    if (j.content_checksum && !j.d_table && !j.table_in_place && !j.table_direct && !sw.no_content_check)      // (a whole frame was walked: res->consumed is behind its checksum word)
-        hipLaunchKernelGGL(k_xxh32_content, dim3(1), dim3(64), 0, st, (const uint8_t*)j.d_dst, 0ull, (uint8_t*)j.d_frame, (ResultRec*)d_res, 1u);
-    tick(7, true);
+    if (size_t e = dec_finish(j, p, r, tbl, ix_flags, path)) return e;
     tick(11, true);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1422,14 +1428,7 @@ size_t lz4f_mi355x_dev_decompressBlocks(lz4f_mi355x_engine* e, void* d_dst, size
                                         const lz4f_mi355x_block* d_table, uint32_t n_blocks, const LZ4F_frameInfo_t* info,
                                         lz4f_mi355x_result* d_result)
 {
-    if (!e || !d_table || !info) return make_err(LZ4F_ERROR_GENERIC);
-    const size_t bs = block_size_of(info->blockSizeID);
-    if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    lz4f_mi355x_engine::DecompressJob j; memset(&j, 0, sizeof(j));
-    j.d_frame = (const uint8_t*)d_frame; j.frame_cap = frameCapacity; j.d_dst = (uint8_t*)d_dst; j.dst_cap = dstCapacity; j.hist0 = 0;
-    j.block_size = (uint32_t)bs; j.linked = info->blockMode == LZ4F_blockLinked; j.block_checksum = info->blockChecksumFlag != 0;
-    j.d_table = d_table; j.n_blocks = n_blocks; j.max_blocks = n_blocks;
-    return e->launch_decompress(j, d_result);
+    return lz4f_mi355x_dev_decompressBlocksIndexed(e, d_dst, dstCapacity, d_frame, frameCapacity, d_table, n_blocks, info, nullptr, 0, d_result);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

@@ -47,6 +47,8 @@ struct PinBuf {
     void release();
 };
 
+struct BlockOut; struct ResultRec;                       // (common.cuh)
+
 }  // namespace lz4f
 
 struct lz4f_mi355x_engine {
@@ -101,7 +103,7 @@ struct lz4f_mi355x_engine {
                            void* d_index = nullptr, size_t index_cap = 0);
     struct DecompressJob {
         const uint8_t* d_frame; uint64_t frame_cap; uint8_t* d_dst; uint64_t dst_cap; uint64_t hist0;
-        void* d_index; size_t index_size;   // sequence index written by launch_compress (optional; independent blocks only)
+        void* d_index; size_t index_size;   // sequence index written by launch_compress (optional; a linked frame uses it when its block table is given or comes from the trailer)
         uint32_t block_size; bool linked; bool block_checksum;
         bool content_checksum;                                   // the frame's FLG asks for one: verified behind the decode (k_xxh32_content)
         const lz4f_mi355x_block* d_table; uint32_t n_blocks;     // when d_table != null the walk is skipped
@@ -144,6 +146,37 @@ struct lz4f_mi355x_engine {
     ~lz4f_mi355x_engine();
 
 private:
+    // ---- launch_decompress: a plan, then one function per stage, in the order they run (engine.hip) ----
+    // What a decode call does that depends on the call alone (job, switches, CU count), never on what is read back from the device
+    struct DecodePlan {
+        bool given, begin_small;     // a block table came with the call: no walk; a given table of a few blocks: one launch begins the call
+        uint32_t n_max, n_ix;        // blocks: the given table's count or the walk's bound; the blocks the index is laid out for
+        enum Walk { WALK_NONE, WALK_TRAILER, WALK_PARALLEL, WALK_SEEDED, WALK_SERIAL } walk;
+        char mode;                   // 'f': fused workgroups, behind the indexed kernels when there is an index; '1': a wave per block
+        bool ix_by_trailer;          // the index came out of the frame's trailer, its counts in the footer
+        bool self_index;             // no usable index came with the call: one may be made on the device (dec_self_index)
+        bool windowed, small, relay; // the window kernel first; the fused workgroups' 4-wave shape; dense big blocks: a workgroup per block
+        uint32_t group;              // consecutive blocks per workgroup of k_copy_indexed
+        uint64_t wait_ticks;         // how long a group of a linked frame waits for the one in front
+    };
+    // the sequence index a call decodes by (d null: none, the generic kernels decode) and where it came from
+    struct IndexSrc {
+        enum From { GIVEN, TRAILER, HEADER, SELF_LINKED, SPX } from = GIVEN;
+        void* d = nullptr; size_t size = 0;
+        uint32_t seqs = 0, entries = 0;      // what it holds: sizes the descriptor workspace (the device checks the real header against it)
+    };
+    // how the indexed kernels decode: one kernel (k_copy_selffed) or the chain; a dense frame by pointer doubling or hop by hop; k_dense_gate's mode
+    struct IxRoute { bool selffed, doubling; uint32_t gate; };
+    static DecodePlan decode_plan(const DecompressJob& j, const Switches& sw, uint32_t cus);
+    static IxRoute ix_route(const DecompressJob& j, const Switches& sw, uint32_t n_ix, uint32_t ix_seqs);
+    size_t dec_table(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut** tbl, uint32_t* path);
+    size_t dec_checksums(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl);
+    size_t dec_index(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, IndexSrc* ix, uint32_t* path);
+    size_t dec_self_index(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, bool spx_walk, IndexSrc* ix);
+    size_t dec_indexed(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const IndexSrc& ix, const uint32_t** ix_flags, uint32_t* path);
+    size_t dec_generic(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const uint32_t* only_if, uint32_t* path);
+    size_t dec_finish(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const uint32_t* ix_flags, uint32_t path);
+
     size_t run_decode_slab(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries,
                            const lz4f::ParsedHeader& ph, const uint8_t* hist, size_t hist_len, uint8_t* dst, size_t dst_room, size_t* got);
 };
