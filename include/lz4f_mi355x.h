@@ -352,6 +352,37 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressBlocksIndexed(lz4f_mi355x_engin
                                                                const LZ4F_frameInfo_t* info, const void* d_index, size_t indexSize,
                                                                lz4f_mi355x_result* d_result);
 
+/* BATCH: n_frames independent frames in one call, with no host synchronisation and no device->host copy.
+ * Frame i is the first frame in d_src[src_off[i] .. src_off[i+1]); its output window is d_dst[dst_off[i] .. dst_off[i+1]).
+ * d_src_off / d_dst_off: n_frames + 1 uint64 each, DEVICE memory.  srcBytes / dstBytes: the extents of d_src / d_dst (host values:
+ * they size the workspace and bound every span).  d_results: n_frames records, DEVICE memory.  Asynchronous on the engine's stream.
+ *   - A frame in a batch decodes exactly as it would alone: d_results[i] and the bytes of window i are what
+ *     lz4f_mi355x_dev_decompressFrame gives for that span and window (status, size, consumed, n_blocks, first_bad_block,
+ *     flags & 0x1FF), with LZ4F_MI355X_PATH_BATCH as the path bits (flags >> 12).  One difference: for a malformed LINKED
+ *     frame first_bad_block is the first block that does not decode in its own block's room (as liblz4 judges it); the single
+ *     call's linked-frame kernels may name a later block of the same frame.  Where the single call rejects a header on
+ *     the host and returns the error code, the batch writes that code to d_results[i].status.  A skippable frame at the
+ *     start of a span is reported as the single call reports it (flag bit 8, consumed = the skippable frame); this library's
+ *     in-band trailer behind a frame is not used, and not counted in consumed (as with the single call).
+ *   - Frames are isolated: no kernel writes outside window i on behalf of frame i, whatever its bytes are, and a malformed
+ *     frame changes no other frame's result or bytes.  The offsets are checked on the device: src_off[i] > src_off[i+1] or a
+ *     span ending past srcBytes gives that frame ERROR_srcPtr_wrong, the same of the window against dstBytes
+ *     ERROR_dstMaxSize_tooSmall; nothing is written for it.  Windows that overlap each other are the caller's race.
+ *   - The call itself fails only on a null engine, a null pointer with n_frames > 0, or a failed allocation (of a workspace of
+ *     80 bytes per frame + 40 bytes per (n_frames + dstBytes / 64 KiB + 1) block-table entries, grown as needed).
+ *     n_frames == 0 is a no-op that returns 0.  Bytes in a failed frame's window are unspecified, as with the single call.
+ * Independent blocks are decoded a wave per block across all frames; linked frames a wave per frame with the blocks in order;
+ * content checksums a wave per frame, side by side.  (Every block of a frame has its provisional place, block b at b * maxBlockSize,
+ * inside the window, so frames whose windows do not overlap always fit the block table; where overlapping windows overflow it, the
+ * independent frames behind the overflow are decoded a wave per frame too, with the same results.)  A big
+ * frame of many blocks gets none of the single call's parallel walks, indexed or workgroup-per-block decoders: send such
+ * frames through lz4f_mi355x_dev_decompressFrame.  Trailers and sequence indexes are not used. */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                        const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                        void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                        lz4f_mi355x_result* d_results);
+#define LZ4F_MI355X_PATH_BATCH 0x1000u   /* result.flags bits 12..: the frame went through the batch decoder (dev_decompressFrames) */
+
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,
                                              const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out);

@@ -42,9 +42,20 @@ __device__ __forceinline__ uint64_t fetch8(const uint8_t* __restrict__ in_al, ui
 //   in      : payload (csize bytes), any alignment, read-only for the whole launch
 //   out     : where this block's bytes go; `hist` valid bytes lie directly in front of it
 //   cap     : bytes available at out (maxBlockSize, or what is left of the destination)
-__device__ __forceinline__ int32_t wave_decode_block(const uint8_t* __restrict__ in, uint32_t csize,
-                                                     uint8_t* out, uint32_t cap, uint64_t hist)
+// LIM (the batch decoder's tight last block, decode_batch.cuh): the block is judged by `cap` but only the first `wlim` (<= cap)
+// bytes may be written - a run that would end beyond wlim is not copied and the parse goes on, so that a block that decodes,
+// only not into wlim, returns -2 and one that does not decode at all -1.  Without LIM wlim is not looked at (wave_decode_block).
+template <bool LIM>
+__device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restrict__ in, uint32_t csize,
+                                                         uint8_t* out, uint32_t cap, uint32_t wlim, uint64_t hist)
 {
+    bool over = false;                         // (LIM: something was not written)
+    auto fits = [&](uint32_t op, uint32_t len) -> bool {
+        if (!LIM) return true;
+        if (!over && (uint64_t)op + len <= wlim) return true;
+        over = true;
+        return false;
+    };
     if (csize == 0) return -1;
     const uint32_t mis = (uint32_t)((uintptr_t)in & 3u);
     const uint8_t* __restrict__ in_al = in - mis;
@@ -80,11 +91,11 @@ __device__ __forceinline__ int32_t wave_decode_block(const uint8_t* __restrict__
         if ((uint64_t)lit + 12 > out_left || (uint64_t)lit + 8 > in_left) {
             // must be the last sequence: literals end exactly at the payload end
             if (lit != in_left || lit > out_left) return -1;
-            wave_copy_disjoint(out + op, in_al + ip, lit);
+            if (fits(op, lit)) wave_copy_disjoint(out + op, in_al + ip, lit);
             op += lit;
-            return (int32_t)op;
+            return (LIM && over) ? -2 : (int32_t)op;
         }
-        wave_copy_disjoint(out + op, in_al + ip, lit);
+        if (fits(op, lit)) wave_copy_disjoint(out + op, in_al + ip, lit);
         ip += lit; op += lit;
 
         // ---- match ------------------------------------------------------------------------
@@ -110,9 +121,14 @@ __device__ __forceinline__ int32_t wave_decode_block(const uint8_t* __restrict__
         }
         mlen += 4;
         if ((uint64_t)mlen + 5 > (uint64_t)(oend - op)) return -1;       // last 5 bytes must be literals
-        wave_copy_match(out + op, offset, mlen);
+        if (fits(op, mlen)) wave_copy_match(out + op, offset, mlen);
         op += mlen;
     }
+}
+__device__ __forceinline__ int32_t wave_decode_block(const uint8_t* __restrict__ in, uint32_t csize,
+                                                     uint8_t* out, uint32_t cap, uint64_t hist)
+{
+    return wave_decode_block_lim<false>(in, csize, out, cap, cap, hist);
 }
 
 // ---- independent small blocks: the lanes look for the tokens ----

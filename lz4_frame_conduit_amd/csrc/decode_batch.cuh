@@ -1,0 +1,347 @@
+// decode_batch.cuh -- many independent frames in one call (lz4f_mi355x_dev_decompressFrames), no host read in between.
+//
+// The single-frame call reads the header back to the host to pick its plan; here every frame carries its own plan on the
+// device, and every kernel takes all frames at once:
+//   k_bf_head    a thread per frame: the span and the window checked against the buffers, then k_walk_frame's rules (skippable
+//                frames, header, size words, EndMark, content checksum word) -> a BatchFrame record and a block count
+//   k_bf_place   one workgroup: exclusive scan of the counts -> each frame's slice of the block table.  Independent frames get one;
+//                the table is sized n_frames + dstBytes / 64 KiB + 1 by the host, so the workspace needs no read-back.  A walked frame
+//                has n_blocks <= window / 64 KiB + 1 (every block's provisional place, b * maxBlockSize, lies inside its window), so
+//                frames whose windows do not overlap always fit; only windows that overlap can overflow the table, and a frame
+//                behind the overflow is decoded by k_bf_serial instead - it still decodes as it would alone
+//   k_bf_table   a thread per placed frame walks its size words again and writes its entries
+//   k_bf_blocks  a wave per entry: block checksum, then the block decoded as k_decode_blocks does (wave_decode_block_win), its
+//                readable bound the frame's span end
+//   k_bf_serial  a wave per frame that has no table slice (linked frames; independent frames behind a table overflow): checksums
+//                and blocks in order, history from the frame's own window; the verdict as k_finish_decode gives it
+//   k_bf_finish  a wave per frame: the placed frames' verdict (tight last block, first failure, packing, content size), then
+//                every frame's content checksum - the chains of different frames run side by side - and the result record
+// Nothing is written outside a frame's window on its behalf: every decode is bounded by the block's room inside the window, and
+// the one decode that is judged against a whole block (the tight last block, k_redo_tight_block's rule) only writes what fits.
+#pragma once
+#include "common.cuh"
+#include "decode.cuh"
+#include "frame_dev.cuh"
+
+namespace lz4f {
+
+constexpr uint32_t BF_NONE = 0xFFFFFFFFu;
+constexpr uint32_t BF_SHARE = 65536;       // table entries per frame: window / BF_SHARE + 1
+
+struct BatchFrame {                         // per frame (device workspace, 80 bytes)
+    uint64_t src, span;                     // the frame's span in d_src
+    uint64_t dst, win;                      // its window in d_dst
+    uint64_t consumed, size;                // as the result record (size: the declared content size until the verdict)
+    uint32_t status, flags, n_blocks, first_bad;
+    uint32_t bs, hsize, tbl_at, pad;        // tbl_at: first table entry, BF_NONE: k_bf_serial decodes it
+};
+struct BatchBlk {                           // block table entry (40 bytes)
+    uint64_t src, dst;                      // payload in d_src, block's place in d_dst (block b of its frame at b * maxBlockSize)
+    uint32_t word, room, frame, ck;         // size word, bytes of the window from dst on (<= maxBlockSize), frame, checksum failed
+    int32_t got, pad;                       // decoded bytes; -1 malformed, -2 does not fit
+};
+
+__device__ __forceinline__ uint32_t bf_rd32(const uint8_t* p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
+// decodes but not into wlim
+__device__ __forceinline__ int32_t bf_decode_block(const uint8_t* __restrict__ in, uint32_t csize, uint8_t* out, uint32_t cap, uint32_t wlim,
+                                                   uint64_t hist)
+{
+    return wave_decode_block_lim<true>(in, csize, out, cap, wlim, hist);
+}
+
+// dst[0..len) = src[0..len) with dst < src (a block of an independent frame moved down to where the blocks in front of it end)
+__device__ __forceinline__ void bf_move_down(uint8_t* dst, const uint8_t* src, uint64_t len)
+{
+    const uint32_t lane = lane_id();
+    uint64_t o = 0;
+    for (; o + 1024 <= len; o += 1024) {                    // (a step reads 1 KiB above everything it and the steps before wrote)
+        const b16_ua v = *(const b16_ua*)(src + o + lane * 16);
+        *(b16_ua*)(dst + o + lane * 16) = v;
+    }
+    for (; o < len; o += WAVE) {
+        uint8_t v = 0;
+        if (o + lane < len) v = src[o + lane];
+        if (o + lane < len) dst[o + lane] = v;
+    }
+}
+
+// the tight last block (k_redo_tight_block): judged against a whole block, written only if it fits.  -> size, -2 or -3
+__device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz, uint8_t* out, uint32_t bs, uint32_t room, uint64_t hist)
+{
+    const int32_t g = bf_decode_block(in, csz, out, bs, room, hist);
+    return g == -1 ? -3 : g;
+}
+
+// k_finish_decode's verdict on a failed block
+__device__ __forceinline__ uint32_t bf_block_status(int32_t kind, uint64_t at, uint64_t win, uint32_t bs)
+{
+    const bool short_room = at <= win && win - at < bs && kind != -3;
+    return (kind == -2 || short_room) ? 11u /* dstMaxSize_tooSmall */ : 1u /* GENERIC */;
+}
+
+__global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src, uint64_t src_bytes, const uint64_t* __restrict__ soff,
+                                                 uint64_t dst_bytes, const uint64_t* __restrict__ doff, uint32_t n_frames,
+                                                 BatchFrame* __restrict__ frames, uint32_t* __restrict__ counts)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_frames) return;
+    BatchFrame r;
+    r.src = soff[i]; r.span = 0; r.dst = doff[i]; r.win = 0; r.consumed = 0; r.size = 0;
+    r.status = 0; r.flags = 0; r.n_blocks = 0; r.first_bad = BF_NONE; r.bs = 0; r.hsize = 0; r.tbl_at = BF_NONE; r.pad = 0;
+    const uint64_t s1 = soff[i + 1], d1 = doff[i + 1];
+    uint32_t count = 0;
+    auto put = [&](uint32_t st) { r.status = st; frames[i] = r; counts[i] = count; };
+    if (r.src > s1 || s1 > src_bytes) { r.src = 0; r.dst = 0; return put(15); }         // srcPtr_wrong: nothing is read or written
+    if (r.dst > d1 || d1 > dst_bytes) { r.src = 0; r.dst = 0; return put(11); }         // dstMaxSize_tooSmall
+    r.span = s1 - r.src; r.win = d1 - r.dst;
+    // k_walk_frame's rules, in its order (the single call's host-side header checks are the same checks)
+    const uint8_t* f = src + r.src;
+    const uint64_t cap = r.span, win = r.win;
+    if (cap < 7) return put(12);
+    const uint32_t magic = bf_rd32(f);
+    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {                                         // skippable frame: no output
+        if (cap < 8) return put(12);
+        const uint64_t sz = bf_rd32(f + 4);
+        if (cap < 8 + sz) return put(12);
+        r.consumed = 8 + sz; r.flags = 0x100;
+        return put(0);
+    }
+    uint32_t hsize = 0, bs = 0, bck = 0, flg = 0; uint64_t content = 0;
+    if (const uint32_t st = walk_header(f, cap, hsize, bs, bck, flg, content)) return put(st);
+    r.flags = flg; r.bs = bs; r.hsize = hsize;
+    uint64_t tcap = win / bs + 2, by_src = cap / 5 + 2;                                  // the single call's table bound
+    if (by_src < tcap) tcap = by_src;
+    if (tcap > 0x7FFFFFFFull) tcap = 0x7FFFFFFFull;
+    uint64_t pos = hsize, out = 0;
+    uint32_t n = 0;
+    if (cap - pos < 4) return put(12);
+    for (;;) {
+        const uint32_t w = bf_rd32(f + pos);
+        pos += 4;
+        if (w == 0) break;
+        const uint32_t csz = w & 0x7FFFFFFFu;
+        if (csz > bs) return put(2);
+        if (cap - pos < (uint64_t)csz + 4 * bck) return put(12);
+        if (n >= tcap) return put(11);
+        if (out >= win) return put(11);
+        out += bs; pos += (uint64_t)csz + 4 * bck; n++;
+        if (cap - pos < 4) return put(12);
+    }
+    if ((flg >> 2) & 1) { if (cap - pos < 4) return put(12); pos += 4; }
+    r.n_blocks = n; r.consumed = pos; r.size = content;
+    const bool linked = !((flg >> 5) & 1);
+    if (!linked) count = n;                                                             // (<= win / BF_SHARE + 1: out < win held for every block)
+    put(0);
+}
+
+// one workgroup: exclusive scan of the counts; a frame whose slice would end beyond the table (only windows that overlap can do
+// that) is left to k_bf_serial.  ctl[0]: the entries in use
+__global__ __launch_bounds__(1024) void k_bf_place(const uint32_t* __restrict__ counts, uint32_t n_frames, BatchFrame* __restrict__ frames,
+                                                   uint64_t table_cap, uint32_t* __restrict__ ctl)
+{
+    __shared__ uint64_t wsum[16];
+    __shared__ uint64_t carry_s;
+    const uint32_t t = threadIdx.x, lane = lane_id(), wv = t >> 6;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < n_frames; base += 1024) {
+        const uint32_t i = base + t;
+        const uint64_t c = i < n_frames ? counts[i] : 0u;
+        uint64_t incl = c;
+        for (uint32_t d = 1; d < WAVE; d <<= 1) { const uint64_t x = __shfl_up(incl, d); if (lane >= d) incl += x; }
+        if (lane == WAVE - 1) wsum[wv] = incl;
+        __syncthreads();
+        uint64_t before = carry_s;
+        for (uint32_t k = 0; k < wv; k++) before += wsum[k];
+        const uint64_t at = before + incl - c;
+        if (c && at + c <= table_cap) frames[i].tbl_at = (uint32_t)at;
+        __syncthreads();
+        if (t == 1023) carry_s = before + incl;
+        __syncthreads();
+    }
+    if (t == 0) ctl[0] = (uint32_t)(carry_s < table_cap ? carry_s : table_cap);
+}
+
+__global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ src, const BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                                  BatchBlk* __restrict__ table)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_frames) return;
+    const BatchFrame r = frames[i];
+    if (r.status != 0 || r.tbl_at == BF_NONE) return;
+    const uint8_t* f = src + r.src;
+    const uint32_t bck = (r.flags >> 4) & 1;
+    uint64_t pos = r.hsize;
+    for (uint32_t b = 0; b < r.n_blocks; b++) {                 // (k_bf_head walked this frame: every block is there)
+        const uint32_t w = bf_rd32(f + pos);
+        pos += 4;
+        const uint64_t out = (uint64_t)b * r.bs;
+        BatchBlk e;
+        e.src = r.src + pos; e.dst = r.dst + out; e.word = w;
+        e.room = (uint32_t)(r.win - out < r.bs ? r.win - out : r.bs);
+        e.frame = i; e.ck = 0; e.got = 0; e.pad = 0;
+        table[r.tbl_at + b] = e;
+        pos += (uint64_t)(w & 0x7FFFFFFFu) + 4 * bck;
+    }
+}
+
+// the grid is sized by the host's bound on the table, capped at BF_BLOCKS_GRID workgroups: the waves stride over the entries in
+// use (ctl[0]), so a small batch into a big destination buffer does not launch a workgroup per 64 KiB of it
+constexpr uint32_t BF_BLOCKS_GRID = 8192;
+template <int W>
+__global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
+                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
+{
+    __shared__ uint32_t expand[W][64];
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = uni(blockIdx.x * W + wv); w < total; w += gridDim.x * W) {
+        const BatchBlk e = table[w];
+        const uint32_t fi = uni(e.frame);
+        if (fi >= n_frames) continue;
+        const uint32_t at = uni(frames[fi].tbl_at), nb = uni(frames[fi].n_blocks);
+        if (at == BF_NONE || w < at || w - at >= nb) continue;     // (an entry of this call: its frame's slice holds it)
+        const uint64_t span_end = uni64(frames[fi].src + frames[fi].span);
+        const uint32_t flg = uni(frames[fi].flags);
+        const uint64_t so = uni64(e.src), dof = uni64(e.dst);
+        const uint32_t word = uni(e.word), room = uni(e.room), csz = word & 0x7FFFFFFFu;
+        uint32_t ck = 0;
+        if ((flg >> 4) & 1) {
+            const uint32_t h = wave_xxh32(src + so, csz);
+            ck = h != bf_rd32(src + so + csz) ? 1u : 0u;
+        }
+        int32_t got;
+        if (word >> 31) {
+            if (csz > room) got = -2;
+            else { wave_copy_disjoint(dst + dof, src + so, csz); got = (int32_t)csz; }
+        } else {
+            got = wave_decode_block_win<true>(src + so, csz, span_end - so, dst + dof, room, expand[wv]);
+        }
+        if (lane_id() == 0) { table[w].got = got; table[w].ck = ck; }
+    }
+}
+
+// a wave per frame without a table slice: blocks in order
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
+{
+    const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
+    if (i >= n_frames) return;
+    const uint32_t status = uni(frames[i].status), n = uni(frames[i].n_blocks), tbl_at = uni(frames[i].tbl_at);
+    if (status != 0 || n == 0 || tbl_at != BF_NONE) return;
+    const uint64_t s0 = uni64(frames[i].src), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
+    const uint32_t flg = uni(frames[i].flags), bs = uni(frames[i].bs), bck = (flg >> 4) & 1;
+    const bool linked = !((flg >> 5) & 1);
+    const uint8_t* f = src + s0;
+    uint8_t* o = dst + d0;
+    uint64_t pos = uni(frames[i].hsize), out = 0;
+    uint32_t st = 0, bad = BF_NONE;
+    for (uint32_t b = 0; b < n; b++) {
+        const uint32_t word = uni(bf_rd32(f + pos));
+        pos += 4;
+        const uint32_t csz = word & 0x7FFFFFFFu;
+        const uint8_t* in = f + pos;
+        pos += (uint64_t)csz + 4 * bck;
+        if (bck && wave_xxh32(in, csz) != bf_rd32(in + csz)) { st = 7; bad = b; break; }       // (the first failure of either kind decides)
+        const uint64_t at = linked ? out : (uint64_t)b * bs;                                 // (independent: the provisional place, < win by the walk)
+        const uint32_t room = (uint32_t)(win - at < bs ? win - at : bs);
+        int32_t got;
+        if (word >> 31) {
+            if (csz > room) got = -2;
+            else { wave_copy_disjoint(o + at, in, csz); got = (int32_t)csz; }
+        } else {
+            got = bf_decode_block(in, csz, o + at, room, room, linked ? at : 0);
+            if (got < 0 && b + 1 == n && csz && win % bs != 0 && win - at < bs)
+                got = bf_redo_tight(in, csz, o + at, bs, room, linked ? at : 0);
+        }
+        if (got < 0) { st = bf_block_status(got, at, win, bs); bad = b; break; }
+        if (at != out) bf_move_down(o + out, o + at, (uint32_t)got);
+        out += (uint32_t)got;
+    }
+    if (lane_id() == 0) {
+        if (st) { frames[i].status = st; frames[i].first_bad = bad; }
+        else {
+            const uint64_t declared = frames[i].size;
+            frames[i].size = out;
+            if (((flg >> 3) & 1) && declared != out) frames[i].status = 14;               // frameSize_wrong
+        }
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                                      const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
+    const uint32_t wv = uni(threadIdx.x >> 6);
+    const uint32_t i = uni(blockIdx.x * W + wv);
+    if (i >= n_frames) return;
+    const uint32_t lane = lane_id();
+    const BatchFrame r = frames[i];
+    uint32_t status = uni(r.status), first_bad = uni(r.first_bad);
+    uint64_t size = uni64(r.size);
+    const uint32_t n = uni(r.n_blocks), flg = uni(r.flags), bs = uni(r.bs), tbl_at = uni(r.tbl_at);
+    const uint64_t win = uni64(r.win);
+    uint8_t* o = dst + uni64(r.dst);
+    if (status == 0 && n == 0) {                                   // no blocks: an empty frame, or a skippable one
+        if (((flg >> 3) & 1) && size != 0) status = 14;
+        size = 0;
+    } else if (status == 0 && tbl_at != BF_NONE) {                 // the placed frames: k_finish_decode's verdict on the table slice
+        const BatchBlk* t = table + tbl_at;
+        // the tight last block first, as k_redo_tight_block runs before the verdict
+        int32_t last = t[n - 1].got;
+        const uint64_t last_at = (uint64_t)(n - 1) * bs;
+        const uint32_t lw = uni(t[n - 1].word), lcsz = lw & 0x7FFFFFFFu;
+        if (uni((uint32_t)last) >> 31 && !(lw >> 31) && lcsz && win % bs != 0 && win - last_at < bs)
+            last = bf_redo_tight(src + uni64(t[n - 1].src), lcsz, o + last_at, bs, uni(t[n - 1].room), 0);
+        last = (int32_t)uni((uint32_t)last);
+        uint32_t bad = BF_NONE, ck = BF_NONE; int32_t kind = 0; bool moves = false; uint64_t sum = 0;
+        for (uint32_t b0 = 0; b0 < n; b0 += WAVE) {
+            const uint32_t b = b0 + lane;
+            const bool in = b < n;
+            const int32_t g = !in ? 0 : b + 1 == n ? last : t[b].got;
+            const uint64_t fm = __ballot(in && g < 0), cm = __ballot(in && t[b].ck);
+            if (fm && bad == BF_NONE) { bad = b0 + (uint32_t)__builtin_ctzll(fm); kind = (int32_t)__shfl((uint32_t)g, (int)(bad - b0)); }
+            if (cm && ck == BF_NONE) ck = b0 + (uint32_t)__builtin_ctzll(cm);
+            if (__ballot(in && b + 1 < n && g != (int32_t)bs)) moves = true;
+            uint64_t s = in && g > 0 ? (uint64_t)g : 0u;
+#pragma unroll
+            for (int sft = 1; sft < 64; sft <<= 1) s += __shfl_xor(s, sft);
+            sum += s;
+        }
+        if (ck != BF_NONE && ck <= bad) { status = 7; first_bad = ck; }
+        else if (bad != BF_NONE) { status = bf_block_status(kind, (uint64_t)bad * bs, win, bs); first_bad = bad; }
+        else {
+            if (moves) {                                           // a non-final block decoded short: pack the blocks (rare)
+                uint64_t out = 0;
+                for (uint32_t b = 0; b < n; b++) {
+                    const uint32_t g = uni(b + 1 == n ? (uint32_t)last : (uint32_t)t[b].got);
+                    const uint64_t at = (uint64_t)b * bs;
+                    if (at != out) bf_move_down(o + out, o + at, g);
+                    out += g;
+                }
+            }
+            if (((flg >> 3) & 1) && size != sum) status = 14;
+            size = sum;
+        }
+    }
+    // the content checksum, behind the frame's EndMark (k_xxh32_content)
+    const uint64_t consumed = uni64(r.consumed);
+    if (status == 0 && ((flg >> 2) & 1) && !(flg & 0x100) && content_check) {
+        const uint32_t h = lane4_xxh32(o, size, park[wv]);
+        if (h != bf_rd32(src + r.src + consumed - 4)) status = 18;              // contentChecksum_invalid
+    }
+    if (lane == 0) {
+        ResultRec x;
+        x.size = size; x.consumed = consumed; x.status = status; x.n_blocks = n; x.first_bad_block = first_bad;
+        x.flags = (flg & 0xFFFu) | (LZ4F_MI355X_PATH_BATCH << 12);
+        results[i] = x;
+    }
+}
+
+}  // namespace lz4f

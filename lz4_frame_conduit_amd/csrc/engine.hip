@@ -13,12 +13,14 @@
 
 #include "engine.hpp"
 #include "frame_dev.cuh"
+#include "decode_batch.cuh"
 
 using namespace lz4f;
 
 static_assert(sizeof(BlockOut) == sizeof(lz4f_mi355x_block), "block table layout");
 static_assert(sizeof(ResultRec) == sizeof(lz4f_mi355x_result), "result layout");
 static_assert(sizeof(ChunkInfo) == 32, "chunk info layout");
+static_assert(sizeof(BatchFrame) == 80 && sizeof(BatchBlk) == 40, "batch workspace layout");
 
 namespace lz4f {
 
@@ -172,7 +174,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -1429,6 +1431,39 @@ size_t lz4f_mi355x_dev_decompressBlocks(lz4f_mi355x_engine* e, void* d_dst, size
                                         lz4f_mi355x_result* d_result)
 {
     return lz4f_mi355x_dev_decompressBlocksIndexed(e, d_dst, dstCapacity, d_frame, frameCapacity, d_table, n_blocks, info, nullptr, 0, d_result);
+}
+
+size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                        void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (!d_src || !d_src_off || !d_dst || !d_dst_off || !d_results) { set_last_error("dev_decompressFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    hipStream_t st = (hipStream_t)e->stream;
+    if (e->aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)e->ev_join, 0)); e->aux_pending = false; }      // (an earlier call's forked work first)
+    // the block table: a frame of full blocks never needs more than window / 64 KiB + 1 entries, so this bound needs nothing read back
+    uint64_t table_cap = (uint64_t)n_frames + dstBytes / BF_SHARE + 1;
+    if (table_cap > 0xFFFFFFF0ull) table_cap = 0xFFFFFFF0ull;
+    const size_t counts_at = (size_t)n_frames * sizeof(BatchFrame), ctl_at = (counts_at + (size_t)n_frames * 4 + 255) & ~(size_t)255;
+    if (e->bframes.ensure(ctl_at + 256) || e->btable.ensure((size_t)table_cap * sizeof(BatchBlk))) return make_err(LZ4F_ERROR_allocation_failed);
+    BatchFrame* frames = (BatchFrame*)e->bframes.p;
+    uint32_t* counts = (uint32_t*)((uint8_t*)e->bframes.p + counts_at);
+    uint32_t* ctl = (uint32_t*)((uint8_t*)e->bframes.p + ctl_at);
+    BatchBlk* table = (BatchBlk*)e->btable.p;
+    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
+    constexpr int W = 4;
+    const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
+    hipLaunchKernelGGL(k_bf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts);
+    hipLaunchKernelGGL(k_bf_place, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
+    hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
+    hipLaunchKernelGGL((k_bf_blocks<W>), dim3((uint32_t)std::min<uint64_t>((table_cap + W - 1) / W, BF_BLOCKS_GRID)), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table,
+                       (const uint32_t*)ctl);
+    hipLaunchKernelGGL((k_bf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames);
+    hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
+                       e->sw.no_content_check ? 0u : 1u);
+    if (hipGetLastError() != hipSuccess) { set_last_error("dev_decompressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    return 0;
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

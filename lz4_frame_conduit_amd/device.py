@@ -24,6 +24,30 @@ def _chk(L, r):
     return r
 
 
+def _check_batch_args(src, src_off, dst, dst_off, results, rec_bytes: int) -> int:
+    """The tensors of a batch call (Engine.decompress_frames_async) -> the number of frames; ValueError for what is wrong with them."""
+    for name, t, dt in (("src", src, torch.uint8), ("dst", dst, torch.uint8), ("src_off", src_off, torch.int64), ("dst_off", dst_off, torch.int64),
+                        ("results", results, torch.uint8)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, not %s" % (name, dt, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous 1-d tensor" % name)
+    if src_off.numel() < 1 or src_off.numel() != dst_off.numel():
+        raise ValueError("src_off and dst_off must both hold n+1 offsets (got %d and %d)" % (src_off.numel(), dst_off.numel()))
+    n = src_off.numel() - 1
+    if n >= 1 << 32:
+        raise ValueError("too many frames for one call")
+    if results.numel() < n * rec_bytes:
+        raise ValueError("results must hold %d bytes for %d frames (got %d)" % (n * rec_bytes, n, results.numel()))
+    if not all(t.is_cuda for t in (src, dst, src_off, dst_off, results)):
+        raise ValueError("the tensors of a batch must be in device memory")
+    if len({src.device, dst.device, src_off.device, dst_off.device, results.device}) != 1:
+        raise ValueError("the tensors of a batch must be on one device")
+    return n
+
+
 class Engine:
     def __init__(self, device: int = 0, stream: "torch.cuda.Stream | None" = None):
         self.L = _ffi.lib()
@@ -109,6 +133,27 @@ class Engine:
 
     def decompress_frame_async(self, frame: torch.Tensor, frame_len: int, dst: torch.Tensor):
         _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrame(self.h, dst.data_ptr(), dst.numel(), frame.data_ptr(), frame_len, self._res.data_ptr()))
+
+    RESULT_BYTES = ctypes.sizeof(Result)
+
+    def new_results(self, n: int) -> torch.Tensor:
+        """Room for the result records of a batch of n frames (decompress_frames_async)."""
+        return torch.zeros(n * self.RESULT_BYTES, dtype=torch.uint8, device="cuda:%d" % self.device)
+
+    def decompress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, results: torch.Tensor):
+        """Enqueue a batch: frame i is the first frame in src[src_off[i]:src_off[i+1]], its output goes to dst[dst_off[i]:dst_off[i+1]].
+        src, dst: uint8 device tensors; src_off, dst_off: int64 device tensors of n+1 offsets; results: uint8 device tensor of
+        32*n bytes (new_results).  Each frame's verdict lands in its record (frame_results) - a bad frame fails alone, the call
+        raises only for what is wrong with the call itself.  Nothing is read back: no synchronisation."""
+        n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
+                                                            dst_off.data_ptr(), results.data_ptr()))
+
+    def frame_results(self, results: torch.Tensor) -> "list[Result]":
+        """Wait for the stream, then the records of a batch (status 0 = ok; otherwise the LZ4F error code of that frame)."""
+        self.stream.synchronize()
+        raw = results.cpu().numpy().tobytes()
+        return [Result.from_buffer_copy(raw, k) for k in range(0, len(raw) - self.RESULT_BYTES + 1, self.RESULT_BYTES)]
 
     def result(self) -> Result:
         r = self._result()                                   # (waits for the stream: everything enqueued so far, then the record's copy)
