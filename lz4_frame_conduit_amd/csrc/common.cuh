@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "records.hpp"      // status codes, BlockOut, ResultRec, the trailer's footer: what the host reads and writes too
+
 #define WAVE 64
 
 namespace lz4f {
@@ -27,19 +29,6 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v)
     uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return ((uint64_t)hi << 32) | lo;
 }
-
-// status codes written by kernels (values of LZ4F_errorCodes that can arise on the device)
-enum : uint32_t { ST_OK = 0, ST_GENERIC = 1, ST_MAXBLOCK = 2, ST_BLOCKCK = 7, ST_DSTSMALL = 11, ST_DECOMP = 16 };
-
-// ---- records shared with the host (include/lz4f_mi355x.h) ----
-struct BlockOut {            // mirrors lz4f_mi355x_block
-    uint64_t src_off, dst_off;
-    uint32_t word, dst_size;
-};
-struct ResultRec {           // mirrors lz4f_mi355x_result
-    uint64_t size, consumed;
-    uint32_t status, n_blocks, first_bad_block, flags;
-};
 
 // sequence descriptor the decoders hand from their parse to their copies: x = lit_src | off[7:0] << 24, y = lit_len | off[15:8] << 24,
 // z = dst, w = match_len (0: last sequence).  Positions and lengths are < 2^23 because a block holds at most 4 MiB.

@@ -1,4 +1,5 @@
-// engine.hip -- kernels (via the .cuh headers) + their launch plumbing + the device-pointer C ABI.
+// engine.hip -- kernels (via the .cuh headers), the engine's lifecycle, the two launch drivers and the device-pointer C ABI
+// (the host-pointer layer around the drivers: engine_host.hip).
 // Target: gfx950 only (MI355X).  No CPU fallback: without a usable device every entry fails loudly.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -8,7 +9,6 @@
 
 #include <algorithm>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "engine.hpp"
@@ -17,8 +17,6 @@
 
 using namespace lz4f;
 
-static_assert(sizeof(BlockOut) == sizeof(lz4f_mi355x_block), "block table layout");
-static_assert(sizeof(ResultRec) == sizeof(lz4f_mi355x_result), "result layout");
 static_assert(sizeof(ChunkInfo) == 32, "chunk info layout");
 static_assert(sizeof(BatchFrame) == 80 && sizeof(BatchBlk) == 40, "batch workspace layout");
 
@@ -33,36 +31,21 @@ void set_last_error(const char* fmt, ...)
 }
 const char* last_error() { return t_err; }
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            set_last_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);  \
-            return make_err(LZ4F_ERROR_GENERIC);                                                        \
-        }                                                                                               \
-    } while (0)
-
-int DevBuf::ensure(size_t n)
+// grow-only: room for n bytes and an eighth more, what was there is freed first (its contents are not kept)
+static int grow(void** p, size_t* cap, size_t n, bool pinned)
 {
-    if (n <= cap) return 0;
-    size_t want = n + n / 8 + 4096;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) { set_last_error("hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); p = nullptr; return 1; }
-    cap = want;
+    if (n <= *cap) return 0;
+    const size_t want = n + n / 8 + 4096;
+    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+    *p = nullptr; *cap = 0;
+    const hipError_t e = pinned ? hipHostMalloc(p, want, hipHostMallocDefault) : hipMalloc(p, want);
+    if (e != hipSuccess) { set_last_error("%s(%zu) failed: %s", pinned ? "hipHostMalloc" : "hipMalloc", want, hipGetErrorString(e)); *p = nullptr; return 1; }
+    *cap = want;
     return 0;
 }
+int DevBuf::ensure(size_t n) { return grow(&p, &cap, n, false); }
+int PinBuf::ensure(size_t n) { return grow(&p, &cap, n, true); }
 void DevBuf::release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-int PinBuf::ensure(size_t n)
-{
-    if (n <= cap) return 0;
-    size_t want = n + n / 8 + 4096;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e != hipSuccess) { set_last_error("hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e)); p = nullptr; return 1; }
-    cap = want;
-    return 0;
-}
 void PinBuf::release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 
 int selected_device()
@@ -84,22 +67,38 @@ uint32_t pick_chunk_size(uint32_t block_size)
 void lz4f_mi355x_engine::Switches::read()
 {
     auto on = [](const char* n) { return getenv(n) != nullptr; };
-    no_index = on("LZ4F_MI355X_NO_INDEX"); no_selfindex = on("LZ4F_MI355X_NO_SELFINDEX"); no_resolve = on("LZ4F_MI355X_NO_RESOLVE");
-    no_trace = on("LZ4F_MI355X_NO_TRACE"); no_doubling = on("LZ4F_MI355X_NO_DOUBLING"); trace_always = on("LZ4F_MI355X_TRACE_ALWAYS");
-    no_groups = on("LZ4F_MI355X_NO_GROUPS"); no_window = on("LZ4F_MI355X_NO_WINDOW"); serial_walk = on("LZ4F_MI355X_SERIAL_WALK");
-    no_trailer = on("LZ4F_MI355X_NO_TRAILER"); no_density_probe = on("LZ4F_MI355X_NO_DENSITY_PROBE"); no_spx = on("LZ4F_MI355X_NO_SPX"); no_overlap = on("LZ4F_MI355X_NO_OVERLAP"); no_content_check = on("LZ4F_MI355X_NO_CONTENT_CHECK"); prof = on("LZ4F_MI355X_PROF"); e1_sync = on("LZ4F_MI355X_E1_SYNC"); no_selffeed = on("LZ4F_MI355X_NO_SELFFEED"); dense_mode = 0; if (const char* v = getenv("LZ4F_MI355X_DENSE_MODE")) { const int g = atoi(v); if (g >= 0 && g <= 2) dense_mode = (unsigned)g; }
-    group_kib = 0; if (const char* v = getenv("LZ4F_MI355X_GROUP_KIB")) { const int k = atoi(v); if (k >= 64 && k <= 4096 && (k & (k - 1)) == 0) group_kib = (unsigned)k; }
-    feed_round = 0; if (const char* v = getenv("LZ4F_MI355X_FEED_ROUND")) { const int k = atoi(v); if (k >= 17 && k <= 4096) feed_round = (unsigned)k; }
-    chain_gate = 0; if (const char* v = getenv("LZ4F_MI355X_CHAIN_GATE")) { const int g = atoi(v); if (g > 0 && g < (1 << 20)) chain_gate = g; }
+    auto num = [](const char* n, int lo, int hi, int dflt) { const char* v = getenv(n); if (!v) return dflt; const int k = atoi(v); return k >= lo && k <= hi ? k : dflt; };      // an integer in [lo, hi], else the default
+    no_index = on("LZ4F_MI355X_NO_INDEX");
+    no_selfindex = on("LZ4F_MI355X_NO_SELFINDEX");
+    no_resolve = on("LZ4F_MI355X_NO_RESOLVE");
+    no_trace = on("LZ4F_MI355X_NO_TRACE");
+    no_doubling = on("LZ4F_MI355X_NO_DOUBLING");
+    trace_always = on("LZ4F_MI355X_TRACE_ALWAYS");
+    no_groups = on("LZ4F_MI355X_NO_GROUPS");
+    no_window = on("LZ4F_MI355X_NO_WINDOW");
+    serial_walk = on("LZ4F_MI355X_SERIAL_WALK");
+    no_trailer = on("LZ4F_MI355X_NO_TRAILER");
+    no_density_probe = on("LZ4F_MI355X_NO_DENSITY_PROBE");
+    no_spx = on("LZ4F_MI355X_NO_SPX");
+    no_overlap = on("LZ4F_MI355X_NO_OVERLAP");
+    no_content_check = on("LZ4F_MI355X_NO_CONTENT_CHECK");
+    prof = on("LZ4F_MI355X_PROF");
+    e1_sync = on("LZ4F_MI355X_E1_SYNC");
+    no_selffeed = on("LZ4F_MI355X_NO_SELFFEED");
+    dense_mode = (unsigned)num("LZ4F_MI355X_DENSE_MODE", 0, 2, 0);
+    group_kib = (unsigned)num("LZ4F_MI355X_GROUP_KIB", 64, 4096, 0);
+    if (group_kib & (group_kib - 1)) group_kib = 0;                  // (a power of two)
+    feed_round = (unsigned)num("LZ4F_MI355X_FEED_ROUND", 17, 4096, 0);
+    chain_gate = num("LZ4F_MI355X_CHAIN_GATE", 1, (1 << 20) - 1, 0);
     decode_mode = 0; if (const char* v = getenv("LZ4F_MI355X_DECODE")) decode_mode = v[0];
-    e1_run = 0; if (const char* v = getenv("LZ4F_MI355X_E1_RUN")) { const int g = atoi(v); if (g >= 1 && g <= 4096) e1_run = (unsigned)g; }
+    e1_run = (unsigned)num("LZ4F_MI355X_E1_RUN", 1, 4096, 0);
     e1_solo = 0; if (const char* v = getenv("LZ4F_MI355X_E1_SOLO")) e1_solo = (unsigned)atoi(v);
     if (on("LZ4F_MI355X_DETERMINISTIC")) e1_solo |= 1u;              // equal input -> equal bytes: one wave per workgroup parses, in order (see lz4f_mi355x_engine_set_deterministic)
     wait_ticks = 0; if (const char* v = getenv("LZ4F_MI355X_WAIT_TICKS")) { unsigned long long a = 0; if (sscanf(v, "%llu", &a) == 1) wait_ticks = a; }
-    dblk_lds = 0; if (const char* v = getenv("LZ4F_MI355X_DBLK_LDS")) { const int k = atoi(v); if (k > 0 && k <= 150) dblk_lds = (unsigned)k << 10; }      // (development: fewer wave-per-block decoders per CU)
-    recs_per_tile = 0; if (const char* v = getenv("LZ4F_MI355X_RECS_PER_TILE")) { const int k = atoi(v); if (k >= 1 && k <= 16385) recs_per_tile = (unsigned)k; }
-    hc_attempts = 0; if (const char* v = getenv("LZ4F_MI355X_HC_ATTEMPTS")) { const int k = atoi(v); if (k >= 1 && k <= 65536) hc_attempts = (unsigned)k; }      // (development: levels 3-12 search this many candidates per position)
-    hc_lazy = 0; if (const char* v = getenv("LZ4F_MI355X_HC_LAZY")) { const int k = atoi(v); if (k >= 1 && k <= 2) hc_lazy = (unsigned)k; }
+    dblk_lds = (unsigned)num("LZ4F_MI355X_DBLK_LDS", 1, 150, 0) << 10;      // (development: fewer wave-per-block decoders per CU)
+    recs_per_tile = (unsigned)num("LZ4F_MI355X_RECS_PER_TILE", 1, 16385, 0);
+    hc_attempts = (unsigned)num("LZ4F_MI355X_HC_ATTEMPTS", 1, 65536, 0);      // (development: levels 3-12 search this many candidates per position)
+    hc_lazy = (unsigned)num("LZ4F_MI355X_HC_LAZY", 1, 2, 0);
     seed = 2; if (const char* v = getenv("LZ4F_MI355X_SEED")) { unsigned a = 0; if (sscanf(v, "%u", &a) == 1 && a >= 1 && a <= 64) seed = a; }
 }
 namespace lz4f {
@@ -231,10 +230,6 @@ extern "C" __attribute__((visibility("default"))) int lz4f_mi355x_debug_prof(uns
     return rc;
 }
 
-// The record pool of one compress call, in records: `per_tile` a 64 KiB tile on average (0 = the default, 12288: a sequence per 5.3 input
-// bytes - the densest input of the tests, Zipf text, needs more than 8192 per tile; the bench input one per 2000), never less than 64 tiles' worst case
-// (small calls are sized for the worst case outright) and never more than the worst case.  LZ4F_MI355X_RECS_PER_TILE=16385 is the worst
-// case for every tile; a caller that knows its data is sparse sets it low (1024: 0.13 bytes of workspace per input byte).
 static uint32_t device_cus(int device)
 {
     static int cus[64];                                                  // (0: not asked yet; a benign race: every thread stores the same number)
@@ -243,6 +238,27 @@ static uint32_t device_cus(int device)
     return (uint32_t)cus[d];
 }
 
+// ------------------------------------------------------------------------------------------------
+// encode: a plan made from the call alone, then one function per stage (launch_compress, behind them, runs them in order)
+
+// How `payload` bytes fall into blocks, and a block into the chunks of passes E1, S and E2.  The public sizing calls (a caller sizes
+// its buffers by them) and the engine (it fills them) both go by these.
+struct EncShape { uint32_t chunk, chunks_per_block; uint64_t n_blocks; };
+static EncShape enc_shape(uint64_t payload, uint32_t block_size)
+{
+    const uint32_t chunk = pick_chunk_size(block_size);
+    return EncShape{chunk, block_size / chunk, (payload + block_size - 1) / block_size};
+}
+// the sequence index: its fixed part and room for one sequence per 64 bytes of input on average (ix_typical_entries)
+static size_t index_capacity(uint64_t payload, const EncShape& s)
+{
+    return ix_entries_at((uint32_t)s.n_blocks, s.chunks_per_block) + ix_typical_entries(payload, (uint32_t)(s.n_blocks * s.chunks_per_block)) * sizeof(IxEntry);
+}
+
+// The record pool of one compress call, in records: `per_tile` a 64 KiB tile on average (0 = the default, 12288: a sequence per 5.3 input
+// bytes - the densest input of the tests, Zipf text, needs more than 8192 per tile; the bench input one per 2000), never less than 64 tiles' worst case
+// (small calls are sized for the worst case outright) and never more than the worst case.  LZ4F_MI355X_RECS_PER_TILE=16385 is the worst
+// case for every tile; a caller that knows its data is sparse sets it low (1024: 0.13 bytes of workspace per input byte).
 static uint64_t rec_pool_records(uint32_t n_chunks, uint32_t max_rec_per_chunk, unsigned per_tile)
 {
     const uint64_t worst = (uint64_t)(n_chunks + 1) * max_rec_per_chunk;
@@ -253,145 +269,208 @@ static uint64_t rec_pool_records(uint32_t n_chunks, uint32_t max_rec_per_chunk, 
     return want;
 }
 
-size_t lz4f_mi355x_engine::launch_compress(const CompressJob& j, uint8_t* d_dst, uint64_t dst_cap,
-                                           lz4f_mi355x_result* d_res, lz4f_mi355x_block* d_table, void* d_index, size_t index_cap)
-{    // in-band: the index is made in the engine's own buffer and copied, with the block list, into a skippable frame behind the
-    // LZ4 frame (frame_dev.cuh: the trailer)
-    const bool inband = d_index == nullptr && index_cap == LZ4F_MI355X_INBAND;
-    HIP_TRY(hipSetDevice(device));                     // (before anything is allocated: the caller's current device may be another one)
-    if (inband) {
-        const size_t bsz = j.block_size, nb_ = (size_t)((j.src_size - j.first_off + bsz - 1) / bsz);
-        const uint32_t ch_ = pick_chunk_size(j.block_size);
-        index_cap = ix_entries_at((uint32_t)nb_, j.block_size / ch_) + ix_typical_entries(j.src_size - j.first_off, (uint32_t)(nb_ * (j.block_size / ch_))) * sizeof(IxEntry) + 64;
-        if (ixtmp.ensure(index_cap + 64) || res.ensure(sizeof(ResultRec) + sizeof(TrailerPlan) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-        d_index = ixtmp.p;
-        if (((uintptr_t)d_dst & 15) != 0) { set_last_error("in-band index: the frame buffer must be 16-byte aligned"); return make_err(LZ4F_ERROR_GENERIC); }
-    }
+struct lz4f_mi355x_engine::EncodePlan {
+    bool too_large;                  // more chunks than a 32-bit count holds: the call is refused, nothing else here is filled in
+    EncGeom g;                       // what every kernel of the call takes
+    enum Finder { E1_SHARED, E1_SOLO, HASH_CHAIN } finder;      // pass E1 (encode.cuh), its deterministic form (encode_solo.cuh), levels 3-12 (encode_hc.cuh)
+    uint32_t e1_wgs;                 // the shared pass E1's workgroups, each with a run of g.tiles_per_wg tiles
+    bool layout_small, e2_split;     // a few blocks: one layout launch instead of three; few chunks: the four waves of an emit workgroup share a chunk
+    bool xxh_lane4;                  // few big blocks: a block checksum's four accumulators as four lanes
+    bool inband;                     // the index is made in the engine's own buffer and copied into a trailer behind the frame
+    size_t index_cap;                // bytes of the sequence index: the caller's, or (in-band) of the engine's own buffer
+    size_t info_bytes, recs_bytes, blk_bytes, table_bytes, res_bytes, e1_scratch_bytes, ixtmp_bytes;      // the workspaces (table: when the caller brings none; ixtmp: in-band)
+};
 
-    hipStream_t st = (hipStream_t)stream;
-    EncGeom g;
-    memset(&g, 0, sizeof(g));
-    g.src_size = j.src_size; g.first_off = j.first_off; g.write_endmark = j.endmark ? (j.content_checksum ? 2 : 1) : 0;
-    g.block_size = j.block_size;
-    g.chunk_size = pick_chunk_size(j.block_size);
-    g.chunks_per_block = j.block_size / g.chunk_size;
+lz4f_mi355x_engine::EncodePlan lz4f_mi355x_engine::encode_plan(const CompressJob& j, const Switches& sw, uint32_t cus, bool inband, size_t index_cap)
+{
+    EncodePlan p; memset(&p, 0, sizeof(p));
+    EncGeom& g = p.g;
     const uint64_t payload = j.src_size - j.first_off;
-    const uint64_t nb = (payload + j.block_size - 1) / j.block_size;
-    if (nb > 0x7FFFFFFFull / g.chunks_per_block) { set_last_error("input too large for one call"); return make_err(LZ4F_ERROR_srcSize_tooLarge); }
-    g.n_blocks = (uint32_t)nb; g.n_chunks = g.n_blocks * g.chunks_per_block;
+    const EncShape s = enc_shape(payload, j.block_size);
+    if (s.n_blocks > 0x7FFFFFFFull / s.chunks_per_block) { p.too_large = true; return p; }
+    g.src_size = j.src_size; g.first_off = j.first_off; g.write_endmark = j.endmark ? (j.content_checksum ? 2 : 1) : 0;
+    g.block_size = j.block_size; g.chunk_size = s.chunk; g.chunks_per_block = s.chunks_per_block;
+    g.n_blocks = (uint32_t)s.n_blocks; g.n_chunks = g.n_blocks * g.chunks_per_block;
     g.linked = j.linked; g.block_checksum = j.block_checksum;
     g.header_size = j.header_size; memcpy(g.header, j.header, j.header_size);
     g.max_rec_per_chunk = g.chunk_size / 4 + 1;
     g.seed_stride = sw.seed;
+    // deterministic mode: a wave per chunk with a table of its own (encode_solo.cuh) - nothing shared, nothing that depends on timing.
+    // (e1_solo bit 2: the shared kernel with one wave per workgroup parsing, the mode's form until round 4 - kept for comparison)
+    // levels 3-12: the hash-chain finder, a workgroup per chunk (encode_hc.cuh) - deterministic too.
     const bool hc = j.level >= 3;
+    p.finder = hc ? EncodePlan::HASH_CHAIN : ((sw.e1_solo & 1u) && !(sw.e1_solo & 4u)) ? EncodePlan::E1_SOLO : EncodePlan::E1_SHARED;
     if (hc) {
         const HcLevel hl = hc_level(j.level);
         g.hc_attempts = sw.hc_attempts ? sw.hc_attempts : hl.attempts;
         g.hc_lazy = sw.hc_lazy ? sw.hc_lazy : hl.lazy;
     }
-
-    if (info.ensure((size_t)(g.n_chunks + 1) * sizeof(ChunkInfo))) return make_err(LZ4F_ERROR_allocation_failed);
     // (deterministic mode: the worst case for every tile - which tiles a short pool turns away is a matter of which workgroup's merge
     // gets to the bump pointer first, and "equal input, equal bytes" must not hang on that: 2 bytes of workspace per input byte)
     // (levels 3-12 likewise: their output is a function of the input alone, so a chunk's list has a place of its own, encode_hc.cuh)
     g.rec_pool = rec_pool_records(g.n_chunks, g.max_rec_per_chunk, ((sw.e1_solo & 1u) || hc) ? 16385u : sw.recs_per_tile);
-    if (recs.ensure((size_t)(rec_pool_at(g.n_chunks) + g.rec_pool) * 8)) return make_err(LZ4F_ERROR_allocation_failed);
-    if (blk_bytes.ensure((size_t)(g.n_blocks + 1) * 4)) return make_err(LZ4F_ERROR_allocation_failed);
-    if (!d_table) { if (table.ensure((size_t)(g.n_blocks + 1) * sizeof(BlockOut))) return make_err(LZ4F_ERROR_allocation_failed); d_table = (lz4f_mi355x_block*)table.p; }
-    if (res.ensure(sizeof(ResultRec) + sizeof(TrailerPlan) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-    if (!d_res) d_res = (lz4f_mi355x_result*)res.p;
+    if (g.n_chunks) {
+        // a workgroup (one per CU: ~150 KiB of LDS) takes a run of consecutive 64 KiB tiles.  At most 1024 workgroups (each
+        // has its slice lists in `e1_scratch`).  Round 4: as many workgroups as there are CUs where the input has fewer than 64 tiles
+        // for each, runs of 64 tiles from there on - a run's first tile pays for the 64 KiB of history in front of it, for seeding the
+        // table with them and for not knowing the data's density yet, so fewer, longer runs win until the CUs run out of work:
+        // tools/e1_run_sweep.py, tiles per workgroup 1024-wide rule -> this one: 64 MiB 0.132 -> 0.065 ms (ratio 1.9154 -> 1.9425),
+        // 256 MiB 0.256 -> 0.187, 1 GiB 0.722 -> 0.647, 2 GiB 1.342 -> 1.228; 4 GiB and beyond as before (64 tiles, 1024 workgroups).
+        uint32_t run = g.n_chunks / cus; run = run < 1 ? 1 : run > 64 ? 64 : run;
+        if ((g.n_chunks + run - 1) / run > 1024) run = (g.n_chunks + 1023) / 1024;
+        if (sw.e1_run) run = sw.e1_run;
+        g.tiles_per_wg = run;
+        g.e1_solo = sw.e1_solo;
+        p.e1_wgs = (g.n_chunks + run - 1) / run;
+        p.e1_scratch_bytes = (size_t)p.e1_wgs * 2 * E1_NSLICE * E1_REC_PER_SLICE * 8 + 2048;      // (the last 2048: E1_DEBUG's counters)
+    }
+    p.layout_small = g.n_blocks <= LAYOUT_SMALL_BLOCKS && g.n_chunks <= LAYOUT_SMALL_CHUNKS; p.e2_split = g.n_chunks <= 512;      // (both: the streaming API's one block per call)
+    p.xxh_lane4 = g.n_blocks < XXH_LANE4_BELOW;
+    p.inband = inband;
+    p.index_cap = inband ? index_capacity(payload, s) + 64 : index_cap;
+    p.ixtmp_bytes = inband ? p.index_cap + 64 : 0;
+    p.info_bytes = (size_t)(g.n_chunks + 1) * sizeof(ChunkInfo); p.recs_bytes = (size_t)(rec_pool_at(g.n_chunks) + g.rec_pool) * 8;
+    p.blk_bytes = (size_t)(g.n_blocks + 1) * 4; p.table_bytes = (size_t)(g.n_blocks + 1) * sizeof(BlockOut);
+    p.res_bytes = sizeof(ResultRec) + sizeof(TrailerPlan) + 64;                                   // (the in-band trailer's plan rides behind the record)
+    return p;
+}
 
+#ifdef E1_DEBUG
+// developer aid (-DE1_DEBUG): pass E1's counters, behind the workgroups' slice lists in e1_scratch
+static void e1_debug_dump(hipStream_t st, const uint8_t* counters)
+{
+    unsigned long long d[256]; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(d, counters, 2048, hipMemcpyDeviceToHost) == hipSuccess) {
+                for (int w = 0; w < 16; w += 5) { unsigned long long* x = d + 16 + w * 8; if (x[6]) fprintf(stderr, "E1 wave %d: per tile cycles: merge %llu parse %llu waitB1 %llu dma-issue %llu dma-wait %llu waitB2 %llu (%llu tiles)\n", w, x[0]/x[6], x[1]/x[6], x[2]/x[6], x[3]/x[6], x[4]/x[6], x[5]/x[6], x[6]); unsigned long long* f = d + 160 + w * 6; fprintf(stderr, "   parse: dequeue %llu cycles x %llu, probe step %llu cycles x %llu, hit %llu cycles x %llu (per tile)\n", f[3] ? f[0]/f[3] : 0, f[3]/x[6], f[4] ? f[1]/f[4] : 0, f[4]/x[6], f[5] ? f[2]/f[5] : 0, f[5]/x[6]); }
+                fprintf(stderr, "E1 dense passes (workgroup 0): %llu, matches taken %llu, positions advanced %llu; one-match steps because: hit in B %llu, mode not dense %llu, step != 1 %llu, first match long %llu\n", d[13], d[14], d[15], d[4], d[5], d[6], d[7]);
+                fprintf(stderr, "E1 debug: bounds hit: dequeue %llu, probe %llu, backward %llu, forward %llu; probe ip/last %llx step/slice %llx; back room/nb %llx; fwd mp/fw %llx end_lim/d %llx\n", d[0], d[1], d[2], d[3], d[8], d[9], d[10], d[11], d[12]); }
+}
+#endif
+
+// Stage 1: the workspaces, each ensured once.  own_table: the caller brought no block table.
+size_t lz4f_mi355x_engine::enc_workspaces(const EncodePlan& p, bool own_table)
+{
+    if (ixtmp.ensure(p.ixtmp_bytes) || res.ensure(p.res_bytes) || info.ensure(p.info_bytes) || recs.ensure(p.recs_bytes) || blk_bytes.ensure(p.blk_bytes) ||
+        (own_table && table.ensure(p.table_bytes)) || e1_scratch.ensure(p.e1_scratch_bytes))
+        return make_err(LZ4F_ERROR_allocation_failed);
+    return 0;
+}
+
+// Stage 2: the match finder - every chunk's sequences as records in the pool
+size_t lz4f_mi355x_engine::enc_find(const CompressJob& j, const EncodePlan& p)
+{
+    hipStream_t st = (hipStream_t)stream; const EncGeom& g = p.g;
+#ifdef E1_DEBUG
+    uint8_t* const counters = (uint8_t*)e1_scratch.p + p.e1_scratch_bytes - 2048;
+    (void)hipMemsetAsync(counters, 0, 2048, st);
+#endif
+    // (the pool's bump pointer and its count of tiles turned away: every call's scan leaves them at zero for the next; zeroed here when the
+    // workspace is new, or when a call before this one may not have got as far as its scan)
+    if (recs_ctl_clean != recs.p) { HIP_TRY(hipMemsetAsync(recs.p, 0, 64, st)); }
+    recs_ctl_clean = nullptr;
+    if (p.finder == EncodePlan::HASH_CHAIN)
+        hipLaunchKernelGGL(k_find_matches_hc, dim3(g.n_chunks), dim3(64 * HC_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
+    else if (p.finder == EncodePlan::E1_SOLO)
+        hipLaunchKernelGGL((k_find_matches_solo<1>), dim3(g.n_chunks), dim3(64), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
+    else
+        hipLaunchKernelGGL(k_find_matches, dim3(p.e1_wgs), dim3(64 * E1_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p, (uint64_t*)e1_scratch.p);
+    if (sw.e1_sync) (void)hipStreamSynchronize(st);
+#ifdef E1_DEBUG
+    e1_debug_dump(st, counters);
+#endif
+    return 0;
+}
+
+// Stage 3: the layout - every block's and chunk's place in the frame, the header, the result record - and the sequence index
+void lz4f_mi355x_engine::enc_layout(const EncodePlan& p, uint8_t* d_dst, uint64_t dst_cap, ResultRec* rec, BlockOut* tbl, void* d_index)
+{
     constexpr int W = 4;
+    hipStream_t st = (hipStream_t)stream; const EncGeom& g = p.g;
+    if (p.layout_small)
+        hipLaunchKernelGGL(k_layout_small, dim3(1), dim3(1024), 0, st, g, (ChunkInfo*)info.p, tbl, (uint32_t*)blk_bytes.p, d_dst, dst_cap, rec, (const uint64_t*)recs.p);
+    else {
+        if (g.n_blocks) hipLaunchKernelGGL((k_layout_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, g, (ChunkInfo*)info.p, tbl, (uint32_t*)blk_bytes.p);
+        hipLaunchKernelGGL(k_layout_scan, dim3(1), dim3(1024), 0, st, g, tbl, (const uint32_t*)blk_bytes.p, d_dst, dst_cap, rec, (const uint64_t*)recs.p);
+        if (g.n_chunks) hipLaunchKernelGGL(k_layout_chunks, dim3((g.n_chunks + 255) / 256), dim3(256), 0, st, g, (ChunkInfo*)info.p, (const BlockOut*)tbl, d_dst, (const ResultRec*)rec);
+    }
+    if (g.n_chunks) recs_ctl_clean = recs.p;                                  // (the scan is enqueued: it leaves the pool's control words at zero)
+    if (d_index) {                                                            // sequence index for the indexed decoder
+        if (g.n_blocks) hipLaunchKernelGGL((k_index_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, g, (const ChunkInfo*)info.p, (const BlockOut*)tbl, (const ResultRec*)rec, d_index, (uint64_t)p.index_cap);
+        hipLaunchKernelGGL(k_build_index, dim3(1), dim3(1024), 0, st, g, (const ChunkInfo*)info.p, (const BlockOut*)tbl, (const ResultRec*)rec, d_index, (uint64_t)p.index_cap, 1u);
+    }
+}
+
+// Stage 4: the emit - the chunks' records and literals become the blocks' bytes - and the block checksums behind it
+void lz4f_mi355x_engine::enc_emit(const CompressJob& j, const EncodePlan& p, uint8_t* d_dst, const ResultRec* rec, BlockOut* tbl, void* d_index)
+{
+    constexpr int W = 4;
+    hipStream_t st = (hipStream_t)stream; const EncGeom& g = p.g;
+    tick(2, false);
+    if (p.e2_split)
+        hipLaunchKernelGGL((k_emit_gather<W, true>), dim3(g.n_chunks), dim3(64 * W), 0, st, j.d_src, g, (const ChunkInfo*)info.p,
+                           (const uint64_t*)recs.p, d_dst, (const BlockOut*)tbl, d_index);
+    else
+        hipLaunchKernelGGL((k_emit_gather<W, false>), dim3((g.n_chunks + W - 1) / W), dim3(64 * W), 0, st, j.d_src, g, (const ChunkInfo*)info.p,
+                           (const uint64_t*)recs.p, d_dst, (const BlockOut*)tbl, d_index);
+    tick(2, true);
+    if (!j.block_checksum) return;
+    tick(3, false);
+    if (p.xxh_lane4)                                                   // (lane4_xxh32)
+        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(g.n_blocks), dim3(64), XXH_SPREAD_LDS, st, d_dst, tbl, rec, g.n_blocks, 0u, (uint32_t*)nullptr);
+    else
+        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, d_dst, tbl, rec, g.n_blocks, 0u, (uint32_t*)nullptr);
+    tick(3, true);
+}
+
+// Stage 5: what ends a frame - the content checksum behind the EndMark, and the in-band trailer: block list and index behind the frame
+void lz4f_mi355x_engine::enc_tail(const CompressJob& j, const EncodePlan& p, uint8_t* d_dst, uint64_t dst_cap, ResultRec* rec, const BlockOut* tbl, const void* d_index)
+{
+    hipStream_t st = (hipStream_t)stream; const EncGeom& g = p.g;
+    if (j.endmark && j.content_checksum)                              // (one chain over the whole input: see k_xxh32_content for what that costs)
+        hipLaunchKernelGGL(k_xxh32_content, dim3(1), dim3(64), 0, st, j.d_src + j.first_off, (uint64_t)(j.src_size - j.first_off), d_dst, rec, 0u);
+    if (p.inband && g.n_blocks) {
+        TrailerPlan* plan = (TrailerPlan*)((uint8_t*)res.p + sizeof(ResultRec) + 32);
+        hipLaunchKernelGGL(k_trailer_plan, dim3(1), dim3(64), 0, st, d_dst, dst_cap, rec, g.n_blocks, d_index,
+                           (uint64_t)ix_entries_at(g.n_blocks, g.chunks_per_block), plan);
+        hipLaunchKernelGGL(k_trailer_copy, dim3(256), dim3(256), 0, st, d_dst, (const TrailerPlan*)plan, tbl, g.n_blocks, d_index);
+    }
+}
+
+lz4f_mi355x_engine::CompressJob lz4f_mi355x_engine::make_compress_job(const uint8_t* d_src, uint64_t src_size, uint64_t first_off, uint32_t block_size,
+                                                                      bool linked, bool block_checksum, int level, const LZ4F_preferences_t* frame)
+{
+    CompressJob j; memset(&j, 0, sizeof(j));
+    j.d_src = d_src; j.src_size = src_size; j.first_off = first_off; j.block_size = block_size;
+    j.linked = linked; j.block_checksum = block_checksum; j.level = level;
+    if (frame) { j.endmark = true; j.content_checksum = frame->frameInfo.contentChecksumFlag != 0; j.header_size = (uint32_t)write_frame_header(j.header, *frame); }
+    return j;
+}
+
+size_t lz4f_mi355x_engine::launch_compress(const CompressJob& j, uint8_t* d_dst, uint64_t dst_cap,
+                                           lz4f_mi355x_result* d_res, lz4f_mi355x_block* d_table, void* d_index, size_t index_cap)
+{   // in-band: the index is made in the engine's own buffer and copied, with the block list, into a skippable frame behind the
+    // LZ4 frame (frame_dev.cuh: the trailer)
+    const bool inband = d_index == nullptr && index_cap == LZ4F_MI355X_INBAND;
+    HIP_TRY(hipSetDevice(device));                     // (before anything is allocated: the caller's current device may be another one)
+    const EncodePlan p = encode_plan(j, sw, device_cus(device), inband, index_cap);
+    if (inband && ((uintptr_t)d_dst & 15) != 0) { set_last_error("in-band index: the frame buffer must be 16-byte aligned"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (p.too_large) { set_last_error("input too large for one call"); return make_err(LZ4F_ERROR_srcSize_tooLarge); }
+    if (size_t e = enc_workspaces(p, !d_table)) return e;
+    if (inband) d_index = ixtmp.p;
+    BlockOut* tbl = (BlockOut*)(d_table ? d_table : table.p);
+    ResultRec* r = (ResultRec*)(d_res ? d_res : res.p);
     for (int i = 0; i < 4; i++) ev_used[i] = false;
     ev_used[10] = false;
     tick(10, false);
-    if (g.n_chunks) {
+    if (p.g.n_chunks) {
         tick(0, false);
-        {
-            // a workgroup (one per CU: ~150 KiB of LDS) takes a run of consecutive 64 KiB tiles.  At most 1024 workgroups (each
-            // has its slice lists in `e1_scratch`).  Round 4: as many workgroups as there are CUs where the input has fewer than 64 tiles
-            // for each, runs of 64 tiles from there on - a run's first tile pays for the 64 KiB of history in front of it, for seeding the
-            // table with them and for not knowing the data's density yet, so fewer, longer runs win until the CUs run out of work:
-            // tools/e1_run_sweep.py, tiles per workgroup 1024-wide rule -> this one: 64 MiB 0.132 -> 0.065 ms (ratio 1.9154 -> 1.9425),
-            // 256 MiB 0.256 -> 0.187, 1 GiB 0.722 -> 0.647, 2 GiB 1.342 -> 1.228; 4 GiB and beyond as before (64 tiles, 1024 workgroups).
-            uint32_t run = g.n_chunks / device_cus(device); run = run < 1 ? 1 : run > 64 ? 64 : run;
-            if ((g.n_chunks + run - 1) / run > 1024) run = (g.n_chunks + 1023) / 1024;
-            if (sw.e1_run) run = sw.e1_run;
-            g.tiles_per_wg = run;
-            g.e1_solo = sw.e1_solo;
-            const uint32_t n_wg = (g.n_chunks + run - 1) / run;
-            if (e1_scratch.ensure((size_t)n_wg * 2 * E1_NSLICE * E1_REC_PER_SLICE * 8 + 2048)) return make_err(LZ4F_ERROR_allocation_failed);
-#ifdef E1_DEBUG
-            (void)hipMemsetAsync((uint8_t*)e1_scratch.p + (size_t)n_wg * 2 * E1_NSLICE * E1_REC_PER_SLICE * 8, 0, 2048, st);
-#endif
-            // (the pool's bump pointer and its count of tiles turned away: every call's scan leaves them at zero for the next; zeroed here when the
-            // workspace is new, or when a call before this one may not have got as far as its scan)
-            if (recs_ctl_clean != recs.p) { HIP_TRY(hipMemsetAsync(recs.p, 0, 64, st)); }
-            recs_ctl_clean = nullptr;
-            // deterministic mode: a wave per chunk with a table of its own (encode_solo.cuh) - nothing shared, nothing that depends on timing.
-            // (e1_solo bit 2: the shared kernel with one wave per workgroup parsing, the mode's form until round 4 - kept for comparison)
-            // levels 3-12: the hash-chain finder, a workgroup per chunk (encode_hc.cuh) - deterministic too.
-            if (hc)
-                hipLaunchKernelGGL(k_find_matches_hc, dim3(g.n_chunks), dim3(64 * HC_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
-            else if ((sw.e1_solo & 1u) && !(sw.e1_solo & 4u))
-                hipLaunchKernelGGL((k_find_matches_solo<1>), dim3(g.n_chunks), dim3(64), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p);
-            else
-            hipLaunchKernelGGL(k_find_matches, dim3(n_wg), dim3(64 * E1_WAVES), 0, st, j.d_src, g, (ChunkInfo*)info.p, (uint64_t*)recs.p, (uint64_t*)e1_scratch.p);
-            if (sw.e1_sync) (void)hipStreamSynchronize(st);
-#ifdef E1_DEBUG
-            { unsigned long long d[256]; if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(d, (uint8_t*)e1_scratch.p + (size_t)n_wg * 2 * E1_NSLICE * E1_REC_PER_SLICE * 8, 2048, hipMemcpyDeviceToHost) == hipSuccess) {
-                for (int w = 0; w < 16; w += 5) { unsigned long long* x = d + 16 + w * 8; if (x[6]) fprintf(stderr, "E1 wave %d: per tile cycles: merge %llu parse %llu waitB1 %llu dma-issue %llu dma-wait %llu waitB2 %llu (%llu tiles)\n", w, x[0]/x[6], x[1]/x[6], x[2]/x[6], x[3]/x[6], x[4]/x[6], x[5]/x[6], x[6]); unsigned long long* f = d + 160 + w * 6; fprintf(stderr, "   parse: dequeue %llu cycles x %llu, probe step %llu cycles x %llu, hit %llu cycles x %llu (per tile)\n", f[3] ? f[0]/f[3] : 0, f[3]/x[6], f[4] ? f[1]/f[4] : 0, f[4]/x[6], f[5] ? f[2]/f[5] : 0, f[5]/x[6]); }
-                fprintf(stderr, "E1 dense passes (workgroup 0): %llu, matches taken %llu, positions advanced %llu; one-match steps because: hit in B %llu, mode not dense %llu, step != 1 %llu, first match long %llu\n", d[13], d[14], d[15], d[4], d[5], d[6], d[7]);
-                fprintf(stderr, "E1 debug: bounds hit: dequeue %llu, probe %llu, backward %llu, forward %llu; probe ip/last %llx step/slice %llx; back room/nb %llx; fwd mp/fw %llx end_lim/d %llx\n", d[0], d[1], d[2], d[3], d[8], d[9], d[10], d[11], d[12]); } }
-#endif
-        }
+        if (size_t e = enc_find(j, p)) return e;
         tick(0, true);
     }
     tick(1, false);
-    {
-        if (g.n_blocks <= LAYOUT_SMALL_BLOCKS && g.n_chunks <= LAYOUT_SMALL_CHUNKS)       // (a few blocks - the streaming API's one per call: one launch instead of three)
-            hipLaunchKernelGGL(k_layout_small, dim3(1), dim3(1024), 0, st, g, (ChunkInfo*)info.p, (BlockOut*)d_table, (uint32_t*)blk_bytes.p, d_dst, dst_cap, (ResultRec*)d_res, (const uint64_t*)recs.p);
-        else {
-        if (g.n_blocks) hipLaunchKernelGGL((k_layout_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, g, (ChunkInfo*)info.p, (BlockOut*)d_table, (uint32_t*)blk_bytes.p);
-        hipLaunchKernelGGL(k_layout_scan, dim3(1), dim3(1024), 0, st, g, (BlockOut*)d_table, (const uint32_t*)blk_bytes.p, d_dst, dst_cap, (ResultRec*)d_res, (const uint64_t*)recs.p);
-        if (g.n_chunks) hipLaunchKernelGGL(k_layout_chunks, dim3((g.n_chunks + 255) / 256), dim3(256), 0, st, g, (ChunkInfo*)info.p, (const BlockOut*)d_table, d_dst, (const ResultRec*)d_res);
-        }
-        if (g.n_chunks) recs_ctl_clean = recs.p;                                  // (the scan is enqueued: it leaves the pool's control words at zero)
-        if (d_index) {                                                            // sequence index for the indexed decoder
-            if (g.n_blocks) hipLaunchKernelGGL((k_index_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, g, (const ChunkInfo*)info.p, (const BlockOut*)d_table, (const ResultRec*)d_res, d_index, (uint64_t)index_cap);
-            hipLaunchKernelGGL(k_build_index, dim3(1), dim3(1024), 0, st, g, (const ChunkInfo*)info.p, (const BlockOut*)d_table, (const ResultRec*)d_res, d_index, (uint64_t)index_cap, 1u);
-        }
-    }
+    enc_layout(p, d_dst, dst_cap, r, tbl, d_index);
     tick(1, true);
-    if (g.n_chunks) {
-        tick(2, false);
-        // (few chunks - the streaming API's one block per call: the four waves of a workgroup share a chunk instead of taking one each)
-        const bool e2_split = g.n_chunks <= 512;
-        if (e2_split)
-            hipLaunchKernelGGL((k_emit_gather<W, true>), dim3(g.n_chunks), dim3(64 * W), 0, st, j.d_src, g, (const ChunkInfo*)info.p,
-                               (const uint64_t*)recs.p, d_dst, (const BlockOut*)d_table, d_index);
-        else
-        hipLaunchKernelGGL((k_emit_gather<W, false>), dim3((g.n_chunks + W - 1) / W), dim3(64 * W), 0, st, j.d_src, g, (const ChunkInfo*)info.p,
-                           (const uint64_t*)recs.p, d_dst, (const BlockOut*)d_table, d_index);
-        tick(2, true);
-        if (j.block_checksum) {
-            tick(3, false);
-            if (g.n_blocks < XXH_LANE4_BELOW)                          // few big blocks: the four accumulators as four lanes (lane4_xxh32)
-                hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(g.n_blocks), dim3(64), XXH_SPREAD_LDS, st, d_dst, (BlockOut*)d_table, (const ResultRec*)d_res, g.n_blocks, 0u, (uint32_t*)nullptr);
-            else
-            hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, d_dst, (BlockOut*)d_table,
-                               (const ResultRec*)d_res, g.n_blocks, 0u, (uint32_t*)nullptr);
-            tick(3, true);
-        }
-    }
-    if (j.endmark && j.content_checksum)                              // (one chain over the whole input: see k_xxh32_content for what that costs)
-        hipLaunchKernelGGL(k_xxh32_content, dim3(1), dim3(64), 0, st, j.d_src + j.first_off, (uint64_t)(j.src_size - j.first_off), d_dst, (ResultRec*)d_res, 0u);
-    if (inband && g.n_blocks) {
-        TrailerPlan* plan = (TrailerPlan*)((uint8_t*)res.p + sizeof(ResultRec) + 32);
-        hipLaunchKernelGGL(k_trailer_plan, dim3(1), dim3(64), 0, st, d_dst, dst_cap, (ResultRec*)d_res, g.n_blocks, (const void*)d_index,
-                           (uint64_t)ix_entries_at(g.n_blocks, g.chunks_per_block), plan);
-        hipLaunchKernelGGL(k_trailer_copy, dim3(256), dim3(256), 0, st, d_dst, (const TrailerPlan*)plan, (const BlockOut*)d_table, g.n_blocks, (const void*)d_index);
-    }
+    if (p.g.n_chunks) enc_emit(j, p, d_dst, r, tbl, d_index);
+    enc_tail(j, p, d_dst, dst_cap, r, tbl, d_index);
     tick(10, true);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -874,368 +953,6 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// host-pointer helpers
-// The host-pointer calls are bounded by how fast bytes move between the caller's (pageable) buffers and the pinned staging
-// buffers: one thread's memcpy is ~10 GB/s, a fifth of what the PCIe link takes.  Large copies are split over a few threads.
-static void big_memcpy(void* dst, const void* src, size_t n)
-{
-    const size_t MIN_PER_THREAD = (size_t)8 << 20;
-    unsigned hw = std::thread::hardware_concurrency();
-    size_t t = std::min<size_t>(std::min<size_t>(hw ? hw : 1, 8), n / MIN_PER_THREAD);
-    if (t <= 1) { memcpy(dst, src, n); return; }
-    const size_t per = ((n / t) + 4095) & ~(size_t)4095;
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < t; i++) {
-        const size_t a = i * per;
-        if (a >= n) break;
-        const size_t len = std::min(per, n - a);
-        th.emplace_back([=] { memcpy((uint8_t*)dst + a, (const uint8_t*)src + a, len); });
-    }
-    memcpy(dst, src, std::min(per, n));
-    for (auto& x : th) x.join();
-}
-
-// Host buffer <-> device through the pinned staging buffer, in pieces: the copy between the caller's pageable memory and the
-// staging buffer (CPU threads) of one piece runs while the DMA of the piece before is in flight, instead of one after the other.
-// Is `p` page-locked memory the DMA engines can reach directly (hipHostMalloc / hipHostRegister: lz4f_mi355x_host_alloc,
-// the conduits' batch buffers)?  Then no staging copy is needed.
-// One upload and one download at a time per device.  Engines that share a device share its host link: two uploads side by
-// side each take twice as long, and - symmetric as they are - the engines then also download side by side, so the link is never
-// busy in both directions (measured: 32 GiB/s).  With a token per direction they fall out of step by themselves: one engine's
-// upload runs beside the other's kernels and download.
-namespace { std::mutex g_up_mu[16], g_down_mu[16]; }
-static std::mutex& up_token(int device) { return g_up_mu[(unsigned)device % 16]; }
-static std::mutex& down_token(int device) { return g_down_mu[(unsigned)device % 16]; }
-
-bool lz4f::is_pinned_host(const void* p)
-{
-    hipPointerAttribute_t a; memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-static const size_t XFER_PIECE = (size_t)32 << 20;
-static hipError_t staged_h2d(void* d_dst, void* pinned, const void* src, size_t n, hipStream_t st)
-{
-    for (size_t a = 0; a < n; a += XFER_PIECE) {
-        const size_t len = std::min(XFER_PIECE, n - a);
-        big_memcpy((uint8_t*)pinned + a, (const uint8_t*)src + a, len);
-        hipError_t e = hipMemcpyAsync((uint8_t*)d_dst + a, (uint8_t*)pinned + a, len, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-static hipError_t staged_d2h(void* dst, void* pinned, const void* d_src, size_t n, hipStream_t st)
-{
-    const size_t np = (n + XFER_PIECE - 1) / XFER_PIECE;
-    std::vector<hipEvent_t> ev(np);
-    hipError_t e = hipSuccess;
-    size_t made = 0;
-    for (size_t i = 0; i < np && e == hipSuccess; i++) {
-        const size_t a = i * XFER_PIECE, len = std::min(XFER_PIECE, n - a);
-        e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) break;
-        made++;
-        e = hipMemcpyAsync((uint8_t*)pinned + a, (const uint8_t*)d_src + a, len, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(ev[i], st);
-    }
-    for (size_t i = 0; i < made; i++) {
-        if (e == hipSuccess) e = hipEventSynchronize(ev[i]);
-        if (e == hipSuccess) { const size_t a = i * XFER_PIECE, len = std::min(XFER_PIECE, n - a); big_memcpy((uint8_t*)dst + a, (uint8_t*)pinned + a, len); }
-        (void)hipEventDestroy(ev[i]);
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    return e;
-}
-
-size_t lz4f_mi355x_engine::slab_compress(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len, uint32_t block_size, bool linked,
-                                         bool block_checksum, bool src_pinned, size_t* size, int level)
-{
-    *size = 0;
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!linked) hist_len = 0;
-    if (hist_len > 65536) { hist += hist_len - 65536; hist_len = 65536; }
-    const size_t total = hist_len + n;
-    const size_t nblocks = (n + block_size - 1) / block_size;
-    const size_t out_cap = n + nblocks * 8 + 64;
-    if ((!src_pinned && h_in.ensure(total)) || h_small.ensure(65536 + 256) || d_in.ensure(total + 64) || d_out.ensure(out_cap) || res.ensure(sizeof(ResultRec)))
-        return make_err(LZ4F_ERROR_allocation_failed);
-    {
-        std::lock_guard<std::mutex> up(up_token(device));
-        if (hist_len) {
-            if (src_pinned && hist + hist_len == src) HIP_TRY(hipMemcpyAsync(d_in.p, hist, hist_len, hipMemcpyHostToDevice, st));      // (the history sits in front of the input, in the same pinned buffer)
-            else { memcpy(h_small.p, hist, hist_len); HIP_TRY(hipMemcpyAsync(d_in.p, h_small.p, hist_len, hipMemcpyHostToDevice, st)); }
-        }
-        if (src_pinned) HIP_TRY(hipMemcpyAsync((uint8_t*)d_in.p + hist_len, src, n, hipMemcpyHostToDevice, st));
-        else HIP_TRY(staged_h2d((uint8_t*)d_in.p + hist_len, (uint8_t*)h_in.p + hist_len, src, n, st));
-        if (n >= ((size_t)8 << 20)) HIP_TRY(hipStreamSynchronize(st));      // (bulk slabs: hold the token until the bytes are over)
-    }
-    CompressJob j; memset(&j, 0, sizeof(j));
-    j.d_src = (const uint8_t*)d_in.p; j.src_size = total; j.first_off = hist_len; j.block_size = block_size;
-    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0; j.level = level;
-    size_t r = launch_compress(j, (uint8_t*)d_out.p, out_cap, (lz4f_mi355x_result*)res.p, nullptr);
-    if (is_err(r)) return r;
-    ResultRec* hr = (ResultRec*)((uint8_t*)h_small.p + 65536 + 64);
-    HIP_TRY(hipMemcpyAsync(hr, res.p, sizeof(ResultRec), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (hr->status != ST_OK) { set_last_error("device compress status %u", hr->status); return make_err((int)hr->status); }
-    *size = hr->size;
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::compress_block_pinned(const uint8_t* pin_src, size_t hist_len, size_t n, uint32_t block_size, bool linked, bool block_checksum,
-                                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size, int level)
-{
-    // (Kernels reading the staging buffer through the link themselves - no copies at all - were tried first: 510 us per 64 KiB block
-    // against 190 us with copies.  A kernel's scattered 16-byte reads over PCIe are not what a DMA engine's are.)
-    *size = 0;
-    if (n == 0) return 0;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!linked) hist_len = 0;
-    const size_t total = hist_len + n;
-    const size_t out_cap = n + ((n + block_size - 1) / block_size) * 8 + 64;
-    const size_t res_at = (out_cap + 63) & ~(size_t)63;                  // the result record rides behind the blocks: one copy back
-    if (out_cap > dst_cap) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-    if (d_in.ensure(total + 64) || d_out.ensure(res_at + sizeof(ResultRec) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-    HIP_TRY(hipMemcpyAsync(d_in.p, pin_src, total, hipMemcpyHostToDevice, st));
-    CompressJob j; memset(&j, 0, sizeof(j));
-    j.d_src = (const uint8_t*)d_in.p; j.src_size = total; j.first_off = hist_len; j.block_size = block_size;
-    j.linked = linked; j.block_checksum = block_checksum; j.endmark = false; j.header_size = 0; j.level = level;
-    lz4f_mi355x_result* d_res = (lz4f_mi355x_result*)((uint8_t*)d_out.p + res_at);
-    size_t r = launch_compress(j, (uint8_t*)d_out.p, out_cap, d_res, nullptr);
-    if (is_err(r)) return r;
-    // (the blocks' size is not known on the host yet: everything up to the record comes back - at most a block and a few bytes)
-    HIP_TRY(hipMemcpyAsync(pin_dst, d_out.p, res_at + sizeof(ResultRec), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const ResultRec* hr = (const ResultRec*)(pin_dst + res_at);
-    if (hr->status != ST_OK) { set_last_error("device compress status %u", hr->status); return make_err((int)hr->status); }
-    *size = hr->size;
-    (void)pin_res;
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::slab_fetch(uint8_t* dst, size_t size, size_t d_off, bool dst_pinned)
-{
-    if (size == 0) return 0;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!dst_pinned && h_out.ensure(size + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-    std::lock_guard<std::mutex> down(down_token(device));
-    if (dst_pinned) { HIP_TRY(hipMemcpyAsync(dst, (const uint8_t*)d_out.p + d_off, size, hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); return 0; }
-    HIP_TRY(staged_d2h(dst, h_out.p, (const uint8_t*)d_out.p + d_off, size, st));
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::compress_blocks_host(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len,
-                                                uint32_t block_size, bool linked, bool block_checksum, uint8_t* dst, size_t dst_cap, size_t* written, int level)
-{
-    *written = 0;
-    size_t size = 0;
-    size_t r = slab_compress(src, n, hist, hist_len, block_size, linked, block_checksum, false, &size, level);
-    if (is_err(r)) return r;
-    if (size > dst_cap) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-    r = slab_fetch(dst, size, 0, false);
-    if (is_err(r)) return r;
-    *written = size;
-    return 0;
-}
-
-static size_t status_to_err(uint32_t st)
-{
-    return st == ST_OK ? 0 : make_err((int)st);
-}
-
-size_t lz4f_mi355x_engine::slab_decode(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries,
-                                       const ParsedHeader& ph, const uint8_t* hist, size_t hist_len, bool src_pinned, size_t* got,
-                                       uint8_t* fetch_to, size_t fetch_room)
-{   // fetch_to (one block of at most 256 KiB - the streaming API's call): the output comes back with the result record, before the ONE
-    // synchronisation of the call - a block's worth is copied whatever the block decodes to, and what it did decode to goes to fetch_to
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t st = (hipStream_t)stream;
-    const bool linked = ph.info.blockMode == LZ4F_blockLinked;
-    if (!linked) hist_len = 0;
-    const size_t nb = entries.size();
-    // the device buffer always has room for every block at full size: blocks are decoded at provisional positions and
-    // compacted when some are short (frames written with LZ4F_flush); only what is actually produced must fit the caller's buffer
-    const size_t out_room = nb * ph.max_block;
-    const size_t tbytes = nb * sizeof(BlockOut);
-    // One block of at most 256 KiB out of pageable memory (the streaming API's call): table, payload and history go up in ONE copy, laid out
-    // [table | payload | history] in front of the output - three copies of a few KiB each cost more in launches than in bytes
-    const bool one_up = fetch_to && nb == 1 && !src_pinned && ph.max_block <= (256u << 10);
-    const size_t up_pay = 64, up_hist = (up_pay + part_len + 63 + 64) & ~(size_t)63, up_out = (up_hist + hist_len + 63) & ~(size_t)63;      // (history right-aligned in front of the output)
-    if (one_up) {
-        if (h_in.ensure(up_out + 256) || d_out.ensure(up_out + out_room + 64) || res.ensure(sizeof(ResultRec))) return make_err(LZ4F_ERROR_allocation_failed);
-        uint8_t* hp = (uint8_t*)h_in.p;
-        memcpy(hp, entries.data(), tbytes);
-        memcpy(hp + up_pay, frame_part, part_len);
-        if (hist_len) memcpy(hp + up_out - hist_len, hist, hist_len);
-        { std::lock_guard<std::mutex> up(up_token(device)); HIP_TRY(hipMemcpyAsync(d_out.p, hp, up_out, hipMemcpyHostToDevice, st)); }
-        DecompressJob j; memset(&j, 0, sizeof(j));
-        j.d_frame = (const uint8_t*)d_out.p + up_pay; j.frame_cap = part_len; j.d_dst = (uint8_t*)d_out.p + up_out; j.dst_cap = out_room; j.hist0 = hist_len;
-        j.block_size = (uint32_t)ph.max_block; j.linked = linked; j.block_checksum = ph.info.blockChecksumFlag != 0;
-        j.table_direct = (lz4f_mi355x_block*)d_out.p; j.n_blocks = 1; j.max_blocks = 1;
-        size_t r = launch_decompress(j, (lz4f_mi355x_result*)res.p);
-        if (is_err(r)) return r;
-        ResultRec* hr = (ResultRec*)(hp + up_out + 64);
-        if (h_out.ensure(ph.max_block + 64)) return make_err(LZ4F_ERROR_allocation_failed);
-        HIP_TRY(hipMemcpyAsync(h_out.p, j.d_dst, ph.max_block, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(hr, res.p, sizeof(ResultRec), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (hr->status != ST_OK) { set_last_error("device decode status %u at block %u", hr->status, hr->first_bad_block); return status_to_err(hr->status); }
-        *got = hr->size;
-        if (hr->size > fetch_room) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-        memcpy(fetch_to, h_out.p, hr->size);
-        return 0;
-    }
-    if (h_in.ensure((src_pinned ? 0 : part_len) + tbytes + hist_len + 128) || d_in.ensure(part_len + 64) || d_out.ensure(hist_len + out_room + 64) ||
-        res.ensure(sizeof(ResultRec)) || table.ensure((nb + 1) * sizeof(BlockOut)))
-        return make_err(LZ4F_ERROR_allocation_failed);
-    uint8_t* hp = (uint8_t*)h_in.p;
-    const size_t at_tab = src_pinned ? 0 : part_len;
-    memcpy(hp + at_tab, entries.data(), tbytes);
-    if (hist_len) memcpy(hp + at_tab + tbytes, hist, hist_len);
-    {
-        std::lock_guard<std::mutex> up(up_token(device));
-        if (src_pinned) HIP_TRY(hipMemcpyAsync(d_in.p, frame_part, part_len, hipMemcpyHostToDevice, st));
-        else HIP_TRY(staged_h2d(d_in.p, hp, frame_part, part_len, st));
-        HIP_TRY(hipMemcpyAsync(table.p, hp + at_tab, tbytes, hipMemcpyHostToDevice, st));
-        if (hist_len) HIP_TRY(hipMemcpyAsync(d_out.p, hp + at_tab + tbytes, hist_len, hipMemcpyHostToDevice, st));
-        if (part_len >= ((size_t)8 << 20)) HIP_TRY(hipStreamSynchronize(st));
-    }
-    DecompressJob j; memset(&j, 0, sizeof(j));
-    j.d_frame = (const uint8_t*)d_in.p; j.frame_cap = part_len; j.d_dst = (uint8_t*)d_out.p + hist_len; j.dst_cap = out_room; j.hist0 = hist_len;
-    j.block_size = (uint32_t)ph.max_block; j.linked = linked; j.block_checksum = ph.info.blockChecksumFlag != 0;
-    j.table_in_place = true; j.n_blocks = (uint32_t)nb; j.max_blocks = (uint32_t)nb;
-    size_t r = launch_decompress(j, (lz4f_mi355x_result*)res.p);
-    if (is_err(r)) return r;
-    ResultRec* hr = (ResultRec*)(hp + at_tab + tbytes + hist_len + 8 - ((at_tab + tbytes + hist_len) & 7) + 8);
-    const bool with_out = fetch_to && nb == 1 && ph.max_block <= (256u << 10) && !h_out.ensure(ph.max_block + 64);
-    if (with_out) HIP_TRY(hipMemcpyAsync(h_out.p, (const uint8_t*)d_out.p + hist_len, ph.max_block, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hr, res.p, sizeof(ResultRec), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (hr->status != ST_OK) { set_last_error("device decode status %u at block %u", hr->status, hr->first_bad_block); return status_to_err(hr->status); }
-    *got = hr->size;
-    if (fetch_to) {
-        if (hr->size > fetch_room) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-        if (with_out) memcpy(fetch_to, h_out.p, hr->size);
-        else { const size_t r2 = slab_fetch(fetch_to, hr->size, hist_len, false); if (is_err(r2)) return r2; }
-    }
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::run_decode_slab(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries,
-                                           const ParsedHeader& ph, const uint8_t* hist, size_t hist_len, uint8_t* dst, size_t dst_room, size_t* got)
-{
-    const bool linked = ph.info.blockMode == LZ4F_blockLinked;
-    if (!linked) hist_len = 0;
-    size_t n = 0;
-    size_t r = slab_decode(frame_part, part_len, entries, ph, hist, hist_len, false, &n, dst, dst_room);
-    if (is_err(r)) return r;
-    *got = n;
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::decompress_block_host(const uint8_t* payload, uint32_t csize, bool bck, const uint8_t* hist, size_t hist_len,
-                                                 uint8_t* dst, uint32_t dst_cap, bool linked, uint32_t block_size, uint32_t* decoded)
-{
-    ParsedHeader ph; memset(&ph, 0, sizeof(ph));
-    ph.max_block = block_size;
-    ph.info.blockMode = linked ? LZ4F_blockLinked : LZ4F_blockIndependent;
-    ph.info.blockChecksumFlag = bck ? LZ4F_blockChecksumEnabled : LZ4F_noBlockChecksum;
-    std::vector<lz4f_mi355x_block> e(1);
-    e[0].src_off = 0; e[0].dst_off = 0; e[0].word = csize; e[0].dst_size = dst_cap < block_size ? dst_cap : block_size;
-    size_t got = 0;
-    size_t r = run_decode_slab(payload, (size_t)csize + (bck ? 4 : 0), e, ph, hist, hist_len, dst, dst_cap, &got);
-    if (is_err(r)) return r;
-    *decoded = (uint32_t)got;
-    return 0;
-}
-
-size_t lz4f_mi355x_engine::decompress_frame_host(const uint8_t* s, size_t n, const ParsedHeader& ph, uint8_t* dst, size_t cap,
-                                                 size_t* decoded, size_t* consumed)
-{
-    const size_t SLAB_SRC = (size_t)256 << 20, SLAB_DST = (size_t)512 << 20;
-    const size_t crc = ph.info.blockChecksumFlag ? 4 : 0;
-    const bool linked = ph.info.blockMode == LZ4F_blockLinked;
-    auto rd32 = [&](size_t at) { return (uint32_t)s[at] | ((uint32_t)s[at + 1] << 8) | ((uint32_t)s[at + 2] << 16) | ((uint32_t)s[at + 3] << 24); };
-    size_t pos = ph.header_size, out = 0;
-    bool end = false;
-    std::vector<lz4f_mi355x_block> entries;
-    while (!end) {
-        entries.clear();
-        const size_t slab_src = pos; size_t prov = 0;
-        for (;;) {
-            if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-            const uint32_t w = rd32(pos);
-            if (w == 0) { end = true; break; }
-            const size_t csz = w & 0x7FFFFFFFu;
-            if (csz > ph.max_block) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-            if (n - pos - 4 < csz + crc) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-            if (!entries.empty() && ((pos - slab_src) + 4 + csz + crc > SLAB_SRC || prov + ph.max_block > SLAB_DST)) break;
-            lz4f_mi355x_block e;
-            e.src_off = pos + 4 - slab_src; e.dst_off = prov; e.word = w;
-            e.dst_size = (uint32_t)ph.max_block;
-            entries.push_back(e);
-            pos += 4 + csz + crc; prov += ph.max_block;
-        }
-        if (!entries.empty()) {
-            size_t got = 0;
-            const size_t hl = linked ? std::min(out, (size_t)65536) : 0;
-            size_t r = run_decode_slab(s + slab_src, pos - slab_src, entries, ph, dst + out - hl, hl, dst + out, cap - out, &got);
-            if (is_err(r)) return r;
-            out += got;
-        }
-    }
-    pos += 4;                                                   // EndMark
-    if (ph.info.contentSize && ph.info.contentSize != out) return make_err(LZ4F_ERROR_frameSize_wrong);
-    if (ph.info.contentChecksumFlag) {
-        if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        if (rd32(pos) != xxh32_host(dst, out)) return make_err(LZ4F_ERROR_contentChecksum_invalid);   // serial by construction: host
-        pos += 4;
-    }
-    *decoded = out; *consumed = pos;
-    return 0;
-}
-
-// ---- the trailer's block list made on the host (same bytes k_trailer_plan / k_trailer_copy write for a frame without a sequence index) ----
-namespace lz4f {
-bool BlockList::add_blocks(const uint8_t* b, size_t n, uint64_t frame_off, bool bck)
-{
-    size_t pos = 0;
-    while (pos < n) {
-        if (n - pos < 4) return false;
-        const uint32_t w = (uint32_t)b[pos] | ((uint32_t)b[pos + 1] << 8) | ((uint32_t)b[pos + 2] << 16) | ((uint32_t)b[pos + 3] << 24);
-        const size_t step = 4 + (size_t)(w & 0x7FFFFFFFu) + (bck ? 4 : 0);
-        if (w == 0 || step > n - pos) return false;
-        at.push_back(frame_off + pos);
-        pos += step;
-    }
-    return true;
-}
-size_t host_trailer_size(uint64_t F, uint64_t n_blocks)
-{
-    if (n_blocks == 0) return 0;
-    if (n_blocks > 0x7FFFFFFFull) return make_err(LZ4F_ERROR_frameSize_wrong);
-    const uint64_t list_at = (F + 8 + 15) & ~(uint64_t)15, n_list = (n_blocks + 1) & ~1ull;
-    const uint64_t total = list_at + n_list * 8 + sizeof(TrailerFoot) - F;
-    if (total - 8 >= 0xFFFFFFFFull) return make_err(LZ4F_ERROR_frameSize_wrong);        // (a skippable frame's size field is 32 bits)
-    return (size_t)total;
-}
-void host_write_trailer(uint8_t* t, uint64_t F, const uint64_t* at, uint32_t n_blocks)
-{
-    const uint64_t list_at = (F + 8 + 15) & ~(uint64_t)15, n_list = ((uint64_t)n_blocks + 1) & ~1ull, ix_at = list_at + n_list * 8;
-    const uint64_t total = ix_at + sizeof(TrailerFoot) - F;
-    const uint32_t sz = (uint32_t)(total - 8);
-    t[0] = 0x5E; t[1] = 0x2A; t[2] = 0x4D; t[3] = 0x18; t[4] = (uint8_t)sz; t[5] = (uint8_t)(sz >> 8); t[6] = (uint8_t)(sz >> 16); t[7] = (uint8_t)(sz >> 24);
-    memset(t + 8, 0, (size_t)(list_at - F - 8));
-    for (uint64_t i = 0; i < n_list; i++) { const uint64_t v = i < n_blocks ? at[i] : 0; memcpy(t + (list_at - F) + i * 8, &v, 8); }
-    const TrailerFoot f{0u, 0u, 0u, 0u, TR_FOOT, n_blocks, total};
-    memcpy(t + (ix_at - F), &f, sizeof(f));
-}
-}  // namespace lz4f
 
 // ------------------------------------------------------------------------------------------------
 // C ABI: engine + device-pointer entry points
@@ -1304,17 +1021,32 @@ size_t lz4f_mi355x_engine_get_timing_n(lz4f_mi355x_engine* e, float* ms, size_t 
 
 size_t lz4f_mi355x_dev_workspace_size(size_t srcSize, const LZ4F_preferences_t* prefs)
 {
-    size_t bs = block_size_of(prefs ? prefs->frameInfo.blockSizeID : 0);
+    const size_t bs = block_size_of(prefs ? prefs->frameInfo.blockSizeID : 0);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    uint32_t ch = pick_chunk_size((uint32_t)bs);
-    size_t nchunks = (srcSize + bs - 1) / bs * (bs / ch) + 1;
+    const EncShape s = enc_shape(srcSize, (uint32_t)bs);
+    const size_t nchunks = s.n_blocks * s.chunks_per_block + 1;
     // (the record pool as an engine with default switches sizes it: 12288 records of 8 bytes per 64 KiB tile = 1.5 bytes per input byte)
-    return nchunks * sizeof(ChunkInfo) + (size_t)(rec_pool_at((uint32_t)nchunks) + rec_pool_records((uint32_t)nchunks, ch / 4 + 1, 0)) * 8
-           + ((srcSize + bs - 1) / bs + 1) * (sizeof(BlockOut) + 4) + 4096;
+    return nchunks * sizeof(ChunkInfo) + (size_t)(rec_pool_at((uint32_t)nchunks) + rec_pool_records((uint32_t)nchunks, s.chunk / 4 + 1, 0)) * 8
+           + (s.n_blocks + 1) * (sizeof(BlockOut) + 4) + 4096;
 }
 
-size_t lz4f_mi355x_dev_compressFrame(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize,
-                                     const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_result, lz4f_mi355x_block* d_table)
+// (the index and trailer bounds take an invalid block size ID as 64 KiB)
+static EncShape sizing_shape(size_t srcSize, const LZ4F_preferences_t* prefs)
+{
+    const size_t bs = block_size_of(prefs ? prefs->frameInfo.blockSizeID : 0);
+    return enc_shape(srcSize, bs ? (uint32_t)bs : 65536u);
+}
+size_t lz4f_mi355x_dev_index_size(size_t srcSize, const LZ4F_preferences_t* prefs) { return index_capacity(srcSize, sizing_shape(srcSize, prefs)); }
+
+
+size_t lz4f_mi355x_trailer_bound(size_t srcSize, const LZ4F_preferences_t* prefs)
+{
+    return lz4f_mi355x_dev_index_size(srcSize, prefs) + (sizing_shape(srcSize, prefs).n_blocks + 2) * 8 + 128;
+}
+
+// the preferences resolved and checked, then the whole-frame job (index_cap: LZ4F_MI355X_INBAND, a given index's capacity, or 0 for none)
+static size_t compress_frame(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, const LZ4F_preferences_t* prefs,
+                             lz4f_mi355x_result* d_result, lz4f_mi355x_block* d_table, void* d_index, size_t index_cap)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
@@ -1323,29 +1055,15 @@ size_t lz4f_mi355x_dev_compressFrame(lz4f_mi355x_engine* e, void* d_dst, size_t 
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
     if (p.frameInfo.contentSize && p.frameInfo.contentSize != srcSize) return make_err(LZ4F_ERROR_frameSize_wrong);
-    lz4f_mi355x_engine::CompressJob j; memset(&j, 0, sizeof(j));
-    j.d_src = (const uint8_t*)d_src; j.src_size = srcSize; j.first_off = 0; j.block_size = (uint32_t)bs;
-    j.linked = p.frameInfo.blockMode == LZ4F_blockLinked; j.block_checksum = p.frameInfo.blockChecksumFlag != 0; j.endmark = true;
-    j.content_checksum = p.frameInfo.contentChecksumFlag != 0;
-    j.header_size = (uint32_t)write_frame_header(j.header, p);
-    j.level = p.compressionLevel;
-    return e->launch_compress(j, (uint8_t*)d_dst, dstCapacity, d_result, d_table);
+    const auto j = lz4f_mi355x_engine::make_compress_job((const uint8_t*)d_src, srcSize, 0, (uint32_t)bs, p.frameInfo.blockMode == LZ4F_blockLinked,
+                                                         p.frameInfo.blockChecksumFlag != 0, p.compressionLevel, &p);
+    return e->launch_compress(j, (uint8_t*)d_dst, dstCapacity, d_result, d_table, d_index, index_cap);
 }
 
-size_t lz4f_mi355x_dev_index_size(size_t srcSize, const LZ4F_preferences_t* prefs)
+size_t lz4f_mi355x_dev_compressFrame(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize,
+                                     const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_result, lz4f_mi355x_block* d_table)
 {
-    size_t bs = block_size_of(prefs ? prefs->frameInfo.blockSizeID : 0);
-    if (!bs) bs = 65536;
-    const uint32_t ch = pick_chunk_size((uint32_t)bs);
-    const uint32_t nb = (uint32_t)((srcSize + bs - 1) / bs), cpb = (uint32_t)(bs / ch);
-    return ix_entries_at(nb, cpb) + ix_typical_entries(srcSize, nb * cpb) * sizeof(IxEntry);
-}
-
-size_t lz4f_mi355x_trailer_bound(size_t srcSize, const LZ4F_preferences_t* prefs)
-{
-    size_t bs = block_size_of(prefs ? prefs->frameInfo.blockSizeID : 0);
-    if (!bs) bs = 65536;
-    return lz4f_mi355x_dev_index_size(srcSize, prefs) + ((srcSize + bs - 1) / bs + 2) * 8 + 128;
+    return compress_frame(e, d_dst, dstCapacity, d_src, srcSize, prefs, d_result, d_table, nullptr, 0);
 }
 
 size_t lz4f_mi355x_dev_compressFrameIndexed(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize,
@@ -1354,19 +1072,7 @@ size_t lz4f_mi355x_dev_compressFrameIndexed(lz4f_mi355x_engine* e, void* d_dst, 
 {
     const bool inband = d_index == nullptr && indexCapacity == LZ4F_MI355X_INBAND;
     if (!e || (!inband && (!d_table || !d_result))) return make_err(LZ4F_ERROR_GENERIC);
-    LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
-    if (prefs) p = *prefs;
-    if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
-    const size_t bs = block_size_of(p.frameInfo.blockSizeID);
-    if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    if (p.frameInfo.contentSize && p.frameInfo.contentSize != srcSize) return make_err(LZ4F_ERROR_frameSize_wrong);
-    lz4f_mi355x_engine::CompressJob j; memset(&j, 0, sizeof(j));
-    j.d_src = (const uint8_t*)d_src; j.src_size = srcSize; j.first_off = 0; j.block_size = (uint32_t)bs;
-    j.linked = p.frameInfo.blockMode == LZ4F_blockLinked; j.block_checksum = p.frameInfo.blockChecksumFlag != 0; j.endmark = true;
-    j.content_checksum = p.frameInfo.contentChecksumFlag != 0;
-    j.header_size = (uint32_t)write_frame_header(j.header, p);
-    j.level = p.compressionLevel;
-    return e->launch_compress(j, (uint8_t*)d_dst, dstCapacity, d_result, d_table, d_index, inband ? LZ4F_MI355X_INBAND : (d_index ? indexCapacity : 0));
+    return compress_frame(e, d_dst, dstCapacity, d_src, srcSize, prefs, d_result, d_table, d_index, inband ? LZ4F_MI355X_INBAND : (d_index ? indexCapacity : 0));
 }
 
 size_t lz4f_mi355x_dev_decompressBlocksIndexed(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_frame, size_t frameCapacity,

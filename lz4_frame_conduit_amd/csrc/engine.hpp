@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/lz4f_mi355x.h"
+#include "records.hpp"
 
 namespace lz4f {
 
@@ -47,7 +48,15 @@ struct PinBuf {
     void release();
 };
 
-struct BlockOut; struct ResultRec;                       // (common.cuh)
+// a failed HIP call ends the function: the call's text as the thread's last error, LZ4F_ERROR_GENERIC as its result
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) {                                                                         \
+            lz4f::set_last_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);  \
+            return lz4f::make_err(LZ4F_ERROR_GENERIC);                                                  \
+        }                                                                                               \
+    } while (0)
 
 }  // namespace lz4f
 
@@ -99,6 +108,9 @@ struct lz4f_mi355x_engine {
         uint8_t header[20]; uint32_t header_size;
         int level;                                               // compressionLevel: <= 2 pass E1 (encode.cuh / encode_solo.cuh), 3-12 the hash-chain finder (encode_hc.cuh), > 12 as 12
     };
+    // blocks only (the streaming calls, the slabs), or - with the resolved preferences of a frame - header, EndMark and content checksum as they say
+    static CompressJob make_compress_job(const uint8_t* d_src, uint64_t src_size, uint64_t first_off, uint32_t block_size, bool linked, bool block_checksum,
+                                         int level, const LZ4F_preferences_t* frame = nullptr);
     // returns 0 or an LZ4F error; d_res/d_table may be null (internal buffers are used)
     size_t launch_compress(const CompressJob& j, uint8_t* d_dst, uint64_t dst_cap, lz4f_mi355x_result* d_res, lz4f_mi355x_block* d_table,
                            void* d_index = nullptr, size_t index_cap = 0);
@@ -117,7 +129,7 @@ struct lz4f_mi355x_engine {
     size_t launch_decompress(const DecompressJob& j, lz4f_mi355x_result* d_res);
     size_t sync();
 
-    // ---- host-pointer helpers used by the streaming contexts and the bulk host calls ----
+    // ---- host-pointer helpers used by the streaming contexts and the bulk host calls (engine_host.hip) ----
     // Encode `n` bytes at src (host) as frame blocks of block_size (last may be short); `hist` bytes of
     // history (host) precede them when linked.  Appends [size word][payload][checksum] per block to out.
     size_t compress_blocks_host(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len,
@@ -127,12 +139,11 @@ struct lz4f_mi355x_engine {
     size_t slab_compress(const uint8_t* src, size_t n, const uint8_t* hist, size_t hist_len, uint32_t block_size, bool linked, bool block_checksum,
                          bool src_pinned, size_t* size, int level = 0);
     size_t slab_fetch(uint8_t* dst, size_t size, size_t d_off, bool dst_pinned);
-    // One block (or a short run of them) out of page-locked host memory and back into it, no copy calls: the kernels read the input
-    // (hist_len bytes of history, then n bytes) and write the block(s) and the result record through the link themselves.  What the
-    // LZ4F_* streaming functions do per completed block (frame_host.cpp): upload, download and one of the two synchronisations of the
-    // staged path are gone.  Both buffers from lz4f::PinBuf (hipHostMalloc).
+    // One block (or a short run of them) out of page-locked host memory and back into it: hist_len bytes of history, then n bytes, go up in one
+    // copy; the block(s) and the result record behind them come back in one copy, with one synchronisation.  What the LZ4F_* streaming
+    // functions do per completed block (frame_host.cpp).  Both buffers from lz4f::PinBuf (hipHostMalloc).
     size_t compress_block_pinned(const uint8_t* pin_src, size_t hist_len, size_t n, uint32_t block_size, bool linked, bool block_checksum,
-                                 uint8_t* pin_dst, size_t dst_cap, void* pin_res, size_t* size, int level = 0);
+                                 uint8_t* pin_dst, size_t dst_cap, size_t* size, int level = 0);
     size_t slab_decode(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries, const lz4f::ParsedHeader& ph,
                        const uint8_t* hist, size_t hist_len, bool src_pinned, size_t* got, uint8_t* fetch_to = nullptr, size_t fetch_room = 0);
     // Decode one compressed block payload (host; followed by its 4-byte checksum when bck) with `hist_len`
@@ -140,13 +151,21 @@ struct lz4f_mi355x_engine {
     // the decoded bytes land in dst (host).
     size_t decompress_block_host(const uint8_t* payload, uint32_t csize, bool bck, const uint8_t* hist, size_t hist_len,
                                  uint8_t* dst, uint32_t dst_cap, bool linked, uint32_t block_size, uint32_t* decoded);
-    // Whole frame (host) -> dst (host): host walk of the size words, then one device call per slab of blocks.
-    size_t decompress_frame_host(const uint8_t* frame, size_t n, const lz4f::ParsedHeader& ph, uint8_t* dst, size_t cap,
-                                 size_t* decoded, size_t* consumed);
 
     ~lz4f_mi355x_engine();
 
 private:
+    // ---- launch_compress: a plan, then one function per stage, in the order they run (engine.hip) ----
+    // What an encode call does that depends on the call alone: the kernels' geometry, which kernels run, every workspace's size
+    // (defined in engine.hip: it holds the kernels' EncGeom)
+    struct EncodePlan;
+    static EncodePlan encode_plan(const CompressJob& j, const Switches& sw, uint32_t cus, bool inband, size_t index_cap);
+    size_t enc_workspaces(const EncodePlan& p, bool own_table);
+    size_t enc_find(const CompressJob& j, const EncodePlan& p);
+    void   enc_layout(const EncodePlan& p, uint8_t* d_dst, uint64_t dst_cap, lz4f::ResultRec* rec, lz4f::BlockOut* tbl, void* d_index);
+    void   enc_emit(const CompressJob& j, const EncodePlan& p, uint8_t* d_dst, const lz4f::ResultRec* rec, lz4f::BlockOut* tbl, void* d_index);
+    void   enc_tail(const CompressJob& j, const EncodePlan& p, uint8_t* d_dst, uint64_t dst_cap, lz4f::ResultRec* rec, const lz4f::BlockOut* tbl, const void* d_index);
+
     // ---- launch_decompress: a plan, then one function per stage, in the order they run (engine.hip) ----
     // What a decode call does that depends on the call alone (job, switches, CU count), never on what is read back from the device
     struct DecodePlan {
@@ -177,9 +196,6 @@ private:
     size_t dec_indexed(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const IndexSrc& ix, const uint32_t** ix_flags, uint32_t* path);
     size_t dec_generic(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const uint32_t* only_if, uint32_t* path);
     size_t dec_finish(const DecompressJob& j, const DecodePlan& p, lz4f::ResultRec* res, lz4f::BlockOut* tbl, const uint32_t* ix_flags, uint32_t path);
-
-    size_t run_decode_slab(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries,
-                           const lz4f::ParsedHeader& ph, const uint8_t* hist, size_t hist_len, uint8_t* dst, size_t dst_room, size_t* got);
 };
 
 namespace lz4f {

@@ -715,8 +715,7 @@ __global__ void k_walk_verdict(const uint8_t* __restrict__ frame, uint64_t frame
 //         |                    u32 'LZIX', u32 n_blocks, u64 trailer bytes (from the magic on)
 // Nothing in it is trusted: the positions are accepted only if they are the chain the size words themselves form (k_walk_link /
 // k_walk_verdict, as for the candidates of the parallel walk), the index only as far as k_parse_indexed can follow it in the payload.
-constexpr uint32_t TR_MAGIC = 0x184D2A5Eu, TR_FOOT = 0x58495A4Cu;
-struct TrailerFoot { uint32_t total_seqs, total_entries, pad0, pad1, magic, n_blocks; uint64_t total; };      // 32 bytes; the last 16 identify it
+// (TR_MAGIC, TR_FOOT and TrailerFoot: records.hpp - the host writes the same trailer for frames it assembles)
 struct TrailerPlan { uint64_t at, list_at, ix_at, ix_bytes, total; uint32_t n_list, ok; };
 
 __global__ void k_trailer_plan(uint8_t* __restrict__ dst, uint64_t dst_cap, ResultRec* __restrict__ res, uint32_t n_blocks, const void* __restrict__ ix,

@@ -223,7 +223,7 @@ static size_t encode_staged(LZ4F_cctx_s* c, uint8_t* dst, size_t cap, size_t n)
     uint8_t* out = (uint8_t*)c->pin_out.p;
     size_t size = 0;
     r = eng->compress_block_pinned(c->hist_at(), c->hist_len, n, (uint32_t)c->block_size, c->prefs.frameInfo.blockMode == LZ4F_blockLinked,
-                                   c->prefs.frameInfo.blockChecksumFlag != 0, out, out_cap + 192, nullptr, &size, c->prefs.compressionLevel);
+                                   c->prefs.frameInfo.blockChecksumFlag != 0, out, out_cap + 192, &size, c->prefs.compressionLevel);
     if (is_err(r)) return r;
     if (size > cap) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
     memcpy(dst, out, size);

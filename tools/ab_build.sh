@@ -10,7 +10,7 @@ pids=()
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function $flags -c -o ../build/ab/engine_$name.o engine.hip &&
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -Wl,-soname,liblz4f_mi355x.so -o ../build/ab/lib_$name.so ../build/ab/engine_$name.o ../build/pipeline.o ../build/frame_host.o ../build/conduit.o &&
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -Wl,-soname,liblz4f_mi355x.so -o ../build/ab/lib_$name.so ../build/ab/engine_$name.o ../build/engine_host.o ../build/pipeline.o ../build/frame_host.o ../build/conduit.o &&
     rm -f ../build/ab/engine_$name.o && echo "built $name ($flags)" ) &
   pids+=($!)
   if [ ${#pids[@]} -ge 6 ]; then wait ${pids[0]}; pids=("${pids[@]:1}"); fi
