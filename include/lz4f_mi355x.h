@@ -272,6 +272,24 @@ typedef struct {
     uint32_t dst_size;    /* decoded bytes (filled by decode; blockSize-capacity on input) */
 } lz4f_mi355x_block;
 
+/* ALIGNMENT of the device pointers of every lz4f_mi355x_dev_* call below (tests/test_gpu_alignment.py moves each of them):
+ *   - data buffers - d_src, d_dst, d_frame, the d_src / d_dst of the batch call and every span and window inside them - take ANY
+ *     byte address: a frame inside a bigger receive buffer, a view that starts at byte 1.  The bytes written (deterministic
+ *     encoders: the frame's bytes; every decoder: the output) and every verdict are the same at every address.
+ *   - block tables (d_table, lz4f_mi355x_block: 64-bit words) and the batch call's d_src_off / d_dst_off: 8 bytes.
+ *   - sequence indexes (d_index, 16-byte units): 16 bytes.
+ *   - result records (d_result / d_results): 8 bytes.
+ *   - the in-band call (indexCapacity == LZ4F_MI355X_INBAND): d_dst 16 bytes - the one requirement on a data buffer, checked:
+ *     the call returns ERROR_GENERIC ("in-band index: the frame buffer must be 16-byte aligned") and writes nothing.
+ *   - one DECISION depends on an address: lz4f_mi355x_dev_decompressFrame looks at a trailer (in-band index, block list) only when
+ *     d_frame is 16-byte aligned; elsewhere the same stream is walked and parsed as a frame without one - same bytes, same
+ *     size and consumed, other path bits (a hint, as said at lz4f_mi355x_appendBlockList).
+ * Nothing is written outside [d_dst, d_dst + dstCapacity), the table's srcSize / blockSize + 1 entries, the index's capacity and the records.
+ * Reads: the kernels bound every fetch from a frame by frameCapacity (the 16-byte fetches at a frame's end go byte by byte);
+ * the block decoder's scalar fetches round a payload's start down and its end up to 4 bytes of ADDRESS, which are bytes of the
+ * same frame (a size word in front, a checksum or the next size word / EndMark behind).  No read outside the extents a call
+ * names is known; the tests do not probe for one at an allocation's edge. */
+
 /* Bytes of device workspace the engine will hold for inputs up to srcSize (informational). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_workspace_size(size_t srcSize, const LZ4F_preferences_t* prefs);
 
