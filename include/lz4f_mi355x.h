@@ -399,7 +399,46 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, u
                                                         const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                         void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
                                                         lz4f_mi355x_result* d_results);
-#define LZ4F_MI355X_PATH_BATCH 0x1000u   /* result.flags bits 12..: the frame went through the batch decoder (dev_decompressFrames) */
+#define LZ4F_MI355X_PATH_BATCH 0x1000u   /* result.flags bits 12..: the frame went through the batch decoder (dev_decompressFrames), or was made by the batch encoder (dev_compressFrames) */
+
+/* BATCH ENCODE: n_frames inputs, one frame each, in one call - the mirror image of lz4f_mi355x_dev_decompressFrames, with its conventions,
+ * so that the output of one is the input of the other without the data visiting the host.  No host synchronisation, no device->host
+ * copy, and a number of kernel launches that does not depend on n_frames.
+ * Input i is d_src[src_off[i] .. src_off[i+1]); frame i is written at d_dst + dst_off[i] and may use the window d_dst[dst_off[i] ..
+ * dst_off[i+1]).  d_src_off / d_dst_off: n_frames + 1 uint64 each, DEVICE memory, 8-byte aligned.  srcBytes / dstBytes: the extents of
+ * d_src / d_dst (host values: they size the workspace and bound every span and window).  The data buffers, spans and windows take any byte
+ * address.  d_results: n_frames records, DEVICE memory.  Asynchronous on the engine's stream.
+ * prefs (NULL = defaults) holds for the whole batch: blockSizeID, blockMode, blockChecksumFlag, contentChecksumFlag, dictID and
+ * compressionLevel mean what they mean to lz4f_mi355x_dev_compressFrame.  frameInfo.contentSize != 0 means "every frame's header declares
+ * its own input's length" (the value itself is ignored; an empty input's header declares none, as a contentSize of 0 means to the single call).
+ *   - A frame in a batch is the frame it would be alone.  The batch always uses the deterministic match finders (levels <= 2 and 3-12),
+ *     whatever lz4f_mi355x_engine_set_deterministic says: frame i's bytes are exactly what lz4f_mi355x_dev_compressFrame writes for input i
+ *     alone on an engine in deterministic mode with the same preferences (contentSize = that input's length where the batch was asked for
+ *     content sizes), and d_results[i] has that call's size (frame bytes), consumed (input bytes), status, n_blocks and FLG byte
+ *     (flags & 0xFF); first_bad_block is 0xFFFFFFFF and the path bits (flags >> 12) are LZ4F_MI355X_PATH_BATCH.  The record workspace is
+ *     sized for the worst case of every chunk: LZ4F_MI355X_ENC_POOL_SHORT never appears.
+ *   - Frames are isolated: nothing is written outside window i on behalf of frame i, nothing beyond `size` bytes of it when the frame
+ *     succeeds, and nothing at all when it does not.  A window smaller than the frame gives that frame ERROR_dstMaxSize_tooSmall (size 0)
+ *     and leaves every other frame as it would have been; a window of lz4f_mi355x_compressFrameBound(length of input i, prefs) always
+ *     suffices.  src_off[i] > src_off[i+1] or a span ending past srcBytes gives that frame ERROR_srcPtr_wrong; dst_off[i] > dst_off[i+1]
+ *     or a window ending past dstBytes ERROR_dstMaxSize_tooSmall; nothing is written for such a frame.  Bytes inside a failed frame's
+ *     window are unspecified.  Windows that overlap each other are the caller's race; spans that overlap are legal (they are only read).
+ *   - The workspace comes from the call's arguments alone: 72 bytes per frame, 128 bytes per (n_frames + srcBytes / 64 KiB + 1) block /
+ *     chunk entries, and 8 bytes per (srcBytes / 4 + one per entry) sequence records - 2 bytes per source byte, grown as needed.  Spans
+ *     that do not overlap never need more.  Where overlapping spans do: entries are handed out in frame order, and the first frame
+ *     that does not get its own, with every non-empty frame behind it, fails with ERROR_srcSize_tooLarge; the frames in front of it
+ *     are what they would have been.
+ *   - The call itself fails only on a null engine, a null pointer with n_frames > 0, an invalid blockSizeID in prefs
+ *     (ERROR_maxBlockSize_invalid, as the single call), or a failed allocation.  n_frames == 0 returns 0 and enqueues nothing.  An empty
+ *     input is a valid frame (header + EndMark, + the checksum of nothing when asked for).
+ * The match finders run a wave (levels <= 2) or a workgroup (3-12) per 64 KiB chunk across all frames; layout and block checksums a
+ * wave per block; header, size words, EndMark and content checksum a wave per frame.  No sequence index, no in-band trailer and no block
+ * table come out of this call, and a big input of many blocks gets one wave for its frame-level passes: send it through
+ * lz4f_mi355x_dev_compressFrame, which puts the shared finder on it. */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                      const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                      void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                      const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results);
 
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,

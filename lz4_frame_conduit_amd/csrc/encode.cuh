@@ -58,6 +58,29 @@ struct EncGeom {
     uint32_t hc_lazy;            // levels 3-12: positions the lazy parse looks ahead (1 or 2)
 };
 
+// A chunk's place in the source, resolved: what the deterministic match finders (encode_solo.cuh, encode_hc.cuh) and pass E2 work from.
+// One call's kernels compute it from the call's uniform EncGeom (enc_place); the batch encoder loads it from its chunk table
+// (encode_batch.cuh), where every frame has a geometry of its own.  All offsets are from `src`.
+struct EncPlace {
+    uint64_t bstart, bend_abs;   // the chunk's block
+    uint64_t cs_abs, ce_abs;     // the chunk
+    uint64_t low_abs;            // matches may not start before this: the block's start, or the input's when linked
+    uint64_t rd_end;             // nothing is read at or beyond this
+};
+// false: the chunk lies beyond a short last block
+__device__ __forceinline__ bool enc_place(const EncGeom& g, uint32_t chunk, EncPlace& pl)
+{
+    const uint32_t blk = chunk / g.chunks_per_block, cib = chunk % g.chunks_per_block;
+    pl.bstart = g.first_off + (uint64_t)blk * g.block_size;
+    pl.bend_abs = (pl.bstart + g.block_size < g.src_size) ? pl.bstart + g.block_size : g.src_size;
+    pl.cs_abs = pl.bstart + (uint64_t)cib * g.chunk_size;
+    if (pl.cs_abs >= pl.bend_abs) return false;
+    pl.ce_abs = (pl.cs_abs + g.chunk_size < pl.bend_abs) ? pl.cs_abs + g.chunk_size : pl.bend_abs;
+    pl.low_abs = g.linked ? 0 : pl.bstart;
+    pl.rd_end = g.src_size;
+    return true;
+}
+
 // The record workspace: [control: bump pointer, tiles that found the pool empty | u32 per chunk: where its list starts | the pool].
 // A tile's list is allocated when its merge knows how long it is - the workspace is sized for what inputs have (the engine: a record per
 // 5.3 input bytes by default), not for one per 4 bytes everywhere; a tile that finds the pool empty is emitted as literals (valid, bigger)
@@ -844,13 +867,12 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
 
 // (the three steps as device functions: a call of a few blocks - the streaming API's one block per call - runs them in ONE launch,
 // k_layout_small below; each of these launches costs ~5 us of an otherwise idle GPU there)
-__device__ __forceinline__ void layout_block(const EncGeom& g, ChunkInfo* __restrict__ info, BlockOut* __restrict__ table, uint32_t* __restrict__ blk_bytes, uint32_t b)
+// one block of `blen` bytes on a wave: its `nch` chunks (ci[0..nch)) get their carries, their offsets within the payload and their flags
+// -> the block's size word (bit 31: stored raw).  (layout_block for one call's uniform geometry; the batch encoder's blocks come from its
+// own table, encode_batch.cuh)
+__device__ __forceinline__ uint32_t layout_block_chunks(ChunkInfo* __restrict__ ci, const uint32_t nch, const uint32_t blen)
 {
     const uint32_t lane = lane_id();
-    const uint64_t bstart = g.first_off + (uint64_t)b * g.block_size;
-    const uint32_t blen = (uint32_t)((bstart + g.block_size < g.src_size) ? g.block_size : g.src_size - bstart);
-    ChunkInfo* ci = info + (uint64_t)b * g.chunks_per_block;
-    const uint32_t nch = (blen + g.chunk_size - 1) / g.chunk_size;
     uint32_t carry_run = 0, total = 0;                      // literals pending from the groups before; payload bytes so far
     for (uint32_t c0 = 0; c0 < nch; c0 += WAVE) {
         const uint32_t c = c0 + lane;
@@ -877,11 +899,18 @@ __device__ __forceinline__ void layout_block(const EncGeom& g, ChunkInfo* __rest
     total += 1 + len_ext_bytes(carry_run) + carry_run;      // final literal-only sequence
     const bool raw = total >= blen;                         // LZ4F stores raw when it does not fit blockSize-1
     if (raw) for (uint32_t c = lane; c < nch; c += WAVE) ci[c].flags = ((c + 1 == nch) ? 2u : 0u) | 1u;
-    if (lane == 0) {
-        table[b].word = raw ? (blen | 0x80000000u) : total;
+    return raw ? (blen | 0x80000000u) : total;
+}
+__device__ __forceinline__ void layout_block(const EncGeom& g, ChunkInfo* __restrict__ info, BlockOut* __restrict__ table, uint32_t* __restrict__ blk_bytes, uint32_t b)
+{
+    const uint64_t bstart = g.first_off + (uint64_t)b * g.block_size;
+    const uint32_t blen = (uint32_t)((bstart + g.block_size < g.src_size) ? g.block_size : g.src_size - bstart);
+    const uint32_t word = layout_block_chunks(info + (uint64_t)b * g.chunks_per_block, (blen + g.chunk_size - 1) / g.chunk_size, blen);
+    if (lane_id() == 0) {
+        table[b].word = word;
         table[b].dst_off = bstart - g.first_off;
         table[b].dst_size = blen;
-        blk_bytes[b] = 4 + (raw ? blen : total) + 4 * g.block_checksum;
+        blk_bytes[b] = 4 + (word & 0x7FFFFFFFu) + 4 * g.block_checksum;
     }
 }
 template <int WAVES_PER_WG>
@@ -1113,25 +1142,17 @@ __device__ __forceinline__ void emit_len_ext(uint8_t* p, uint32_t v /* value min
 #ifndef E2_V2
 #define E2_V2 1               // pass E2, long literal runs: the records' arithmetic in the lanes, 64 records at a time (0: the round 2 loop, all of it scalar)
 #endif
-template <int WAVES_PER_WG, bool split = false>
-__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_emit_gather(const uint8_t* __restrict__ src, EncGeom g,
-                                                                   const ChunkInfo* __restrict__ info, const uint64_t* __restrict__ recs,
-                                                                   uint8_t* __restrict__ dst, const BlockOut* __restrict__ table, void* __restrict__ ix)
-{   // split (a call of few chunks - the streaming API's one block): the workgroup's waves share ONE chunk instead of taking one each.  Every wave
-    // walks all of the chunk's batches of 64 records for their sizes (two prefix sums), and emits its share: every nsub-th record of a batch of
-    // long literal runs, every nsub-th batch of short ones.  A 64 KiB block's emit is then a quarter as long as one wave's walk through it.
-    __shared__ uint4 s_gt[WAVES_PER_WG][2][64];
-    const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
-    const uint32_t chunk = uni(split ? blockIdx.x : blockIdx.x * WAVES_PER_WG + wave);
-    const uint32_t sub = split ? wave : 0u, nsub = split ? (uint32_t)WAVES_PER_WG : 1u;
-    if (chunk >= g.n_chunks) return;
-    const uint32_t blk = chunk / g.chunks_per_block, cib = chunk % g.chunks_per_block;
-    const uint64_t bstart = g.first_off + (uint64_t)blk * g.block_size;
-    const uint64_t bend_abs = (bstart + g.block_size < g.src_size) ? bstart + g.block_size : g.src_size;
-    const uint64_t cs_abs = bstart + (uint64_t)cib * g.chunk_size;
-    if (cs_abs >= bend_abs) return;
-    const uint64_t ce_abs = (cs_abs + g.chunk_size < bend_abs) ? cs_abs + g.chunk_size : bend_abs;
-    const ChunkInfo ci = info[chunk];
+// One chunk's emit, for a chunk whose place is resolved (EncPlace): k_emit_gather below computes it from the call's EncGeom, the batch
+// encoder loads it from its chunk table (encode_batch.cuh).  `rec`: the chunk's record list; ci.out_off: where its bytes go, from `dst`;
+// T0 / T1: 64 uint4 each, the wave's own, in LDS; sub / nsub: the wave's share of the chunk when split; ent..pay0: the sequence index's
+// entries for this chunk (ent null: none), blk its block's number there.
+template <bool split>
+__device__ __forceinline__ void emit_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, const ChunkInfo& ci, const uint64_t* __restrict__ rec,
+                                           uint8_t* __restrict__ dst, IxEntry* ent, const uint32_t ent_seq0, const uint32_t ent_last, const uint64_t pay0,
+                                           const uint32_t blk, uint4* T0, uint4* T1, const uint32_t sub, const uint32_t nsub)
+{
+    const uint32_t lane = lane_id();
+    const uint64_t bstart = pl.bstart, cs_abs = pl.cs_abs, ce_abs = pl.ce_abs;
     if (ci.flags & 4u) return;
     if (ci.flags & 1u) {                                   // stored block: this chunk's slice of it
         uint8_t* o = dst + ci.out_off;
@@ -1143,18 +1164,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_emit_gather(const uint8_t
         }
         return;
     }
-    const uint64_t* rec = rec_pool_of(recs, g) + (ci.nrec ? rec_offs(recs)[chunk] : 0u);
     uint64_t lp_off = cs_abs - ci.carry_in;                 // input offset of the pending literal run
     uint64_t o_off = ci.out_off;                            // frame offset of the next token
-    IxEntry* ent = nullptr; uint32_t ent_seq0 = 0, ent_last = 0; uint64_t pay0 = 0;
-    if (ix && ((const IxHeader*)ix)->magic == IX_MAGIC && ci.nrec) {
-        const IxChunk ck = ix_chunks(ix, g.n_blocks)[chunk];
-        ent = ix_entries_w(ix, g.n_blocks, g.chunks_per_block) + ix_blocks(ix)[blk].entry_base + (ck.ent_off & 0x7FFFFFFFu);
-        ent_seq0 = ck.seq_off; ent_last = ck.ent_off >> 31;
-        pay0 = table[blk].src_off;
-    }
-    uint4* T0 = s_gt[wave][0];
-    uint4* T1 = s_gt[wave][1];
     auto scan = [&](uint32_t v, uint32_t& total) -> uint32_t {              // exclusive prefix sum over the wave
         uint32_t incl = v;
 #pragma unroll
@@ -1419,6 +1430,34 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_emit_gather(const uint8_t
         if (lit >= 15) { emit_len_ext(o, lit - 15); o += len_ext_bytes(lit); }
         wave_copy_disjoint(o, src + lp_off, lit);
     }
+}
+
+template <int WAVES_PER_WG, bool split = false>
+__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_emit_gather(const uint8_t* __restrict__ src, EncGeom g,
+                                                                   const ChunkInfo* __restrict__ info, const uint64_t* __restrict__ recs,
+                                                                   uint8_t* __restrict__ dst, const BlockOut* __restrict__ table, void* __restrict__ ix)
+{   // split (a call of few chunks - the streaming API's one block): the workgroup's waves share ONE chunk instead of taking one each.  Every wave
+    // walks all of the chunk's batches of 64 records for their sizes (two prefix sums), and emits its share: every nsub-th record of a batch of
+    // long literal runs, every nsub-th batch of short ones.  A 64 KiB block's emit is then a quarter as long as one wave's walk through it.
+    __shared__ uint4 s_gt[WAVES_PER_WG][2][64];
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t chunk = uni(split ? blockIdx.x : blockIdx.x * WAVES_PER_WG + wave);
+    const uint32_t sub = split ? wave : 0u, nsub = split ? (uint32_t)WAVES_PER_WG : 1u;
+    if (chunk >= g.n_chunks) return;
+    EncPlace pl;
+    if (!enc_place(g, chunk, pl)) return;
+    const uint32_t blk = chunk / g.chunks_per_block;
+    const ChunkInfo ci = info[chunk];
+    const bool parsed = !(ci.flags & 5u);                  // (does not fit, or a stored block's slice: emit_chunk needs neither records nor index)
+    const uint64_t* rec = rec_pool_of(recs, g) + (parsed && ci.nrec ? rec_offs(recs)[chunk] : 0u);
+    IxEntry* ent = nullptr; uint32_t ent_seq0 = 0, ent_last = 0; uint64_t pay0 = 0;
+    if (parsed && ix && ((const IxHeader*)ix)->magic == IX_MAGIC && ci.nrec) {
+        const IxChunk ck = ix_chunks(ix, g.n_blocks)[chunk];
+        ent = ix_entries_w(ix, g.n_blocks, g.chunks_per_block) + ix_blocks(ix)[blk].entry_base + (ck.ent_off & 0x7FFFFFFFu);
+        ent_seq0 = ck.seq_off; ent_last = ck.ent_off >> 31;
+        pay0 = table[blk].src_off;
+    }
+    emit_chunk<split>(src, pl, ci, rec, dst, ent, ent_seq0, ent_last, pay0, blk, s_gt[wave][0], s_gt[wave][1], sub, nsub);
 }
 
 }  // namespace lz4f

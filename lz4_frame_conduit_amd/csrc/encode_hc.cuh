@@ -57,36 +57,21 @@ __device__ __forceinline__ uint32_t hc_len(uint32_t r) { return r ? (r >> 24) + 
 __device__ __forceinline__ uint32_t hc_off(uint32_t r) { return r & 0xFFFFu; }
 __device__ __forceinline__ uint32_t hc_back(uint32_t r) { return (r >> 16) & 0xFFu; }
 
-// grid: one workgroup of 64 * HC_WAVES threads per chunk; g.hc_attempts / g.hc_lazy from hc_level()
-__global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t* __restrict__ src, EncGeom g,
-                                                                  ChunkInfo* __restrict__ info, uint64_t* __restrict__ recs)
+// One chunk, one workgroup of 64 * HC_WAVES threads: the search itself, for a chunk whose place is resolved (EncPlace, encode.cuh) - by
+// k_find_matches_hc from the call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `rec`: the chunk's record
+// list (max_rec records of room; !rec_room: none, the chunk goes out as literals).  Every path ends behind a barrier or before the
+// first use of `sh`, so a workgroup may call this for one chunk after another.
+__device__ __forceinline__ void hc_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
+                                              uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
+                                              const uint32_t hc_attempts, const uint32_t lazy, HcShared& sh)
 {
-    __shared__ HcShared sh;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
-    const uint32_t chunk = blockIdx.x;
-    if (chunk >= g.n_chunks) return;
-
-    const uint32_t blk = chunk / g.chunks_per_block, cib = chunk % g.chunks_per_block;
-    const uint64_t bstart = g.first_off + (uint64_t)blk * g.block_size;
-    const uint64_t bend_abs = (bstart + g.block_size < g.src_size) ? bstart + g.block_size : g.src_size;
-    const uint64_t cs_abs = bstart + (uint64_t)cib * g.chunk_size;
-    ChunkInfo* ci = info + chunk;
-    if (cs_abs >= bend_abs) {               // chunk beyond a short last block
-        if (tid == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = 0; ci->body_size = 0; }
-        return;
-    }
-    const uint64_t ce_abs = (cs_abs + g.chunk_size < bend_abs) ? cs_abs + g.chunk_size : bend_abs;
-    const uint64_t low_abs = g.linked ? 0 : bstart;                  // matches may not start before this
+    const uint64_t bstart = pl.bstart, bend_abs = pl.bend_abs, cs_abs = pl.cs_abs, ce_abs = pl.ce_abs, low_abs = pl.low_abs;
     const uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
     const uint8_t* base = src + (cs_abs - back);                     // position 0 of the window
-    const uint8_t* rd_end = src + g.src_size;                        // nothing is read at or beyond this
+    const uint8_t* rd_end = src + pl.rd_end;                         // nothing is read at or beyond this
     const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
     const uint32_t bend = back + (uint32_t)(bend_abs - cs_abs);
-    // (a place of its own in the pool for this chunk's list: the engine sizes the pool for the worst case at these levels)
-    const uint64_t rec_at = (uint64_t)chunk * g.max_rec_per_chunk;
-    const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
-    uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
-    if (tid == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
 
     // a match may start at p iff cs <= p <= last_start, and may end at end_lim (as in encode_solo.cuh)
     const uint32_t blen = (uint32_t)(bend_abs - bstart), clen = ce - cs;
@@ -101,7 +86,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t
         if (tid == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = ce - cs; ci->body_size = 0; }
         return;
     }
-    const uint32_t attempts = g.hc_attempts ? g.hc_attempts : 1u, lazy = g.hc_lazy;
+    const uint32_t attempts = hc_attempts ? hc_attempts : 1u;
 
     for (uint32_t k = tid; k < (1u << HC_HASH_LOG) / 2; k += 64 * HC_WAVES) ((uint32_t*)sh.head)[k] = 0;
     __syncthreads();
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t
             const bool fin = it == nbatch + 1;
             const uint32_t known_end = fin ? 0xFFFFFFFFu : (it >= 1 ? (it - 1) * HC_T : 0u);
             const uint32_t res_end = last_start + 1;                     // results beyond: no match
-            while (p <= last_start && (fin || p + HC_LOOK < known_end) && nrec < g.max_rec_per_chunk) {
+            while (p <= last_start && (fin || p + HC_LOOK < known_end) && nrec < max_rec) {
                 const uint32_t w0 = p;
                 const uint32_t x = w0 + lane;
                 uint32_t v = 0;
@@ -166,7 +151,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t
                 // positions p in this window whose look-ahead is in the window and known
                 uint32_t wend = w0 + 64 - HC_LOOK;
                 if (!fin && known_end - HC_LOOK < wend) wend = known_end - HC_LOOK;
-                while (p < wend && nrec < g.max_rec_per_chunk) {
+                while (p < wend && nrec < max_rec) {
                     const uint64_t bal = __ballot(v != 0 && x >= p && x < wend);
                     if (!bal) { p = wend; break; }
                     p = w0 + (uint32_t)__builtin_ctzll(bal);
@@ -250,6 +235,28 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t
         __syncthreads();
     }
     if (tid == 0) { ci->nrec = nrec; ci->first_lit = first_lit; ci->tail_lit = ce - anchor; ci->body_size = body; }
+}
+
+// grid: one workgroup of 64 * HC_WAVES threads per chunk; g.hc_attempts / g.hc_lazy from hc_level()
+__global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t* __restrict__ src, EncGeom g,
+                                                                  ChunkInfo* __restrict__ info, uint64_t* __restrict__ recs)
+{
+    __shared__ HcShared sh;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t chunk = blockIdx.x;
+    if (chunk >= g.n_chunks) return;
+    ChunkInfo* ci = info + chunk;
+    EncPlace pl;
+    if (!enc_place(g, chunk, pl)) {         // chunk beyond a short last block
+        if (tid == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = 0; ci->body_size = 0; }
+        return;
+    }
+    // (a place of its own in the pool for this chunk's list: the engine sizes the pool for the worst case at these levels)
+    const uint64_t rec_at = (uint64_t)chunk * g.max_rec_per_chunk;
+    const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
+    uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
+    if (tid == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
+    hc_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, g.hc_attempts, g.hc_lazy, sh);
 }
 
 }  // namespace lz4f

@@ -24,40 +24,20 @@ constexpr uint32_t SOLO_SEED_STRIDE = 4, SOLO_SEED_DENSE = 1024;
 constexpr uint32_t SOLO_LONG_MATCH = 192;
 __device__ __forceinline__ uint32_t solo_slot(uint32_t hv) { return ((hv >> (32 - SOLO_HASH_LOG)) * 15u) >> 4; }
 
-// grid: one wave per chunk (blockDim = 64 * WAVES_PER_WG)
-template <int WAVES_PER_WG>
-__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const uint8_t* __restrict__ src, EncGeom g,
-                                                                         ChunkInfo* __restrict__ info, uint64_t* __restrict__ recs)
+// One chunk, one wave: the search itself, for a chunk whose place is resolved (EncPlace, encode.cuh) - by k_find_matches_solo from the
+// call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `table` / `tags`: the wave's own, in LDS; `rec`: the
+// chunk's record list (max_rec records of room; !rec_room: none, the chunk goes out as literals).
+__device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
+                                                uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
+                                                uint16_t* table, uint8_t* tags)
 {
-    __shared__ uint16_t s_table[WAVES_PER_WG][SOLO_HASH_SIZE];
-    __shared__ uint8_t s_tag[WAVES_PER_WG][SOLO_HASH_SIZE];     // 8 more hash bits per entry: filters false candidates without touching memory
-    const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
-    const uint32_t chunk = uni(blockIdx.x * WAVES_PER_WG + wave);
-    if (chunk >= g.n_chunks) return;
-    uint16_t* table = s_table[wave];
-    uint8_t* tags = s_tag[wave];
-
-    const uint32_t blk = chunk / g.chunks_per_block, cib = chunk % g.chunks_per_block;
-    const uint64_t bstart = g.first_off + (uint64_t)blk * g.block_size;
-    const uint64_t bend_abs = (bstart + g.block_size < g.src_size) ? bstart + g.block_size : g.src_size;
-    const uint64_t cs_abs = bstart + (uint64_t)cib * g.chunk_size;
-    ChunkInfo* ci = info + chunk;
-    if (cs_abs >= bend_abs) {               // chunk beyond a short last block
-        if (lane == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = 0; ci->body_size = 0; }
-        return;
-    }
-    const uint64_t ce_abs = (cs_abs + g.chunk_size < bend_abs) ? cs_abs + g.chunk_size : bend_abs;
-    const uint64_t low_abs = g.linked ? 0 : bstart;                  // matches may not start before this
+    const uint32_t lane = lane_id();
+    const uint64_t bstart = pl.bstart, bend_abs = pl.bend_abs, cs_abs = pl.cs_abs, ce_abs = pl.ce_abs, low_abs = pl.low_abs;
     const uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
     const uint8_t* base = src + (cs_abs - back);                     // position 0
-    const uint8_t* rd_end = src + g.src_size;                        // nothing is read at or beyond this
+    const uint8_t* rd_end = src + pl.rd_end;                         // nothing is read at or beyond this
     const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
     const uint32_t bend = back + (uint32_t)(bend_abs - cs_abs);
-    // (this chunk's list: a place of its own in the pool - the deterministic mode sizes the pool for the worst case, engine.hip)
-    const uint64_t rec_at = (uint64_t)chunk * g.max_rec_per_chunk;
-    const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
-    uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
-    if (lane == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
 
     // clear + pre-seed the table with the history in front of the chunk.  A 4096-entry table cannot hold
     // 64 KiB of positions, and later inserts win: seed the whole window sparsely (every SEED_STRIDE-th position,
@@ -259,7 +239,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const u
             // the bench input is 512 random bytes - strides 1..6 took three rounds of two steps to get across them, 4 and 5 take one; a match found a few bytes late gets
             // its start back from the backward extension)
             step = (SOLO_STEP_LONG > 1 && mlen >= SOLO_LONG_MATCH) ? (uint32_t)SOLO_STEP_LONG : 1u;
-            if (nrec >= g.max_rec_per_chunk) break;          // cannot happen with chunk/4+1 slots; belt and braces
+            if (nrec >= max_rec) break;          // cannot happen with chunk/4+1 slots; belt and braces
             // like the CPU encoder, also index ip-2; its bytes are requested together with the refilled stream queue
             const bool ins2 = ip >= 2 + cs && ip + 2 <= ce;
             const uint32_t q2 = ins2 ? ip - 2 : cs;
@@ -269,6 +249,30 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const u
         }
     }
     if (lane == 0) { ci->nrec = nrec; ci->first_lit = first_lit; ci->tail_lit = ce - anchor; ci->body_size = body; }
+}
+
+// grid: one wave per chunk (blockDim = 64 * WAVES_PER_WG)
+template <int WAVES_PER_WG>
+__global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const uint8_t* __restrict__ src, EncGeom g,
+                                                                         ChunkInfo* __restrict__ info, uint64_t* __restrict__ recs)
+{
+    __shared__ uint16_t s_table[WAVES_PER_WG][SOLO_HASH_SIZE];
+    __shared__ uint8_t s_tag[WAVES_PER_WG][SOLO_HASH_SIZE];     // 8 more hash bits per entry: filters false candidates without touching memory
+    const uint32_t wave = threadIdx.x >> 6, lane = lane_id();
+    const uint32_t chunk = uni(blockIdx.x * WAVES_PER_WG + wave);
+    if (chunk >= g.n_chunks) return;
+    ChunkInfo* ci = info + chunk;
+    EncPlace pl;
+    if (!enc_place(g, chunk, pl)) {         // chunk beyond a short last block
+        if (lane == 0) { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = 0; ci->body_size = 0; }
+        return;
+    }
+    // (this chunk's list: a place of its own in the pool - the deterministic mode sizes the pool for the worst case, engine.hip)
+    const uint64_t rec_at = (uint64_t)chunk * g.max_rec_per_chunk;
+    const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
+    uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
+    if (lane == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
+    solo_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, s_table[wave], s_tag[wave]);
 }
 
 // ------------------------------- pass S --------------------------------------------------------

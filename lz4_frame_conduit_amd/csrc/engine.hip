@@ -14,11 +14,13 @@
 #include "engine.hpp"
 #include "frame_dev.cuh"
 #include "decode_batch.cuh"
+#include "encode_batch.cuh"
 
 using namespace lz4f;
 
 static_assert(sizeof(ChunkInfo) == 32, "chunk info layout");
 static_assert(sizeof(BatchFrame) == 80 && sizeof(BatchBlk) == 40, "batch workspace layout");
+static_assert(sizeof(BcFrame) == 72 && sizeof(BcBlk) == 32 && sizeof(BcChunk) == 64, "batch encode workspace layout");
 
 namespace lz4f {
 
@@ -173,7 +175,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release(); bframes.release(); btable.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release(); cframes.release(); cblocks.release(); cchunks.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -1169,6 +1171,83 @@ size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames
     hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
                        e->sw.no_content_check ? 0u : 1u);
     if (hipGetLastError() != hipSuccess) { set_last_error("dev_decompressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    return 0;
+}
+
+size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                      void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                                      lz4f_mi355x_result* d_results)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
+    if (prefs) p = *prefs;
+    if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
+    const size_t bs = block_size_of(p.frameInfo.blockSizeID);
+    if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
+    if (n_frames == 0) return 0;
+    if (!d_src || !d_src_off || !d_dst || !d_dst_off || !d_results) { set_last_error("dev_compressFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    hipStream_t st = (hipStream_t)e->stream;
+    // what the frames have in common.  The header's FLG and BD as write_frame_header (frame_host.cpp) makes them - keep the two in
+    // step; the content size and the HC byte are each frame's own (k_bc_frames)
+    const LZ4F_frameInfo_t& f = p.frameInfo;
+    BcPrefs pf; memset(&pf, 0, sizeof(pf));
+    pf.block_size = (uint32_t)bs; pf.linked = f.blockMode == LZ4F_blockLinked; pf.block_checksum = f.blockChecksumFlag != 0;
+    pf.content_checksum = f.contentChecksumFlag != 0; pf.content_size = f.contentSize != 0; pf.dict_id = f.dictID;
+    pf.flg = (1u << 6) | (((unsigned)f.blockMode & 1u) << 5) | (((unsigned)f.blockChecksumFlag & 1u) << 4) | ((unsigned)(f.contentSize > 0) << 3) |
+             (((unsigned)f.contentChecksumFlag & 1u) << 2) | (unsigned)(f.dictID > 0);
+    pf.bd = ((unsigned)f.blockSizeID & 7u) << 4;
+    const bool hc = p.compressionLevel >= 3;                           // (the deterministic finders whatever the engine's switch says)
+    if (hc) {
+        const HcLevel hl = hc_level(p.compressionLevel);
+        pf.hc_attempts = e->sw.hc_attempts ? e->sw.hc_attempts : hl.attempts;
+        pf.hc_lazy = e->sw.hc_lazy ? e->sw.hc_lazy : hl.lazy;
+    }
+    // the tables and the pool, from the call's arguments alone: chunks are 64 KiB whatever the block size (pick_chunk_size), so spans
+    // that do not overlap have at most n_frames + srcBytes / 64 KiB chunks, no more blocks, and a record per 4 bytes + one per chunk
+    uint64_t cap = (uint64_t)n_frames + srcBytes / BC_CHUNK + 1;
+    if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+    const uint64_t rec_cap = (uint64_t)srcBytes / 4 + cap;
+    const size_t ctl_at = ((size_t)n_frames * sizeof(BcFrame) + 255) & ~(size_t)255;
+    const size_t recs_had = e->recs.cap;
+    if (e->cframes.ensure(ctl_at + 256) || e->cblocks.ensure((size_t)cap * sizeof(BcBlk)) || e->cchunks.ensure((size_t)cap * sizeof(BcChunk)) ||
+        e->info.ensure((size_t)cap * sizeof(ChunkInfo)) || e->recs.ensure(64 + (size_t)rec_cap * 8))
+        return make_err(LZ4F_ERROR_allocation_failed);
+    if (e->recs.cap != recs_had) e->recs_ctl_clean = nullptr;          // (a new pool: the single call's control words in its first 64 bytes are not zero yet)
+    BcFrame* frames = (BcFrame*)e->cframes.p;
+    uint32_t* ctl = (uint32_t*)((uint8_t*)e->cframes.p + ctl_at);
+    BcBlk* blocks = (BcBlk*)e->cblocks.p;
+    BcChunk* chunks = (BcChunk*)e->cchunks.p;
+    ChunkInfo* info = (ChunkInfo*)e->info.p;
+    // The pool lies behind the single call's control words, which stay as they are (recs_ctl_clean).  It does overwrite the single
+    // call's per-chunk list offsets (rec_offs) and `info`: both are a call's own - every single-call finder writes the offset and the
+    // ChunkInfo of every chunk it later reads before anything reads them, and nothing is carried from one call to the next.
+    uint64_t* pool = (uint64_t*)e->recs.p + 8;
+    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
+    constexpr int W = 4;
+    const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
+    const uint32_t g_ent = (uint32_t)std::min<uint64_t>((cap + W - 1) / W, BC_GRID);      // (a wave per entry, striding over the entries in use)
+    hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
+    hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
+    hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
+    if (hc)
+        hipLaunchKernelGGL(k_bc_find_hc, dim3((uint32_t)std::min<uint64_t>(cap, BC_GRID / 4)), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
+                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
+    else
+        hipLaunchKernelGGL(k_bc_find_solo, dim3((uint32_t)std::min<uint64_t>(cap, BC_GRID * 2)), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
+                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool);
+    hipLaunchKernelGGL((k_bc_layout<W>), dim3(g_ent), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
+    hipLaunchKernelGGL((k_bc_frames<W>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results);
+    hipLaunchKernelGGL((k_bc_emit<W>), dim3(g_ent), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
+                       (const ChunkInfo*)info, (const uint64_t*)pool);
+    if (pf.block_checksum) {
+        if (bs > (256u << 10))                                         // (few big blocks: the four-lane chain, as the single call's k_xxh32_blocks4)
+            hipLaunchKernelGGL((k_bc_blockck<W, true>), dim3(g_ent), dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+        else
+            hipLaunchKernelGGL((k_bc_blockck<W, false>), dim3(g_ent), dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+    }
+    if (pf.content_checksum) hipLaunchKernelGGL((k_bc_content<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames);
+    if (hipGetLastError() != hipSuccess) { set_last_error("dev_compressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
     return 0;
 }
 

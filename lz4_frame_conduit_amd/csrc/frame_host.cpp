@@ -91,6 +91,8 @@ size_t block_size_of(unsigned id)
     return (size_t)1 << (8 + 2 * id);
 }
 
+// (the batch encoder makes the same bytes on the device, a frame's own content size in them: k_bc_frames in encode_batch.cuh, with FLG and
+// BD from lz4f_mi355x_dev_compressFrames in engine.hip - a change here is a change there; tests/test_gpu_batch_compress.py compares the frames)
 size_t write_frame_header(uint8_t* dst, const LZ4F_preferences_t& p)
 {
     uint8_t* d = dst;

@@ -48,6 +48,21 @@ def _check_batch_args(src, src_off, dst, dst_off, results, rec_bytes: int) -> in
     return n
 
 
+def frame_windows(lengths, prefs: Preferences, gap: int = 0) -> "list[int]":
+    """Window offsets for Engine.compress_frames_async: n+1 cumulative offsets, window i being
+    lz4f_mi355x_compressFrameBound(lengths[i], prefs) bytes - which always suffice for input i's frame - plus `gap` spare bytes
+    behind it.  Host arithmetic only: no device is touched."""
+    if not isinstance(prefs, Preferences):
+        raise ValueError("prefs must be a Preferences")
+    if gap < 0:
+        raise ValueError("gap must not be negative")
+    L = _ffi.lib()
+    offs = [0]
+    for n in lengths:
+        offs.append(offs[-1] + _chk(L, L.lz4f_mi355x_compressFrameBound(int(n), ctypes.byref(prefs))) + gap)
+    return offs
+
+
 class Engine:
     def __init__(self, device: int = 0, stream: "torch.cuda.Stream | None" = None):
         self.L = _ffi.lib()
@@ -148,6 +163,20 @@ class Engine:
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
         _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
                                                             dst_off.data_ptr(), results.data_ptr()))
+
+    def compress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, prefs: Preferences,
+                              results: torch.Tensor):
+        """Enqueue a batch: input i is src[src_off[i]:src_off[i+1]], its frame is written at dst[dst_off[i]] and may use
+        dst[dst_off[i]:dst_off[i+1]] (this module's frame_windows gives offsets that always suffice).  One prefs for all frames; a non-zero
+        prefs.frameInfo.contentSize means every header declares its own input's length.  Tensors as for decompress_frames_async,
+        whose src / src_off the dst / dst_off of this call can be as they are.  Each frame is byte for byte what compress_async
+        writes for its input alone on an engine with set_deterministic(True); its size and verdict land in its record
+        (frame_results) - a frame whose window is too small fails alone.  Nothing is read back: no synchronisation."""
+        if not isinstance(prefs, Preferences):
+            raise ValueError("prefs must be a Preferences")
+        n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
+                                                          dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr()))
 
     def frame_results(self, results: torch.Tensor) -> "list[Result]":
         """Wait for the stream, then the records of a batch (status 0 = ok; otherwise the LZ4F error code of that frame)."""
