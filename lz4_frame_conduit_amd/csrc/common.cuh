@@ -8,7 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "records.hpp"      // status codes, BlockOut, ResultRec, the trailer's footer: what the host reads and writes too
+#include "records.hpp"      // status codes and the frame grammar (frame_format.hpp), BlockOut, ResultRec, the trailer's footer: what the host reads and writes too
 
 #define WAVE 64
 
@@ -34,9 +34,7 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v)
 // z = dst, w = match_len (0: last sequence).  Positions and lengths are < 2^23 because a block holds at most 4 MiB.
 struct SeqDesc { uint32_t x, y, z, w; };
 
-// ---- XXH32 constants ----
-constexpr uint32_t XP1 = 2654435761u, XP2 = 2246822519u, XP3 = 3266489917u, XP4 = 668265263u, XP5 = 374761393u;
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+// (XXH32's constants and rotl32: frame_format.hpp)
 
 // ---- wave-cooperative copies (all arguments wave-uniform) --------------------------------------
 // Non-overlapping copy of len bytes, any alignment.  16 B per lane (1 KiB per wave instruction);

@@ -301,7 +301,7 @@ void decompressBatched(const Await& await, const Yield& yield, size_t batchBytes
         }
         return buf.size() - off >= want;
     };
-    auto le32 = [&](size_t at) { const uint8_t* q = buf.data() + off + at; return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24); };
+    auto le32 = [&](size_t at) { return rd32le(buf.data() + off + at); };
     struct Ctx { const Yield* y; } ctx{&yield};
     auto to_yield = [](void* user, const void* data, size_t size) { (*((Ctx*)user)->y)(Slice{(const uint8_t*)data, size}); };
     struct Dec { lz4f_mi355x_fdec* d = nullptr; ~Dec() { lz4f_mi355x_fdec_free(d); } };
@@ -313,8 +313,7 @@ void decompressBatched(const Await& await, const Yield& yield, size_t batchBytes
             handleLz4Error(make_err(LZ4F_ERROR_frameHeader_incomplete));
         }
         any = true;
-        const uint32_t magic = le32(0);
-        if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {                        // skippable: magic, u32 size, payload - dropped as it arrives
+        if (is_skippable(le32(0))) {                                       // magic, u32 size, payload - dropped as it arrives
             if (!ensure(8)) handleLz4Error(make_err(LZ4F_ERROR_frameHeader_incomplete));
             size_t sz = le32(4);
             off += 8;
@@ -342,8 +341,8 @@ void decompressBatched(const Await& await, const Yield& yield, size_t batchBytes
         for (;;) {
             if (!ensure(run + 4)) throw std::runtime_error("lz4 decompress error: stream ended before EndMark");
             const uint32_t w = le32(run);
-            if (w == 0) break;
-            const size_t csz = w & 0x7FFFFFFFu;
+            if (is_endmark(w)) break;
+            const size_t csz = word_size(w);
             if (csz > max_block) handleLz4Error(make_err(LZ4F_ERROR_maxBlockSize_invalid));
             const size_t step = 4 + csz + crc;
             if (!ensure(run + step)) throw std::runtime_error("lz4 decompress error: stream ended before EndMark");

@@ -2,8 +2,8 @@
 //
 // The single-frame call reads the header back to the host to pick its plan; here every frame carries its own plan on the
 // device, and every kernel takes all frames at once:
-//   k_bf_head    a thread per frame: the span and the window checked against the buffers, then k_walk_frame's rules (skippable
-//                frames, header, size words, EndMark, content checksum word) -> a BatchFrame record and a block count
+//   k_bf_head    a thread per frame: the span and the window checked against the buffers, then the frame's grammar (frame_format.hpp:
+//                skippable frames, header, size words, EndMark, content checksum word) -> a BatchFrame record and a block count
 //   k_bf_place   one workgroup: exclusive scan of the counts -> each frame's slice of the block table.  Independent frames get one;
 //                the table is sized n_frames + dstBytes / 64 KiB + 1 by the host, so the workspace needs no read-back.  A walked frame
 //                has n_blocks <= window / 64 KiB + 1 (every block's provisional place, b * maxBlockSize, lies inside its window), so
@@ -41,9 +41,23 @@ struct BatchBlk {                           // block table entry (40 bytes)
     int32_t got, pad;                       // decoded bytes; -1 malformed, -2 does not fit
 };
 
-__device__ __forceinline__ uint32_t bf_rd32(const uint8_t* p)
+// The walk over a frame's size words, from `pos` (the first word) to behind the EndMark: each(w, csz, at) for block b with size
+// word w and csz payload bytes at f + at; what it returns, if not ST_OK, ends the walk and is the walk's status, as the grammar's
+// own errors are.  b: the blocks walked (on an error: the block it ended at).  UNI: a wave walks (the words are wave-uniform).
+template <bool UNI, typename F>
+__device__ __forceinline__ uint32_t bf_walk(const uint8_t* __restrict__ f, uint64_t cap, uint64_t& pos, uint32_t& b, uint32_t bs, uint32_t bck, F&& each)
 {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    for (b = 0;; b++) {
+        if (!frame_word_fits(cap - pos)) return ST_INCOMPLETE;
+        const uint32_t w = UNI ? uni(rd32le(f + pos)) : rd32le(f + pos);
+        pos += 4;
+        if (is_endmark(w)) return ST_OK;
+        uint32_t csz; uint64_t step;
+        if (const uint32_t st = frame_block_word(w, bs, bck, cap - pos, csz, step)) return st;
+        const uint64_t at = pos;
+        pos += step;                                              // (first: nothing of this hop is alive while `each` works)
+        if (const uint32_t st = each(w, csz, at)) return st;
+    }
 }
 
 // wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
@@ -77,13 +91,6 @@ __device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz
     return g == -1 ? -3 : g;
 }
 
-// k_finish_decode's verdict on a failed block
-__device__ __forceinline__ uint32_t bf_block_status(int32_t kind, uint64_t at, uint64_t win, uint32_t bs)
-{
-    const bool short_room = at <= win && win - at < bs && kind != -3;
-    return (kind == -2 || short_room) ? 11u /* dstMaxSize_tooSmall */ : 1u /* GENERIC */;
-}
-
 __global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src, uint64_t src_bytes, const uint64_t* __restrict__ soff,
                                                  uint64_t dst_bytes, const uint64_t* __restrict__ doff, uint32_t n_frames,
                                                  BatchFrame* __restrict__ frames, uint32_t* __restrict__ counts)
@@ -96,47 +103,36 @@ __global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src
     const uint64_t s1 = soff[i + 1], d1 = doff[i + 1];
     uint32_t count = 0;
     auto put = [&](uint32_t st) { r.status = st; frames[i] = r; counts[i] = count; };
-    if (r.src > s1 || s1 > src_bytes) { r.src = 0; r.dst = 0; return put(15); }         // srcPtr_wrong: nothing is read or written
-    if (r.dst > d1 || d1 > dst_bytes) { r.src = 0; r.dst = 0; return put(11); }         // dstMaxSize_tooSmall
+    if (r.src > s1 || s1 > src_bytes) { r.src = 0; r.dst = 0; return put(ST_SRCPTR); }      // nothing is read or written
+    if (r.dst > d1 || d1 > dst_bytes) { r.src = 0; r.dst = 0; return put(ST_DSTSMALL); }
     r.span = s1 - r.src; r.win = d1 - r.dst;
-    // k_walk_frame's rules, in its order (the single call's host-side header checks are the same checks)
+    // the single call's walk (k_walk_frame), check for check
     const uint8_t* f = src + r.src;
     const uint64_t cap = r.span, win = r.win;
-    if (cap < 7) return put(12);
-    const uint32_t magic = bf_rd32(f);
-    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {                                         // skippable frame: no output
-        if (cap < 8) return put(12);
-        const uint64_t sz = bf_rd32(f + 4);
-        if (cap < 8 + sz) return put(12);
-        r.consumed = 8 + sz; r.flags = 0x100;
-        return put(0);
+    if (cap < 7) return put(ST_INCOMPLETE);
+    if (is_skippable(rd32le(f))) {                                                      // no output
+        if (const uint32_t st = skippable_span(f, cap, r.consumed)) { r.consumed = 0; return put(st); }
+        r.flags = FLAG_SKIPPABLE;
+        return put(ST_OK);
     }
-    uint32_t hsize = 0, bs = 0, bck = 0, flg = 0; uint64_t content = 0;
-    if (const uint32_t st = walk_header(f, cap, hsize, bs, bck, flg, content)) return put(st);
-    r.flags = flg; r.bs = bs; r.hsize = hsize;
-    uint64_t tcap = win / bs + 2, by_src = cap / 5 + 2;                                  // the single call's table bound
+    FrameHead h;
+    if (const uint32_t st = frame_head_parse(f, cap, h)) return put(st);
+    r.flags = h.flg; r.bs = h.bs; r.hsize = h.hsize;
+    uint64_t tcap = win / h.bs + 2, by_src = cap / 5 + 2;                                // the single call's table bound
     if (by_src < tcap) tcap = by_src;
     if (tcap > 0x7FFFFFFFull) tcap = 0x7FFFFFFFull;
-    uint64_t pos = hsize, out = 0;
+    uint64_t pos = h.hsize, out = 0;
     uint32_t n = 0;
-    if (cap - pos < 4) return put(12);
-    for (;;) {
-        const uint32_t w = bf_rd32(f + pos);
-        pos += 4;
-        if (w == 0) break;
-        const uint32_t csz = w & 0x7FFFFFFFu;
-        if (csz > bs) return put(2);
-        if (cap - pos < (uint64_t)csz + 4 * bck) return put(12);
-        if (n >= tcap) return put(11);
-        if (out >= win) return put(11);
-        out += bs; pos += (uint64_t)csz + 4 * bck; n++;
-        if (cap - pos < 4) return put(12);
-    }
-    if ((flg >> 2) & 1) { if (cap - pos < 4) return put(12); pos += 4; }
-    r.n_blocks = n; r.consumed = pos; r.size = content;
-    const bool linked = !((flg >> 5) & 1);
-    if (!linked) count = n;                                                             // (<= win / BF_SHARE + 1: out < win held for every block)
-    put(0);
+    if (const uint32_t st = bf_walk<false>(f, cap, pos, n, h.bs, h.bck, [&](uint32_t, uint32_t, uint64_t) -> uint32_t {
+            if (n >= tcap || out >= win) return ST_DSTSMALL;
+            out += h.bs;
+            return ST_OK;
+        })) return put(st);
+    uint32_t tail;
+    if (const uint32_t st = frame_end(h.flg, cap - pos, tail)) return put(st);
+    r.n_blocks = n; r.consumed = pos + tail; r.size = h.content;
+    if (flg_indep(h.flg)) count = n;                                                    // (<= win / BF_SHARE + 1: out < win held for every block)
+    put(ST_OK);
 }
 
 // one workgroup: exclusive scan of the counts; a frame whose slice would end beyond the table (only windows that overlap can do
@@ -175,19 +171,18 @@ __global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ sr
     const BatchFrame r = frames[i];
     if (r.status != 0 || r.tbl_at == BF_NONE) return;
     const uint8_t* f = src + r.src;
-    const uint32_t bck = (r.flags >> 4) & 1;
     uint64_t pos = r.hsize;
-    for (uint32_t b = 0; b < r.n_blocks; b++) {                 // (k_bf_head walked this frame: every block is there)
-        const uint32_t w = bf_rd32(f + pos);
-        pos += 4;
+    uint32_t b;
+    bf_walk<false>(f, r.span, pos, b, r.bs, flg_bck(r.flags), [&](uint32_t w, uint32_t, uint64_t at) -> uint32_t {
+        if (b >= r.n_blocks) return ST_GENERIC;                 // (k_bf_head walked this frame: it has n_blocks of them)
         const uint64_t out = (uint64_t)b * r.bs;
         BatchBlk e;
-        e.src = r.src + pos; e.dst = r.dst + out; e.word = w;
+        e.src = r.src + at; e.dst = r.dst + out; e.word = w;
         e.room = (uint32_t)(r.win - out < r.bs ? r.win - out : r.bs);
         e.frame = i; e.ck = 0; e.got = 0; e.pad = 0;
         table[r.tbl_at + b] = e;
-        pos += (uint64_t)(w & 0x7FFFFFFFu) + 4 * bck;
-    }
+        return ST_OK;
+    });
 }
 
 // the grid is sized by the host's bound on the table, capped at BF_BLOCKS_GRID workgroups: the waves stride over the entries in
@@ -209,14 +204,14 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restri
         const uint64_t span_end = uni64(frames[fi].src + frames[fi].span);
         const uint32_t flg = uni(frames[fi].flags);
         const uint64_t so = uni64(e.src), dof = uni64(e.dst);
-        const uint32_t word = uni(e.word), room = uni(e.room), csz = word & 0x7FFFFFFFu;
+        const uint32_t word = uni(e.word), room = uni(e.room), csz = word_size(word);
         uint32_t ck = 0;
-        if ((flg >> 4) & 1) {
+        if (flg_bck(flg)) {
             const uint32_t h = wave_xxh32(src + so, csz);
-            ck = h != bf_rd32(src + so + csz) ? 1u : 0u;
+            ck = h != rd32le(src + so + csz) ? 1u : 0u;
         }
         int32_t got;
-        if (word >> 31) {
+        if (word_stored(word)) {
             if (csz > room) got = -2;
             else { wave_copy_disjoint(dst + dof, src + so, csz); got = (int32_t)csz; }
         } else {
@@ -228,30 +223,27 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restri
 
 // a wave per frame without a table slice: blocks in order
 template <int W>
-__global__ __launch_bounds__(64 * W) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
+__global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
 {
     const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
     if (i >= n_frames) return;
     const uint32_t status = uni(frames[i].status), n = uni(frames[i].n_blocks), tbl_at = uni(frames[i].tbl_at);
     if (status != 0 || n == 0 || tbl_at != BF_NONE) return;
     const uint64_t s0 = uni64(frames[i].src), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
-    const uint32_t flg = uni(frames[i].flags), bs = uni(frames[i].bs), bck = (flg >> 4) & 1;
-    const bool linked = !((flg >> 5) & 1);
+    const uint32_t flg = uni(frames[i].flags), bs = uni(frames[i].bs), bck = flg_bck(flg);
+    const bool linked = !flg_indep(flg);
     const uint8_t* f = src + s0;
     uint8_t* o = dst + d0;
     uint64_t pos = uni(frames[i].hsize), out = 0;
-    uint32_t st = 0, bad = BF_NONE;
-    for (uint32_t b = 0; b < n; b++) {
-        const uint32_t word = uni(bf_rd32(f + pos));
-        pos += 4;
-        const uint32_t csz = word & 0x7FFFFFFFu;
-        const uint8_t* in = f + pos;
-        pos += (uint64_t)csz + 4 * bck;
-        if (bck && wave_xxh32(in, csz) != bf_rd32(in + csz)) { st = 7; bad = b; break; }       // (the first failure of either kind decides)
+    uint32_t b;
+    // (k_bf_head has held every word of this frame to its span: no bound to hold them to again)
+    const uint32_t st = bf_walk<true>(f, ~0ull, pos, b, bs, bck, [&](uint32_t word, uint32_t csz, uint64_t src_at) -> uint32_t {
+        const uint8_t* in = f + src_at;
+        if (bck && wave_xxh32(in, csz) != rd32le(in + csz)) return ST_BLOCKCK;               // (the first failure of either kind decides)
         const uint64_t at = linked ? out : (uint64_t)b * bs;                                 // (independent: the provisional place, < win by the walk)
         const uint32_t room = (uint32_t)(win - at < bs ? win - at : bs);
         int32_t got;
-        if (word >> 31) {
+        if (word_stored(word)) {
             if (csz > room) got = -2;
             else { wave_copy_disjoint(o + at, in, csz); got = (int32_t)csz; }
         } else {
@@ -259,16 +251,16 @@ __global__ __launch_bounds__(64 * W) void k_bf_serial(const uint8_t* __restrict_
             if (got < 0 && b + 1 == n && csz && win % bs != 0 && win - at < bs)
                 got = bf_redo_tight(in, csz, o + at, bs, room, linked ? at : 0);
         }
-        if (got < 0) { st = bf_block_status(got, at, win, bs); bad = b; break; }
+        if (got < 0) return block_fail_status(got, at, win, bs);
         if (at != out) bf_move_down(o + out, o + at, (uint32_t)got);
         out += (uint32_t)got;
-    }
+        return ST_OK;
+    });
     if (lane_id() == 0) {
-        if (st) { frames[i].status = st; frames[i].first_bad = bad; }
+        if (st) { frames[i].status = st; frames[i].first_bad = b; }
         else {
-            const uint64_t declared = frames[i].size;
+            frames[i].status = frame_size_status(flg, frames[i].size, out);
             frames[i].size = out;
-            if (((flg >> 3) & 1) && declared != out) frames[i].status = 14;               // frameSize_wrong
         }
     }
 }
@@ -289,15 +281,15 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
     const uint64_t win = uni64(r.win);
     uint8_t* o = dst + uni64(r.dst);
     if (status == 0 && n == 0) {                                   // no blocks: an empty frame, or a skippable one
-        if (((flg >> 3) & 1) && size != 0) status = 14;
+        status = frame_size_status(flg, size, 0);
         size = 0;
     } else if (status == 0 && tbl_at != BF_NONE) {                 // the placed frames: k_finish_decode's verdict on the table slice
         const BatchBlk* t = table + tbl_at;
         // the tight last block first, as k_redo_tight_block runs before the verdict
         int32_t last = t[n - 1].got;
         const uint64_t last_at = (uint64_t)(n - 1) * bs;
-        const uint32_t lw = uni(t[n - 1].word), lcsz = lw & 0x7FFFFFFFu;
-        if (uni((uint32_t)last) >> 31 && !(lw >> 31) && lcsz && win % bs != 0 && win - last_at < bs)
+        const uint32_t lw = uni(t[n - 1].word), lcsz = word_size(lw);
+        if (uni((uint32_t)last) >> 31 && !word_stored(lw) && lcsz && win % bs != 0 && win - last_at < bs)
             last = bf_redo_tight(src + uni64(t[n - 1].src), lcsz, o + last_at, bs, uni(t[n - 1].room), 0);
         last = (int32_t)uni((uint32_t)last);
         uint32_t bad = BF_NONE, ck = BF_NONE; int32_t kind = 0; bool moves = false; uint64_t sum = 0;
@@ -314,8 +306,8 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
             for (int sft = 1; sft < 64; sft <<= 1) s += __shfl_xor(s, sft);
             sum += s;
         }
-        if (ck != BF_NONE && ck <= bad) { status = 7; first_bad = ck; }
-        else if (bad != BF_NONE) { status = bf_block_status(kind, (uint64_t)bad * bs, win, bs); first_bad = bad; }
+        if (ck != BF_NONE && ck <= bad) { status = ST_BLOCKCK; first_bad = ck; }
+        else if (bad != BF_NONE) { status = block_fail_status(kind, (uint64_t)bad * bs, win, bs); first_bad = bad; }
         else {
             if (moves) {                                           // a non-final block decoded short: pack the blocks (rare)
                 uint64_t out = 0;
@@ -326,15 +318,15 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
                     out += g;
                 }
             }
-            if (((flg >> 3) & 1) && size != sum) status = 14;
+            status = frame_size_status(flg, size, sum);
             size = sum;
         }
     }
     // the content checksum, behind the frame's EndMark (k_xxh32_content)
     const uint64_t consumed = uni64(r.consumed);
-    if (status == 0 && ((flg >> 2) & 1) && !(flg & 0x100) && content_check) {
+    if (status == 0 && flg_cck(flg) && !(flg & FLAG_SKIPPABLE) && content_check) {
         const uint32_t h = lane4_xxh32(o, size, park[wv]);
-        if (h != bf_rd32(src + r.src + consumed - 4)) status = 18;              // contentChecksum_invalid
+        if (h != rd32le(src + r.src + consumed - 4)) status = ST_CONTENTCK;
     }
     if (lane == 0) {
         ResultRec x;

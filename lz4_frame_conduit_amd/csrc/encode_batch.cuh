@@ -60,8 +60,7 @@ struct BcChunk {                            // chunk table entry (64 bytes): Enc
 };
 // what one batch's frames have in common (the call's preferences, resolved on the host)
 struct BcPrefs {
-    uint32_t block_size, linked, block_checksum, content_checksum, content_size, dict_id;
-    uint32_t flg, bd;                       // the header's FLG and BD bytes
+    uint32_t block_size, bsid, linked, block_checksum, content_checksum, content_size, dict_id;
     uint32_t hc_attempts, hc_lazy;          // levels 3-12 (0: level <= 2)
 };
 
@@ -88,12 +87,12 @@ __global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint6
     r.src = 0; r.len = 0; r.dst = 0; r.win = 0; r.rec_at = 0; r.fsize = 0;
     r.status = 0; r.n_blocks = 0; r.n_chunks = 0; r.blk_at = BC_NONE; r.chk_at = BC_NONE; r.pad = 0;
     const uint64_t s0 = soff[i], s1 = soff[i + 1], d0 = doff[i], d1 = doff[i + 1];
-    if (s0 > s1 || s1 > src_bytes) r.status = 15;                        // srcPtr_wrong: nothing is read or written
-    else if (d0 > d1 || d1 > dst_bytes) r.status = 11;                   // dstMaxSize_tooSmall
+    if (s0 > s1 || s1 > src_bytes) r.status = ST_SRCPTR;                 // nothing is read or written
+    else if (d0 > d1 || d1 > dst_bytes) r.status = ST_DSTSMALL;
     else {
         r.src = s0; r.len = s1 - s0; r.dst = d0; r.win = d1 - d0;
         const uint64_t nb = (r.len + pf.block_size - 1) / pf.block_size, full = r.len / BC_CHUNK, rem = r.len % BC_CHUNK;
-        if (nb > 0x7FFFFFFFull / (pf.block_size / BC_CHUNK)) r.status = 10;      // srcSize_tooLarge: more chunks than a 32-bit count holds (as the single call's plan)
+        if (nb > 0x7FFFFFFFull / (pf.block_size / BC_CHUNK)) r.status = ST_SRCLARGE;      // more chunks than a 32-bit count holds (as the single call's plan)
         else {
             r.n_blocks = (uint32_t)nb; r.n_chunks = (uint32_t)(full + (rem ? 1 : 0));
             r.rec_at = full * BC_CHUNK_RECS + (rem ? rem / 4 + 1 : 0);   // the worst case of every chunk: a record per 4 bytes, + 1
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(1024) void k_bc_place(BcFrame* __restrict__ frames,
         if (in && c[1]) {
             if (at[0] + c[0] <= blk_cap && at[1] + c[1] <= chk_cap && at[2] + c[2] <= rec_cap) {
                 frames[i].blk_at = (uint32_t)at[0]; frames[i].chk_at = (uint32_t)at[1]; frames[i].rec_at = at[2];
-            } else frames[i].status = 10;                                // srcSize_tooLarge
+            } else frames[i].status = ST_SRCLARGE;
         }
         __syncthreads();
         if (t == 1023) { carry_s[0] = at[0] + c[0]; carry_s[1] = at[1] + c[1]; carry_s[2] = at[2] + c[2]; }
@@ -242,15 +241,15 @@ __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __r
     const uint32_t lane = lane_id();
     const uint32_t status = uni(frames[i].status), nb = uni(frames[i].n_blocks), nc = uni(frames[i].n_chunks);
     const uint32_t blk_at = uni(frames[i].blk_at), chk_at = uni(frames[i].chk_at);
-    if (status != 0) {
-        if (lane == 0) results[i] = ResultRec{0ull, 0ull, status, 0u, 0xFFFFFFFFu, pf.flg | (LZ4F_MI355X_PATH_BATCH << 12)};
+    const uint64_t len = uni64(frames[i].len), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
+    auto flg_with = [&](bool csize) { return make_flg(!pf.linked, pf.block_checksum, csize, pf.content_checksum, pf.dict_id != 0); };
+    if (status != 0) {                                                    // (no frame: the call's FLG)
+        if (lane == 0) results[i] = ResultRec{0ull, 0ull, status, 0u, 0xFFFFFFFFu, flg_with(pf.content_size) | (LZ4F_MI355X_PATH_BATCH << 12)};
         return;
     }
-    const uint64_t len = uni64(frames[i].len), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
     // (an empty input's header declares no content size: a contentSize of 0 is "not given", to the single call too)
-    const bool csz = pf.content_size && len != 0;
-    const uint32_t flg = csz ? pf.flg | 8u : pf.flg & ~8u, flags = flg | (LZ4F_MI355X_PATH_BATCH << 12);
-    const uint32_t hs = 7u + (csz ? 8u : 0u) + (pf.dict_id ? 4u : 0u);
+    const uint32_t flg = flg_with(pf.content_size && len != 0), flags = flg | (LZ4F_MI355X_PATH_BATCH << 12);
+    const uint32_t hs = frame_head_size(flg);
     // the blocks, one behind the other behind the header
     uint64_t at = d0 + hs;
     for (uint32_t b0 = 0; b0 < nb; b0 += WAVE) {
@@ -265,25 +264,12 @@ __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __r
     const bool fits = fsize <= win;
     __threadfence();                                                      // (the lanes read each other's entries below)
     if (fits) {
-        if (lane == 0) {                                                  // the header: the device twin of write_frame_header (frame_host.cpp) - keep the two in step
+        if (lane == 0) {                                                  // the header: made in registers, then stored
             uint8_t h[20];
-            h[0] = 0x04; h[1] = 0x22; h[2] = 0x4D; h[3] = 0x18; h[4] = (uint8_t)flg; h[5] = (uint8_t)pf.bd;
-            uint32_t n = 6;
-            if (csz) { for (int k = 0; k < 8; k++) h[n + k] = (uint8_t)(len >> (8 * k)); n += 8; }
-            if (pf.dict_id) { for (int k = 0; k < 4; k++) h[n + k] = (uint8_t)(pf.dict_id >> (8 * k)); n += 4; }
-            uint32_t x = XP5 + (n - 4);                                   // XXH32 of the descriptor: fewer than 16 bytes
-            uint32_t k = 4;
-            for (; k + 4 <= n; k += 4) x = rotl32(x + ((uint32_t)h[k] | ((uint32_t)h[k + 1] << 8) | ((uint32_t)h[k + 2] << 16) | ((uint32_t)h[k + 3] << 24)) * XP3, 17) * XP4;
-            for (; k < n; k++) x = rotl32(x + h[k] * XP5, 11) * XP1;
-            x ^= x >> 15; x *= XP2; x ^= x >> 13; x *= XP3; x ^= x >> 16;
-            h[n++] = (uint8_t)(x >> 8);
+            const uint32_t n = frame_head_write(h, flg, pf.bsid, len, pf.dict_id);
             for (uint32_t q = 0; q < n; q++) dst[d0 + q] = h[q];
         }
-        for (uint32_t b = lane; b < nb; b += WAVE) {
-            const uint32_t w = blocks[blk_at + b].word;
-            uint8_t* q = dst + blocks[blk_at + b].out - 4;
-            q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
-        }
+        for (uint32_t b = lane; b < nb; b += WAVE) st32le(dst + blocks[blk_at + b].out - 4, blocks[blk_at + b].word);
         if (lane < 4) dst[at + lane] = 0;                                 // EndMark
     }
     // every chunk's place (layout_chunk)
@@ -336,7 +322,7 @@ __global__ __launch_bounds__(64 * W) void k_bc_blockck(uint8_t* dst, const BcFra
         const uint32_t n = uni(blocks[w].word) & 0x7FFFFFFFu;
         uint32_t h;
         if constexpr (LANE4) h = lane4_xxh32(dst + off, n, park[wv]); else h = wave_xxh32(dst + off, n);
-        if (lane_id() == 0) { uint8_t* c = dst + off + n; c[0] = (uint8_t)h; c[1] = (uint8_t)(h >> 8); c[2] = (uint8_t)(h >> 16); c[3] = (uint8_t)(h >> 24); }
+        if (lane_id() == 0) st32le(dst + off + n, h);
     }
 }
 
@@ -350,7 +336,7 @@ __global__ __launch_bounds__(64 * W) void k_bc_content(const uint8_t* __restrict
     if (i >= n_frames) return;
     if (uni(frames[i].status) != 0) return;
     const uint32_t h = lane4_xxh32(src + uni64(frames[i].src), uni64(frames[i].len), park[wv]);
-    if (lane_id() == 0) { uint8_t* c = dst + uni64(frames[i].dst) + uni64(frames[i].fsize) - 4; c[0] = (uint8_t)h; c[1] = (uint8_t)(h >> 8); c[2] = (uint8_t)(h >> 16); c[3] = (uint8_t)(h >> 24); }
+    if (lane_id() == 0) st32le(dst + uni64(frames[i].dst) + uni64(frames[i].fsize) - 4, h);
 }
 
 }  // namespace lz4f

@@ -1108,8 +1108,7 @@ size_t lz4f_mi355x_dev_decompressFrame(lz4f_mi355x_engine* e, void* d_dst, size_
     lz4f_mi355x_engine::DecompressJob j; memset(&j, 0, sizeof(j));
     j.d_frame = (const uint8_t*)d_frame; j.frame_cap = frameCapacity; j.d_dst = (uint8_t*)d_dst; j.dst_cap = dstCapacity; j.hist0 = 0;
     j.block_size = 65536; j.linked = false; j.block_checksum = false; j.max_blocks = 1;
-    const uint32_t magic = (uint32_t)hdr[0] | (hdr[1] << 8) | (hdr[2] << 16) | ((uint32_t)hdr[3] << 24);
-    if (magic == 0x184D2204u) {
+    if (rd32le(hdr) == FRAME_MAGIC) {
         ParsedHeader ph;
         size_t hs = parse_frame_header(hdr, peek, &ph);
         if (is_err(hs)) return hs;
@@ -1188,15 +1187,11 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     if (!d_src || !d_src_off || !d_dst || !d_dst_off || !d_results) { set_last_error("dev_compressFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
     if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
     hipStream_t st = (hipStream_t)e->stream;
-    // what the frames have in common.  The header's FLG and BD as write_frame_header (frame_host.cpp) makes them - keep the two in
-    // step; the content size and the HC byte are each frame's own (k_bc_frames)
+    // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
     BcPrefs pf; memset(&pf, 0, sizeof(pf));
-    pf.block_size = (uint32_t)bs; pf.linked = f.blockMode == LZ4F_blockLinked; pf.block_checksum = f.blockChecksumFlag != 0;
+    pf.block_size = (uint32_t)bs; pf.bsid = (uint32_t)f.blockSizeID; pf.linked = f.blockMode == LZ4F_blockLinked; pf.block_checksum = f.blockChecksumFlag != 0;
     pf.content_checksum = f.contentChecksumFlag != 0; pf.content_size = f.contentSize != 0; pf.dict_id = f.dictID;
-    pf.flg = (1u << 6) | (((unsigned)f.blockMode & 1u) << 5) | (((unsigned)f.blockChecksumFlag & 1u) << 4) | ((unsigned)(f.contentSize > 0) << 3) |
-             (((unsigned)f.contentChecksumFlag & 1u) << 2) | (unsigned)(f.dictID > 0);
-    pf.bd = ((unsigned)f.blockSizeID & 7u) << 4;
     const bool hc = p.compressionLevel >= 3;                           // (the deterministic finders whatever the engine's switch says)
     if (hc) {
         const HcLevel hl = hc_level(p.compressionLevel);

@@ -277,12 +277,12 @@ bool BlockList::add_blocks(const uint8_t* b, size_t n, uint64_t frame_off, bool 
 {
     size_t pos = 0;
     while (pos < n) {
-        if (n - pos < 4) return false;
-        const uint32_t w = (uint32_t)b[pos] | ((uint32_t)b[pos + 1] << 8) | ((uint32_t)b[pos + 2] << 16) | ((uint32_t)b[pos + 3] << 24);
-        const size_t step = 4 + (size_t)(w & 0x7FFFFFFFu) + (bck ? 4 : 0);
-        if (w == 0 || step > n - pos) return false;
+        if (!frame_word_fits(n - pos)) return false;
+        const uint32_t w = rd32le(b + pos);
+        uint32_t csz; uint64_t step;                              // (a run of blocks without its header: any block size passes)
+        if (is_endmark(w) || frame_block_word(w, 0x7FFFFFFFu, bck, n - pos - 4, csz, step)) return false;
         at.push_back(frame_off + pos);
-        pos += step;
+        pos += 4 + (size_t)step;
     }
     return true;
 }
@@ -300,7 +300,7 @@ void host_write_trailer(uint8_t* t, uint64_t F, const uint64_t* at, uint32_t n_b
     const uint64_t list_at = (F + 8 + 15) & ~(uint64_t)15, n_list = ((uint64_t)n_blocks + 1) & ~1ull, ix_at = list_at + n_list * 8;
     const uint64_t total = ix_at + sizeof(TrailerFoot) - F;
     const uint32_t sz = (uint32_t)(total - 8);
-    t[0] = 0x5E; t[1] = 0x2A; t[2] = 0x4D; t[3] = 0x18; t[4] = (uint8_t)sz; t[5] = (uint8_t)(sz >> 8); t[6] = (uint8_t)(sz >> 16); t[7] = (uint8_t)(sz >> 24);
+    st32le(t, TR_MAGIC); st32le(t + 4, sz);
     memset(t + 8, 0, (size_t)(list_at - F - 8));
     for (uint64_t i = 0; i < n_list; i++) { const uint64_t v = i < n_blocks ? at[i] : 0; memcpy(t + (list_at - F) + i * 8, &v, 8); }
     const TrailerFoot f{0u, 0u, 0u, 0u, TR_FOOT, n_blocks, total};

@@ -98,11 +98,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks(uint8_t* fra
     const uint32_t h = wave_xxh32(frame + off, len);
     if (lane_id() == 0) {
         uint8_t* c = frame + off + len;
-        if (mode == 0) { c[0] = (uint8_t)h; c[1] = (uint8_t)(h >> 8); c[2] = (uint8_t)(h >> 16); c[3] = (uint8_t)(h >> 24); }
-        else {
-            const uint32_t stored = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
-            if (stored != h) atomicMin(bad, b);
-        }
+        if (mode == 0) st32le(c, h);
+        else if (rd32le(c) != h) atomicMin(bad, b);
     }
 }
 
@@ -195,11 +192,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks4(uint8_t* fr
     const uint32_t h = lane4_xxh32(frame + off, len, park[wv]);
     if (lane_id() == 0) {
         uint8_t* c = frame + off + len;
-        if (mode == 0) { c[0] = (uint8_t)h; c[1] = (uint8_t)(h >> 8); c[2] = (uint8_t)(h >> 16); c[3] = (uint8_t)(h >> 24); }
-        else {
-            const uint32_t stored = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
-            if (stored != h) atomicMin(bad, b);
-        }
+        if (mode == 0) st32le(c, h);
+        else if (rd32le(c) != h) atomicMin(bad, b);
     }
 }
 
@@ -209,38 +203,22 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks4(uint8_t* fr
 // reference's conduit (Conduit.hsc:205) leave it off.
 //   mode 0 (compress): `data` is the input; the word goes to the frame's last 4 bytes (res->size counts them already).
 //   mode 1 (decompress): `data` is the decoded output, res->size its length; the stored word is the 4 bytes in front of
-//                        res->consumed; a mismatch sets ERROR_contentChecksum_invalid (18).
+//                        res->consumed; a mismatch sets ERROR_contentChecksum_invalid.
 __global__ __launch_bounds__(64) void k_xxh32_content(const uint8_t* __restrict__ data, uint64_t data_len, uint8_t* frame, ResultRec* __restrict__ res, uint32_t mode)
 {
     __shared__ __attribute__((aligned(16))) uint32_t park[XXH_PARK / 4];
     if (res->status != ST_OK) return;
-    if (mode == 1 && !((res->flags >> 2) & 1)) return;                 // (the frame has none)
+    if (mode == 1 && !flg_cck(res->flags)) return;                     // (the frame has none)
     const uint64_t len = mode == 0 ? data_len : res->size;
     const uint32_t h = lane4_xxh32(data, len, park);
     if (threadIdx.x == 0) {
         uint8_t* c = frame + (mode == 0 ? res->size : res->consumed) - 4;
-        if (mode == 0) { c[0] = (uint8_t)h; c[1] = (uint8_t)(h >> 8); c[2] = (uint8_t)(h >> 16); c[3] = (uint8_t)(h >> 24); }
-        else {
-            const uint32_t stored = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
-            if (stored != h) res->status = 18;                         // contentChecksum_invalid
-        }
+        if (mode == 0) st32le(c, h);
+        else if (rd32le(c) != h) res->status = ST_CONTENTCK;
     }
 }
 
 // ------------------------------- frame walk -----------------------------------------------------
-__device__ __forceinline__ uint32_t rd32_any(const uint8_t* p)
-{
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-__device__ uint32_t xxh32_small(const uint8_t* p, uint32_t len)   // len < 16: header descriptor
-{
-    uint32_t h = XP5 + len;
-    while (len >= 4) { h = rotl32(h + rd32_any(p) * XP3, 17) * XP4; p += 4; len -= 4; }
-    while (len > 0) { h = rotl32(h + (*p) * XP5, 11) * XP1; p++; len--; }
-    h ^= h >> 15; h *= XP2; h ^= h >> 13; h *= XP3; h ^= h >> 16;
-    return h;
-}
-
 // Single thread: the walk is a pointer chase (each size word's position depends on all earlier
 // ones).  Same validation order as the oracle's orc_decompress_frame.
 __global__ __launch_bounds__(64) void k_walk_frame(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint64_t dst_cap,
@@ -257,32 +235,16 @@ __global__ __launch_bounds__(64) void k_walk_frame(const uint8_t* __restrict__ f
     __shared__ uint32_t ra_sink[WAVE];
     const uint32_t sink0 = uni((uint32_t)(uintptr_t)(lptr_t)ra_sink);
     auto fail = [&](uint32_t st) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); r.status = st; *res = r; };      // (a read-ahead may be in flight)
-    if (frame_cap < 7) return fail(12);                              // frameHeader_incomplete
-    const uint32_t magic = rd32_any(frame);
-    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {                      // skippable frame: no output
-        if (frame_cap < 8) return fail(12);
-        const uint64_t sz = rd32_any(frame + 4);
-        if (frame_cap < 8 + sz) return fail(12);
-        r.consumed = 8 + sz; r.flags = 0x100; *res = r; return;
+    if (frame_cap < 7) return fail(ST_INCOMPLETE);
+    if (is_skippable(rd32le(frame))) {                               // no output
+        if (const uint32_t st = skippable_span(frame, frame_cap, r.consumed)) { r.consumed = 0; return fail(st); }
+        r.flags = FLAG_SKIPPABLE; *res = r; return;
     }
-    if (magic != 0x184D2204u) return fail(13);                       // frameType_unknown
-    const uint32_t flg = frame[4];
-    if ((flg >> 1) & 1) return fail(8);                              // reservedFlag_set
-    if (((flg >> 6) & 3) != 1) return fail(6);                       // headerVersion_wrong
-    const uint32_t hsize = 7 + (((flg >> 3) & 1) ? 8 : 0) + ((flg & 1) ? 4 : 0);
-    if (frame_cap < hsize) return fail(12);
-    const uint32_t bd = frame[5];
-    const uint32_t bsid = (bd >> 4) & 7;
-    if ((bd >> 7) & 1) return fail(8);
-    if (bsid < 4) return fail(ST_MAXBLOCK);
-    if (bd & 15) return fail(8);
-    if (((xxh32_small(frame + 4, hsize - 5) >> 8) & 0xFF) != frame[hsize - 1]) return fail(17);   // headerChecksum_invalid
+    FrameHead h;
+    if (const uint32_t st = frame_head_parse(frame, frame_cap, h)) return fail(st);
+    const uint32_t flg = h.flg, bs = h.bs, bck = h.bck;
     r.flags = flg;
-    const uint32_t bs = 1u << (8 + 2 * bsid);
-    const uint32_t bck = (flg >> 4) & 1;
-    uint64_t content = 0;
-    if ((flg >> 3) & 1) content = (uint64_t)rd32_any(frame + 6) | ((uint64_t)rd32_any(frame + 10) << 32);
-    uint64_t pos = hsize, out = 0;
+    uint64_t pos = h.hsize, out = 0;
     uint32_t n = 0;
     // Every hop is a dependent read that misses every cache: 0.66 us per block (4 GiB in 4 MiB blocks: 0.68 ms).  Where the size word
     // AFTER the next one will be is not known - but blocks of one stream are often of similar size, so the 64 lanes touch the 32 KiB
@@ -293,23 +255,22 @@ __global__ __launch_bounds__(64) void k_walk_frame(const uint8_t* __restrict__ f
     // read-ahead behind it, and the wait is for all but the youngest - which the compiler cannot be told, hence the asm.  The
     // read-ahead is a global_load_lds_dword: it lands in 256 bytes of LDS nobody reads, no register is written.  Two or four lines
     // per lane measured slower than one - 0.478 / 0.600 against 0.451 ms for the bench frame - and are gone.)
-    if (frame_cap - pos < 4) return fail(12);
+    if (!frame_word_fits(frame_cap - pos)) return fail(ST_INCOMPLETE);
     uint32_t w = *(const u32_ua*)(frame + pos);
     for (;;) {
         pos += 4;
-        if (w == 0) break;
-        const uint32_t csz = w & 0x7FFFFFFFu;
-        if (csz > bs) return fail(ST_MAXBLOCK);
-        if (frame_cap - pos < (uint64_t)csz + 4 * bck) return fail(12);
+        if (is_endmark(w)) break;
+        uint32_t csz; uint64_t step;
+        if (const uint32_t st = frame_block_word(w, bs, bck, frame_cap - pos, csz, step)) return fail(st);
         if (n >= table_cap) return fail(ST_DSTSMALL);
         if (out >= dst_cap) return fail(ST_DSTSMALL);
         table[n].src_off = pos; table[n].dst_off = out; table[n].word = w;
         table[n].dst_size = (uint32_t)((dst_cap - out < bs) ? dst_cap - out : bs);      // capacity; decode overwrites
         out += bs;                                                  // provisional: full blocks (fixed up after decode)
-        pos += (uint64_t)csz + 4 * bck;
+        pos += step;
         n++;
-        if (frame_cap - pos < 4) return fail(12);
-        const uint64_t guess = pos + 4 + csz + 4 * bck + (uint64_t)lane * 128u;          // lane 32 = the guess itself
+        if (!frame_word_fits(frame_cap - pos)) return fail(ST_INCOMPLETE);
+        const uint64_t guess = pos + 4 + step + (uint64_t)lane * 128u;                   // lane 32 = the guess itself
         const bool inside = guess >= 4096u + 4u && guess - 4096u + 4u <= frame_cap;
         const uint8_t* pw = frame + pos;
         const uint8_t* pa = inside ? frame + ((guess - 4096u) & ~(uint64_t)3) : pw;
@@ -318,8 +279,10 @@ __global__ __launch_bounds__(64) void k_walk_frame(const uint8_t* __restrict__ f
                      : "=&v"(w), "=&s"(keep) : "v"(pw), "v"(pa), "s"(sink0) : "memory");
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((flg >> 2) & 1) { if (frame_cap - pos < 4) return fail(12); pos += 4; }   // content checksum: verified behind the decode (k_xxh32_content)
-    r.n_blocks = n; r.consumed = pos; r.size = content;             // size = declared content size until decode fills it
+    uint32_t tail;                                                  // content checksum: verified behind the decode (k_xxh32_content)
+    if (const uint32_t st = frame_end(flg, frame_cap - pos, tail)) return fail(st);
+    pos += tail;
+    r.n_blocks = n; r.consumed = pos; r.size = h.content;           // size = declared content size until decode fills it
     *res = r;
 }
 
@@ -347,52 +310,26 @@ struct WalkState {                     // device scratch, zeroed per call
 };
 struct WalkChunk { uint32_t n; uint32_t off[WK_SLOTS]; uint32_t pad; };      // 128 bytes per 64 KiB of frame
 
-// header checks of k_walk_frame, shared (returns 0 and fills the fields, or the LZ4F error code)
-__device__ __forceinline__ uint32_t walk_header(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint32_t& hsize, uint32_t& bs, uint32_t& bck,
-                                                uint32_t& flg, uint64_t& content)
-{
-    if (frame_cap < 7) return 12;
-    const uint32_t magic = rd32_any(frame);
-    if (magic != 0x184D2204u) return 13;                              // (skippable frames: k_walk_frame)
-    flg = frame[4];
-    if ((flg >> 1) & 1) return 8;
-    if (((flg >> 6) & 3) != 1) return 6;
-    hsize = 7 + (((flg >> 3) & 1) ? 8 : 0) + ((flg & 1) ? 4 : 0);
-    if (frame_cap < hsize) return 12;
-    const uint32_t bd = frame[5];
-    const uint32_t bsid = (bd >> 4) & 7;
-    if ((bd >> 7) & 1) return 8;
-    if (bsid < 4) return ST_MAXBLOCK;
-    if (bd & 15) return 8;
-    if (((xxh32_small(frame + 4, hsize - 5) >> 8) & 0xFF) != frame[hsize - 1]) return 17;
-    bs = 1u << (8 + 2 * bsid);
-    bck = (flg >> 4) & 1;
-    content = 0;
-    if ((flg >> 3) & 1) content = (uint64_t)rd32_any(frame + 6) | ((uint64_t)rd32_any(frame + 10) << 32);
-    return 0;
-}
-
 __global__ void k_walk_head(const uint8_t* __restrict__ frame, uint64_t frame_cap, WalkState* __restrict__ ws, uint32_t preset_total = 0)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint32_t hsize = 0, bs = 0, bck = 0, flg = 0; uint64_t content = 0;
-    const uint32_t st = walk_header(frame, frame_cap, hsize, bs, bck, flg, content);
+    FrameHead h = {};
+    const uint32_t st = frame_head_parse(frame, frame_cap, h);         // (a skippable frame is no frame here: k_walk_frame)
     ws->done = 0; ws->overflow = 0; ws->total = preset_total; ws->first_end = 0xFFFFFFFFu; ws->first_break = 0xFFFFFFFFu;
-    ws->hsize = hsize; ws->bs = bs; ws->bck = bck; ws->flg = flg; ws->content = content;
-    ws->head_ok = st == 0 ? 1u : 0u;                                  // (a bad header: k_walk_frame gives the verdict)
+    ws->hsize = h.hsize; ws->bs = h.bs; ws->bck = h.bck; ws->flg = h.flg; ws->content = h.content;
+    ws->head_ok = st == ST_OK ? 1u : 0u;                              // (a bad header: k_walk_frame gives the verdict)
 }
 
 // does the word at `pos` look like a size word whose block fits the frame?  -> position of the next word
 __device__ __forceinline__ bool walk_step(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint32_t bs, uint32_t bck, uint64_t pos, uint64_t& next, bool& end)
 {
-    if (pos > frame_cap || frame_cap - pos < 4) return false;       // (positions out of a trailer are anybody's numbers)
+    if (pos > frame_cap || !frame_word_fits(frame_cap - pos)) return false;       // (positions out of a trailer are anybody's numbers)
     const uint32_t w = *(const u32_ua*)(frame + pos);
-    end = w == 0;
-    if (end) { next = pos + 4; return true; }
-    const uint32_t csz = w & 0x7FFFFFFFu;
-    if (csz > bs) return false;
-    next = pos + 4 + csz + 4 * bck;
-    return next + 4 <= frame_cap;                                     // (there is at least an EndMark behind every block)
+    end = is_endmark(w);
+    uint32_t csz; uint64_t step;
+    if (frame_block_word(w, bs, bck, frame_cap - pos - 4, csz, step)) return false;
+    next = pos + 4 + step;
+    return end || frame_word_fits(frame_cap - next);                  // (there is at least an EndMark behind every block)
 }
 
 __global__ __launch_bounds__(256) void k_walk_cand(const uint8_t* __restrict__ frame, uint64_t frame_cap, const WalkState* __restrict__ ws,
@@ -698,9 +635,11 @@ __global__ void k_walk_verdict(const uint8_t* __restrict__ frame, uint64_t frame
         if ((uint64_t)e * bs >= dst_cap) return;                      // (no room: k_walk_frame says so)
         n = e + 1;
         const uint64_t p = list[e];
-        pos = p + 4 + (*(const u32_ua*)(frame + p) & 0x7FFFFFFFu) + 4 * bck + 4;      // behind the EndMark
+        pos = p + 4 + word_size(*(const u32_ua*)(frame + p)) + 4 * bck + 4;           // behind the EndMark
     }
-    if ((flg >> 2) & 1) { if (frame_cap - pos < 4) return; pos += 4; }               // content checksum
+    uint32_t tail;                                                                   // content checksum
+    if (frame_end(flg, frame_cap - pos, tail)) return;
+    pos += tail;
     ResultRec r; r.size = ws->content; r.consumed = pos; r.status = ST_OK; r.n_blocks = n; r.first_bad_block = 0xFFFFFFFFu; r.flags = flg;
     *res = r;
     ws->done = 1;
@@ -737,7 +676,7 @@ __global__ void k_trailer_plan(uint8_t* __restrict__ dst, uint64_t dst_cap, Resu
         if (p.ok) {
             uint8_t* t = dst + F;
             const uint32_t sz = (uint32_t)(p.total - 8);
-            t[0] = 0x5E; t[1] = 0x2A; t[2] = 0x4D; t[3] = 0x18; t[4] = (uint8_t)sz; t[5] = (uint8_t)(sz >> 8); t[6] = (uint8_t)(sz >> 16); t[7] = (uint8_t)(sz >> 24);
+            st32le(t, TR_MAGIC); st32le(t + 4, sz);
             for (uint64_t q = F + 8; q < p.list_at; q++) dst[q] = 0;
             TrailerFoot f{with_ix ? hd->total_seqs : 0u, with_ix ? hd->total_entries : 0u, 0u, 0u, TR_FOOT, n_blocks, p.total};
             memcpy(dst + p.ix_at + p.ix_bytes, &f, sizeof(f));
@@ -984,11 +923,8 @@ __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __
         return;
     }
     if (first_bad != 0xFFFFFFFFu) {
-        // (a block that did not decode into LESS room than a whole block is "the output does not fit", as the oracle's frame decoder and
-        // the host paths call it: oracle/orc_lz4frame.c "room < bs ? dstMaxSize_tooSmall : GENERIC")
-        const uint64_t at_bad = table[first_bad].dst_off;
-        const bool short_room = at_bad <= dst_cap && dst_cap - at_bad < block_size && bad_kind != (uint32_t)-3;   // (-3: k_redo_tight_block gave it a whole block)
-        if (lane == 0) { res->status = (bad_kind == (uint32_t)-2 || short_room) ? ST_DSTSMALL : ST_GENERIC; res->first_bad_block = first_bad; }
+        // (-3: k_redo_tight_block gave it a whole block)
+        if (lane == 0) { res->status = block_fail_status((int32_t)bad_kind, table[first_bad].dst_off, dst_cap, block_size); res->first_bad_block = first_bad; }
         return;
     }
     // usual case, checked 64 blocks per step: every block already sits where its predecessors end (all blocks but
@@ -1028,7 +964,7 @@ __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __
     if (lane == 0) {
         const uint64_t declared = res->size;
         res->size = out;
-        if ((res->flags >> 3) & 1) { if (declared != out) res->status = 14; }   // frameSize_wrong
+        if (const uint32_t st = frame_size_status(res->flags, declared, out)) res->status = st;
     }
 }
 

@@ -41,17 +41,12 @@ const char* err_name(size_t v)
 }
 
 // ---------------- XXH32 on the host ----------------
-static const uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
-static inline uint32_t rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-static inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-static inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
-static inline void st32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-static inline uint32_t lane_step(uint32_t acc, uint32_t w) { return rotl(acc + w * P2, 13) * P1; }
+static inline uint32_t lane_step(uint32_t acc, uint32_t w) { return rotl32(acc + w * XP2, 13) * XP1; }
 
 void Xxh32State::reset(uint32_t seed)
 {
     total_len = 0; large = 0; memsize = 0;
-    v[0] = seed + P1 + P2; v[1] = seed + P2; v[2] = seed; v[3] = seed - P1;
+    v[0] = seed + XP1 + XP2; v[1] = seed + XP2; v[2] = seed; v[3] = seed - XP1;
 }
 void Xxh32State::update(const void* data, size_t len)
 {
@@ -62,20 +57,20 @@ void Xxh32State::update(const void* data, size_t len)
     if (memsize + len < 16) { memcpy(mem + memsize, p, len); memsize += (uint32_t)len; return; }
     if (memsize) {
         memcpy(mem + memsize, p, 16 - memsize);
-        for (int i = 0; i < 4; i++) v[i] = lane_step(v[i], le32(mem + 4 * i));
+        for (int i = 0; i < 4; i++) v[i] = lane_step(v[i], rd32le(mem + 4 * i));
         p += 16 - memsize; memsize = 0;
     }
-    for (; p + 16 <= end; p += 16) for (int i = 0; i < 4; i++) v[i] = lane_step(v[i], le32(p + 4 * i));
+    for (; p + 16 <= end; p += 16) for (int i = 0; i < 4; i++) v[i] = lane_step(v[i], rd32le(p + 4 * i));
     if (p < end) { memsize = (uint32_t)(end - p); memcpy(mem, p, memsize); }
 }
 uint32_t Xxh32State::digest() const
 {
-    uint32_t h = large ? rotl(v[0], 1) + rotl(v[1], 7) + rotl(v[2], 12) + rotl(v[3], 18) : v[2] + P5;
+    uint32_t h = large ? rotl32(v[0], 1) + rotl32(v[1], 7) + rotl32(v[2], 12) + rotl32(v[3], 18) : v[2] + XP5;
     h += total_len;
     const uint8_t* p = mem; uint32_t rem = memsize;
-    for (; rem >= 4; p += 4, rem -= 4) h = rotl(h + le32(p) * P3, 17) * P4;
-    for (; rem; p++, rem--) h = rotl(h + (*p) * P5, 11) * P1;
-    h ^= h >> 15; h *= P2; h ^= h >> 13; h *= P3; h ^= h >> 16;
+    for (; rem >= 4; p += 4, rem -= 4) h = rotl32(h + rd32le(p) * XP3, 17) * XP4;
+    for (; rem; p++, rem--) h = rotl32(h + (*p) * XP5, 11) * XP1;
+    h ^= h >> 15; h *= XP2; h ^= h >> 13; h *= XP3; h ^= h >> 16;
     return h;
 }
 uint32_t xxh32_host(const void* data, size_t len, uint32_t seed)
@@ -91,20 +86,11 @@ size_t block_size_of(unsigned id)
     return (size_t)1 << (8 + 2 * id);
 }
 
-// (the batch encoder makes the same bytes on the device, a frame's own content size in them: k_bc_frames in encode_batch.cuh, with FLG and
-// BD from lz4f_mi355x_dev_compressFrames in engine.hip - a change here is a change there; tests/test_gpu_batch_compress.py compares the frames)
 size_t write_frame_header(uint8_t* dst, const LZ4F_preferences_t& p)
 {
-    uint8_t* d = dst;
-    st32(d, 0x184D2204u); d += 4;
     const LZ4F_frameInfo_t& f = p.frameInfo;
-    *d++ = (uint8_t)((1u << 6) | (((unsigned)f.blockMode & 1u) << 5) | (((unsigned)f.blockChecksumFlag & 1u) << 4) |
-                     ((unsigned)(f.contentSize > 0) << 3) | (((unsigned)f.contentChecksumFlag & 1u) << 2) | (unsigned)(f.dictID > 0));
-    *d++ = (uint8_t)(((unsigned)f.blockSizeID & 7u) << 4);
-    if (f.contentSize) { st32(d, (uint32_t)f.contentSize); st32(d + 4, (uint32_t)(f.contentSize >> 32)); d += 8; }
-    if (f.dictID) { st32(d, f.dictID); d += 4; }
-    *d = (uint8_t)(xxh32_host(dst + 4, (size_t)(d - (dst + 4))) >> 8);
-    return (size_t)(d + 1 - dst);
+    const uint32_t flg = make_flg((unsigned)f.blockMode & 1u, (unsigned)f.blockChecksumFlag & 1u, f.contentSize > 0, (unsigned)f.contentChecksumFlag & 1u, f.dictID > 0);
+    return frame_head_write(dst, flg, (uint32_t)f.blockSizeID, f.contentSize, f.dictID);
 }
 
 size_t compress_bound_internal(size_t srcSize, const LZ4F_preferences_t* prefs, size_t alreadyBuffered)
@@ -129,28 +115,18 @@ size_t compress_bound_internal(size_t srcSize, const LZ4F_preferences_t* prefs, 
 size_t parse_frame_header(const uint8_t* src, size_t n, ParsedHeader* out)
 {
     memset(out, 0, sizeof(*out));
-    if (n < 7) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-    if (le32(src) != 0x184D2204u) return make_err(LZ4F_ERROR_frameType_unknown);
-    const unsigned flg = src[4];
-    if ((flg >> 1) & 1) return make_err(LZ4F_ERROR_reservedFlag_set);
-    if (((flg >> 6) & 3) != 1) return make_err(LZ4F_ERROR_headerVersion_wrong);
-    const size_t hs = 7 + (((flg >> 3) & 1) ? 8 : 0) + ((flg & 1) ? 4 : 0);
-    if (n < hs) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-    const unsigned bd = src[5], bsid = (bd >> 4) & 7;
-    if ((bd >> 7) & 1) return make_err(LZ4F_ERROR_reservedFlag_set);
-    if (bsid < 4) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    if (bd & 15) return make_err(LZ4F_ERROR_reservedFlag_set);
-    if ((uint8_t)(xxh32_host(src + 4, hs - 5) >> 8) != src[hs - 1]) return make_err(LZ4F_ERROR_headerChecksum_invalid);
-    out->info.blockMode = (LZ4F_blockMode_t)((flg >> 5) & 1);
-    out->info.blockChecksumFlag = (LZ4F_blockChecksum_t)((flg >> 4) & 1);
-    out->info.contentChecksumFlag = (LZ4F_contentChecksum_t)((flg >> 2) & 1);
-    out->info.blockSizeID = (LZ4F_blockSizeID_t)bsid;
+    FrameHead h;
+    if (const uint32_t st = frame_head_parse(src, n, h)) return make_err((int)st);      // (the status codes are LZ4F's error codes)
+    out->info.blockMode = (LZ4F_blockMode_t)flg_indep(h.flg);
+    out->info.blockChecksumFlag = (LZ4F_blockChecksum_t)flg_bck(h.flg);
+    out->info.contentChecksumFlag = (LZ4F_contentChecksum_t)flg_cck(h.flg);
+    out->info.blockSizeID = (LZ4F_blockSizeID_t)h.bsid;
     out->info.frameType = LZ4F_frame;
-    if ((flg >> 3) & 1) out->info.contentSize = le64(src + 6);
-    if (flg & 1) out->info.dictID = le32(src + hs - 5);
-    out->header_size = hs;
-    out->max_block = block_size_of(bsid);
-    return hs;
+    out->info.contentSize = h.content;
+    out->info.dictID = h.dict_id;
+    out->header_size = h.hsize;
+    out->max_block = h.bs;
+    return h.hsize;
 }
 
 }  // namespace lz4f
@@ -328,10 +304,10 @@ size_t LZ4F_compressEnd(LZ4F_cctx* c, void* dstBuffer, size_t dstCapacity, const
     if (is_err(f)) return f;
     dst += f; dstCapacity -= f;
     if (dstCapacity < 4) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-    st32(dst, 0); dst += 4;
+    st32le(dst, 0); dst += 4;
     if (c->prefs.frameInfo.contentChecksumFlag == LZ4F_contentChecksumEnabled) {
         if (dstCapacity < 8) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-        st32(dst, c->xxh.digest()); dst += 4;
+        st32le(dst, c->xxh.digest()); dst += 4;
     }
     c->stage = 0;
     if (c->prefs.frameInfo.contentSize && c->prefs.frameInfo.contentSize != c->total_in) return make_err(LZ4F_ERROR_frameSize_wrong);
@@ -388,26 +364,22 @@ static size_t decode_header(LZ4F_dctx_s* d, const uint8_t* src, size_t n)
 {
     if (n < 7) return make_err(LZ4F_ERROR_frameHeader_incomplete);
     memset(&d->info, 0, sizeof(d->info));
-    if ((le32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
+    if (is_skippable(rd32le(src))) {
         d->info.frameType = LZ4F_skippableFrame;
         if (src == d->header) { d->tmp_in_size = n; d->tmp_in_target = 8; d->stage = ds_storeSFrameSize; return n; }
         d->stage = ds_getSFrameSize;
         return 4;
     }
     ParsedHeader ph;
-    // only the first `needed` bytes are looked at; when fewer are present the stage machine gathers the rest
-    if (le32(src) != 0x184D2204u) return make_err(LZ4F_ERROR_frameType_unknown);
-    const unsigned flg = src[4];
-    if ((flg >> 1) & 1) return make_err(LZ4F_ERROR_reservedFlag_set);
-    if (((flg >> 6) & 3) != 1) return make_err(LZ4F_ERROR_headerVersion_wrong);
-    const size_t hs = 7 + (((flg >> 3) & 1) ? 8 : 0) + ((flg & 1) ? 4 : 0);
-    if (n < hs) {
+    const size_t r = parse_frame_header(src, n, &ph);
+    if (r == make_err(LZ4F_ERROR_frameHeader_incomplete)) {
+        // (n >= 7: magic, reserved bit and version have passed, the header is longer than what is here; the stage machine gathers the rest)
         if (src != d->header) memcpy(d->header, src, n);
-        d->tmp_in_size = n; d->tmp_in_target = hs; d->stage = ds_storeFrameHeader;
+        d->tmp_in_size = n; d->tmp_in_target = frame_head_size(src[4]); d->stage = ds_storeFrameHeader;
         return n;
     }
-    const size_t r = parse_frame_header(src, hs, &ph);
     if (is_err(r)) return r;
+    const size_t hs = ph.header_size;
     d->info = ph.info;
     d->max_block = ph.max_block;
     if (ph.info.contentSize) d->frame_remaining = ph.info.contentSize;
@@ -443,10 +415,9 @@ size_t LZ4F_headerSize(const void* src, size_t srcSize)
     if (!src) return make_err(LZ4F_ERROR_srcPtr_wrong);
     if (srcSize < 5) return make_err(LZ4F_ERROR_frameHeader_incomplete);
     const uint8_t* s = (const uint8_t*)src;
-    if ((le32(s) & 0xFFFFFFF0u) == 0x184D2A50u) return 8;
-    if (le32(s) != 0x184D2204u) return make_err(LZ4F_ERROR_frameType_unknown);
-    const unsigned flg = s[4];
-    return 7 + (((flg >> 3) & 1) ? 8 : 0) + ((flg & 1) ? 4 : 0);
+    if (is_skippable(rd32le(s))) return 8;
+    if (rd32le(s) != FRAME_MAGIC) return make_err(LZ4F_ERROR_frameType_unknown);
+    return frame_head_size(s[4]);
 }
 
 size_t LZ4F_getFrameInfo(LZ4F_dctx* d, LZ4F_frameInfo_t* frameInfoPtr, const void* srcBuffer, size_t* srcSizePtr)
@@ -527,12 +498,12 @@ size_t LZ4F_decompress(LZ4F_dctx* d, void* dstBuffer, size_t* dstSizePtr, const 
                 selected = d->tmp_in.data();
             }
             {
-                const uint32_t bh = le32(selected);
-                const size_t csz = bh & 0x7FFFFFFFu;
+                const uint32_t bh = rd32le(selected);
+                const size_t csz = word_size(bh);
                 const size_t crc = d->info.blockChecksumFlag ? 4 : 0;
-                if (bh == 0) { d->stage = ds_getSuffix; break; }
+                if (is_endmark(bh)) { d->stage = ds_getSuffix; break; }
                 if (csz > d->max_block) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-                if (bh & 0x80000000u) {
+                if (word_stored(bh)) {
                     d->tmp_in_target = csz;
                     if (d->info.blockChecksumFlag) d->block_xxh.reset(0);
                     d->stage = ds_copyDirect;
@@ -572,7 +543,7 @@ size_t LZ4F_decompress(LZ4F_dctx* d, void* dstBuffer, size_t* dstSizePtr, const 
                 if (d->tmp_in_size < 4) { again = false; break; }
                 crcSrc = d->header;
             }
-            if (le32(crcSrc) != d->block_xxh.digest()) return make_err(LZ4F_ERROR_blockChecksum_invalid);
+            if (rd32le(crcSrc) != d->block_xxh.digest()) return make_err(LZ4F_ERROR_blockChecksum_invalid);
             d->stage = ds_getBlockHeader;
             break;
         }
@@ -636,7 +607,7 @@ size_t LZ4F_decompress(LZ4F_dctx* d, void* dstBuffer, size_t* dstSizePtr, const 
                 if (d->tmp_in_size < 4) { hint = 4 - d->tmp_in_size; again = false; break; }
                 selected = d->tmp_in.data();
             }
-            if (le32(selected) != d->xxh.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
+            if (rd32le(selected) != d->xxh.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
             hint = 0; dctx_reset(d); again = false;
             break;
         case ds_getSFrameSize:
@@ -650,8 +621,8 @@ size_t LZ4F_decompress(LZ4F_dctx* d, void* dstBuffer, size_t* dstSizePtr, const 
                 if (d->tmp_in_size < d->tmp_in_target) { hint = d->tmp_in_target - d->tmp_in_size; again = false; break; }
                 selected = d->header + 4;
             }
-            d->info.contentSize = le32(selected);
-            d->tmp_in_target = le32(selected);
+            d->info.contentSize = rd32le(selected);
+            d->tmp_in_target = rd32le(selected);
             d->stage = ds_skipSkippable;
             break;
         case ds_skipSkippable: {
@@ -743,8 +714,8 @@ size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src,
     if (is_err(r)) return r;
     used += written;
     if (dstCapacity - used < (size_t)(want_cck ? 8 : 4)) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);
-    st32(d + used, 0); used += 4;
-    if (want_cck) { st32(d + used, cck); used += 4; }
+    st32le(d + used, 0); used += 4;
+    if (want_cck) { st32le(d + used, cck); used += 4; }
     return used;
 }
 
@@ -752,24 +723,22 @@ size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src,
 // (host work only: one 4-byte read per block)
 static size_t walk_for_block_list(const uint8_t* s, size_t n, BlockList* bl)
 {
-    if (n < 7) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-    ParsedHeader ph;
-    const size_t hs = parse_frame_header(s, n, &ph);                    // (a skippable frame is frameType_unknown here: nothing to list)
-    if (is_err(hs)) return hs;
-    const size_t crc = ph.info.blockChecksumFlag ? 4 : 0;
-    size_t pos = ph.header_size;
+    FrameHead h;
+    if (const uint32_t st = frame_head_parse(s, n, h)) return make_err((int)st);      // (a skippable frame is frameType_unknown here: nothing to list)
+    size_t pos = h.hsize;
     for (;;) {
-        if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        const uint32_t w = le32(s + pos);
-        if (w == 0) break;
-        const size_t csz = w & 0x7FFFFFFFu;
-        if (csz > ph.max_block) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-        if (n - pos - 4 < csz + crc) return make_err(LZ4F_ERROR_frameHeader_incomplete);
+        if (!frame_word_fits(n - pos)) return make_err(LZ4F_ERROR_frameHeader_incomplete);
+        const uint32_t w = rd32le(s + pos);
+        uint32_t csz; uint64_t step;
+        if (const uint32_t st = frame_block_word(w, h.bs, h.bck, n - pos - 4, csz, step)) return make_err((int)st);
+        if (is_endmark(w)) break;
         bl->at.push_back(pos);
-        pos += 4 + csz + crc;
+        pos += 4 + (size_t)step;
     }
     pos += 4;
-    if (ph.info.contentChecksumFlag) { if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete); pos += 4; }
+    uint32_t tail;
+    if (const uint32_t st = frame_end(h.flg, n - pos, tail)) return make_err((int)st);
+    pos += tail;
     if (pos != n) { set_last_error("block list: the frame ends at %zu, not at frameSize %zu", pos, n); return make_err(LZ4F_ERROR_frameSize_wrong); }
     return 0;
 }
@@ -806,9 +775,10 @@ static size_t decompress_frame_common(void* dst, size_t dstCapacity, const void*
     const uint8_t* s = (const uint8_t*)src;
     if (srcConsumed) *srcConsumed = 0;
     if (srcSize < 7) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-    if ((le32(s) & 0xFFFFFFF0u) == 0x184D2A50u) {
-        if (srcSize < 8 || srcSize < 8 + (size_t)le32(s + 4)) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        if (srcConsumed) *srcConsumed = 8 + (size_t)le32(s + 4);
+    if (is_skippable(rd32le(s))) {
+        uint64_t took = 0;
+        if (const uint32_t st = skippable_span(s, srcSize, took)) return make_err((int)st);
+        if (srcConsumed) *srcConsumed = (size_t)took;
         return 0;
     }
     ParsedHeader ph;
@@ -868,10 +838,10 @@ size_t lz4f_mi355x_fdec_end(lz4f_mi355x_fdec* d, const void* tail, size_t n)
     const uint8_t* t = (const uint8_t*)tail;
     const size_t need = 4 + (d->ph.info.contentChecksumFlag ? 4 : 0);
     if (!t || n < need) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-    if (le32(t) != 0) return make_err(LZ4F_ERROR_GENERIC);                        // not an EndMark
+    if (rd32le(t) != 0) return make_err(LZ4F_ERROR_GENERIC);                        // not an EndMark
     d->ended = true;
     if (d->ph.info.contentSize && d->ph.info.contentSize != d->carry.out_total) return make_err(LZ4F_ERROR_frameSize_wrong);
-    if (d->ph.info.contentChecksumFlag && le32(t + 4) != d->carry.cck.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
+    if (d->ph.info.contentChecksumFlag && rd32le(t + 4) != d->carry.cck.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
     return need;
 }
 void lz4f_mi355x_fdec_free(lz4f_mi355x_fdec* d) { delete d; }

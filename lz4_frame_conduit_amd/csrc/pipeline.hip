@@ -145,9 +145,8 @@ size_t pipe_decompress_frame(const uint8_t* s, size_t n, const ParsedHeader& ph,
                              const std::function<void(const uint8_t*, size_t)>* sink, size_t* decoded, size_t* consumed, FrameCarry* carry)
 {
     const size_t SLAB_SRC = (size_t)64 << 20, SLAB_DST = (size_t)192 << 20;
-    const size_t crc = ph.info.blockChecksumFlag ? 4 : 0;
+    const uint32_t bck = ph.info.blockChecksumFlag ? 1 : 0;
     const bool linked = ph.info.blockMode == LZ4F_blockLinked;
-    auto rd32 = [&](size_t at) { return (uint32_t)s[at] | ((uint32_t)s[at + 1] << 8) | ((uint32_t)s[at + 2] << 16) | ((uint32_t)s[at + 3] << 24); };
     // the host walks the size words (a read per block of memory it holds) and cuts the block list into slabs
     struct SlabD { size_t src_at, src_len, first, count; };
     std::vector<lz4f_mi355x_block> entries;
@@ -156,19 +155,18 @@ size_t pipe_decompress_frame(const uint8_t* s, size_t n, const ParsedHeader& ph,
     bool endmark = false;
     for (;;) {
         if (carry && pos == n) break;                           // (a batch ends with its last whole block)
-        if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        const uint32_t w = rd32(pos);
-        if (w == 0) { endmark = true; break; }
-        const size_t csz = w & 0x7FFFFFFFu;
-        if (csz > ph.max_block) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-        if (n - pos - 4 < csz + crc) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        if (slabs.empty() || (pos - slabs.back().src_at) + 4 + csz + crc > SLAB_SRC || (slabs.back().count + 1) * ph.max_block > SLAB_DST)
+        if (!frame_word_fits(n - pos)) return make_err(LZ4F_ERROR_frameHeader_incomplete);
+        const uint32_t w = rd32le(s + pos);
+        if (is_endmark(w)) { endmark = true; break; }
+        uint32_t csz; uint64_t step;
+        if (const uint32_t st = frame_block_word(w, (uint32_t)ph.max_block, bck, n - pos - 4, csz, step)) return make_err((int)st);
+        if (slabs.empty() || (pos - slabs.back().src_at) + 4 + step > SLAB_SRC || (slabs.back().count + 1) * ph.max_block > SLAB_DST)
             slabs.push_back(SlabD{pos, 0, entries.size(), 0});
         SlabD& sl = slabs.back();
         lz4f_mi355x_block e;
         e.src_off = pos + 4 - sl.src_at; e.dst_off = sl.count * ph.max_block; e.word = w; e.dst_size = (uint32_t)ph.max_block;
         entries.push_back(e);
-        pos += 4 + csz + crc;
+        pos += 4 + (size_t)step;
         sl.count++; sl.src_len = pos - sl.src_at;
     }
     if (endmark) pos += 4;
@@ -261,8 +259,8 @@ size_t pipe_decompress_frame(const uint8_t* s, size_t n, const ParsedHeader& ph,
     if (carry) { carry->out_total += out_total; *decoded = out_total; *consumed = pos; return 0; }
     if (ph.info.contentSize && ph.info.contentSize != out_total) return make_err(LZ4F_ERROR_frameSize_wrong);
     if (want_cck) {
-        if (n - pos < 4) return make_err(LZ4F_ERROR_frameHeader_incomplete);
-        if (rd32(pos) != cck.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
+        if (!frame_word_fits(n - pos)) return make_err(LZ4F_ERROR_frameHeader_incomplete);
+        if (rd32le(s + pos) != cck.digest()) return make_err(LZ4F_ERROR_contentChecksum_invalid);
         pos += 4;
     }
     *decoded = out_total; *consumed = pos;

@@ -3,11 +3,9 @@
 #include <stdint.h>
 
 #include "../../include/lz4f_mi355x.h"
+#include "frame_format.hpp"      // the status codes the kernels write, and the frame grammar
 
 namespace lz4f {
-
-// status codes written by kernels (values of LZ4F_errorCodes that can arise on the device)
-enum : uint32_t { ST_OK = 0, ST_GENERIC = 1, ST_MAXBLOCK = 2, ST_BLOCKCK = 7, ST_DSTSMALL = 11, ST_DECOMP = 16 };
 
 // ---- records shared with the host (include/lz4f_mi355x.h) ----
 struct BlockOut {            // mirrors lz4f_mi355x_block
@@ -22,7 +20,7 @@ static_assert(sizeof(BlockOut) == sizeof(lz4f_mi355x_block), "block table layout
 static_assert(sizeof(ResultRec) == sizeof(lz4f_mi355x_result), "result layout");
 
 // ---- the trailer behind a frame (frame_dev.cuh: the trailer; the host writes the same bytes for frames it assembles) ----
-constexpr uint32_t TR_MAGIC = 0x184D2A5Eu, TR_FOOT = 0x58495A4Cu;
+constexpr uint32_t TR_MAGIC = SKIP_MAGIC | 0xEu, TR_FOOT = 0x58495A4Cu;
 struct TrailerFoot { uint32_t total_seqs, total_entries, pad0, pad1, magic, n_blocks; uint64_t total; };      // 32 bytes; the last 16 identify it
 
 }  // namespace lz4f
