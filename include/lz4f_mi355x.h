@@ -401,6 +401,50 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, u
                                                         lz4f_mi355x_result* d_results);
 #define LZ4F_MI355X_PATH_BATCH 0x1000u   /* result.flags bits 12..: the frame went through the batch decoder (dev_decompressFrames), or was made by the batch encoder (dev_compressFrames) */
 
+/* BATCH MEASURE: what n_frames frames decode to, and the windows lz4f_mi355x_dev_decompressFrames needs for them, without decoding:
+ * "receive -> measure -> decode" on one stream, for frames whose headers declare no content size.  The conventions are the batch
+ * decoder's: frame i is the first frame in d_src[src_off[i] .. src_off[i+1]); d_src_off: n_frames + 1 uint64, DEVICE memory, 8-byte
+ * aligned; the data at any byte address; srcBytes the extent of d_src (a host value: it sizes the workspace and bounds every span);
+ * d_results: n_frames records, DEVICE memory.  Asynchronous on the engine's stream, no host synchronisation, no device->host copy,
+ * and a number of kernel launches that does not depend on n_frames.  Nothing is written except d_results, d_dst_off and the engine's
+ * workspace: there is no output buffer.  Spans that overlap are legal (they are only read).
+ *   - d_results[i]: size = the decoded bytes, counted from the block's tokens (not taken from the header); consumed, n_blocks and
+ *     flags & 0x1FF exactly what lz4f_mi355x_dev_decompressFrames reports for a frame it accepts (a skippable frame first in the span:
+ *     flag bit 8, size 0, consumed = that skippable frame); the path bits (flags >> 12) are LZ4F_MI355X_PATH_BATCH; first_bad_block
+ *     0xFFFFFFFF unless a block is malformed.  A frame that fails has size 0 (ERROR_frameSize_wrong: the measured size), and consumed
+ *     and n_blocks 0 when it fails before its blocks are looked at.
+ *   - The verdict is the batch decoder's wherever that needs no decoded byte: the span and the offsets (src_off[i] > src_off[i+1] or
+ *     a span ending past srcBytes: ERROR_srcPtr_wrong for that frame only), the header, the size words, truncation, the EndMark and
+ *     the content checksum's word, ERROR_frameSize_wrong where a declared content size differs from the measured one, and the
+ *     decoder's bound on a span's blocks (more than span bytes / 5 + 2 of them - only empty stored blocks, 4 bytes each, get there -
+ *     is ERROR_dstMaxSize_tooSmall to the batch decoder in every window, and so it is here, with W = 0); and every rule
+ *     of the block grammar that needs neither output bytes nor history, judged against room = maxBlockSize as liblz4 judges it: a
+ *     length run past the payload, the last-sequence rules, a match that ends fewer than 5 bytes before room, match-length bytes
+ *     reaching the payload's last 4 bytes, a block decoding past maxBlockSize, a compressed block with an empty payload; a stored
+ *     block decodes to its size.  Such a block gives ERROR_GENERIC with first_bad_block = the first of them.
+ *   - NOT LOOKED AT, by design: match offsets (0 < offset <= bytes in front, history included), block checksums and content
+ *     checksums.  The two offset bytes of a match are stepped over and nothing is hashed.  A frame that measure accepts may still be
+ *     rejected by the decode for one of these three reasons, and for no other.
+ *   - d_dst_off (n_frames + 1 uint64, DEVICE memory, 8-byte aligned; may be NULL): the exclusive prefix sum of W[i], the total in
+ *     d_dst_off[n_frames] - as it is, the d_dst_off of lz4f_mi355x_dev_decompressFrames for the same d_src / d_src_off, with any
+ *     dstBytes >= the total.  W[i] is the smallest window that call accepts for frame i; 0 for a frame measure rejects or that has
+ *     no blocks.  The batch decoder gives block b of a frame its provisional place at b * maxBlockSize and wants every place inside
+ *     the window (k_bf_head), an independent block decoded at its place and a linked one behind its predecessors, each in what is
+ *     left of the window up to maxBlockSize (k_bf_table, k_bf_serial), and judges a last block with less than a block of room
+ *     against a whole block (k_bf_finish); so, with n blocks of maxBlockSize bs and the last one decoding to g bytes,
+ *         independent blocks: W = (n - 1) * bs + max(g, 1)        linked blocks: W = max(size, (n - 1) * bs + 1).
+ *     W == size whenever every block but the last decodes to bs and the last one to at least a byte - the usual case; a frame
+ *     written with flushes (short inner blocks) needs W > size; W <= n * bs always.
+ *   - Workspace, from the call's arguments alone: 76 bytes per frame and 24 bytes per (n_frames + srcBytes / 256 + 1) block-table
+ *     entries - under 0.1 byte per source byte - grown as needed.  A block needs only 5 bytes of source, so frames of many tiny
+ *     blocks can overflow the table: the frames behind the overflow are measured a wave per frame, in order, with identical results.
+ *   - The call itself fails only on a null engine, a null pointer with n_frames > 0 (d_dst_off excepted), or a failed allocation.
+ *     n_frames == 0 returns 0 and enqueues nothing.
+ * Every block of every frame, linked ones included (a size needs no history), is measured by a wave of its own. */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                     const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                     uint64_t* d_dst_off, lz4f_mi355x_result* d_results);
+
 /* BATCH ENCODE: n_frames inputs, one frame each, in one call - the mirror image of lz4f_mi355x_dev_decompressFrames, with its conventions,
  * so that the output of one is the input of the other without the data visiting the host.  No host synchronisation, no device->host
  * copy, and a number of kernel launches that does not depend on n_frames.

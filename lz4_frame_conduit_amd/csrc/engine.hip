@@ -15,11 +15,13 @@
 #include "frame_dev.cuh"
 #include "decode_batch.cuh"
 #include "encode_batch.cuh"
+#include "measure_batch.cuh"
 
 using namespace lz4f;
 
 static_assert(sizeof(ChunkInfo) == 32, "chunk info layout");
 static_assert(sizeof(BatchFrame) == 80 && sizeof(BatchBlk) == 40, "batch workspace layout");
+static_assert(sizeof(MeasFrame) == 64 && sizeof(MeasBlk) == 24, "batch measure workspace layout");
 static_assert(sizeof(BcFrame) == 72 && sizeof(BcBlk) == 32 && sizeof(BcChunk) == 64, "batch encode workspace layout");
 
 namespace lz4f {
@@ -175,7 +177,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release(); bframes.release(); btable.release(); cframes.release(); cblocks.release(); cchunks.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); cframes.release(); cblocks.release(); cchunks.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -1170,6 +1172,41 @@ size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames
     hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
                        e->sw.no_content_check ? 0u : 1u);
     if (hipGetLastError() != hipSuccess) { set_last_error("dev_decompressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    return 0;
+}
+
+size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                     uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (!d_src || !d_src_off || !d_results) { set_last_error("dev_measureFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    hipStream_t st = (hipStream_t)e->stream;
+    if (e->aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)e->ev_join, 0)); e->aux_pending = false; }      // (an earlier call's forked work first)
+    // the block table: sized from the call's arguments alone; frames behind an overflow are measured a wave per frame
+    uint64_t table_cap = (uint64_t)n_frames + srcBytes / MF_SHARE + 1;
+    if (table_cap > 0xFFFFFFF0ull) table_cap = 0xFFFFFFF0ull;
+    const size_t wins_at = (size_t)n_frames * sizeof(MeasFrame), counts_at = wins_at + (size_t)n_frames * 8,
+                 ctl_at = (counts_at + (size_t)n_frames * 4 + 255) & ~(size_t)255;
+    if (e->mframes.ensure(ctl_at + 256) || e->mtable.ensure((size_t)table_cap * sizeof(MeasBlk))) return make_err(LZ4F_ERROR_allocation_failed);
+    MeasFrame* frames = (MeasFrame*)e->mframes.p;
+    uint64_t* wins = (uint64_t*)((uint8_t*)e->mframes.p + wins_at);
+    uint32_t* counts = (uint32_t*)((uint8_t*)e->mframes.p + counts_at);
+    uint32_t* ctl = (uint32_t*)((uint8_t*)e->mframes.p + ctl_at);
+    MeasBlk* table = (MeasBlk*)e->mtable.p;
+    const uint8_t* src = (const uint8_t*)d_src;
+    constexpr int W = 4;
+    const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
+    hipLaunchKernelGGL(k_mf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, n_frames, frames, counts);
+    hipLaunchKernelGGL(k_mf_place, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
+    hipLaunchKernelGGL(k_mf_table, dim3(g256), dim3(256), 0, st, src, (const MeasFrame*)frames, n_frames, table);
+    hipLaunchKernelGGL((k_mf_blocks<W>), dim3((uint32_t)std::min<uint64_t>((table_cap + W - 1) / W, MF_BLOCKS_GRID)), dim3(64 * W), 0, st, src, (const MeasFrame*)frames, n_frames,
+                       table, (const uint32_t*)ctl);
+    hipLaunchKernelGGL((k_mf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, frames, n_frames);
+    hipLaunchKernelGGL((k_mf_finish<W>), dim3(gw), dim3(64 * W), 0, st, (const MeasFrame*)frames, n_frames, (const MeasBlk*)table, (ResultRec*)d_results, wins);
+    if (d_dst_off) hipLaunchKernelGGL(k_mf_scan, dim3(1), dim3(1024), 0, st, (const uint64_t*)wins, n_frames, d_dst_off);
+    if (hipGetLastError() != hipSuccess) { set_last_error("dev_measureFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
     return 0;
 }
 

@@ -48,6 +48,34 @@ def _check_batch_args(src, src_off, dst, dst_off, results, rec_bytes: int) -> in
     return n
 
 
+def _check_measure_args(src, src_off, results, dst_off, rec_bytes: int) -> int:
+    """The tensors of a measure call (Engine.measure_frames_async) -> the number of frames; ValueError for what is wrong with them."""
+    named = [("src", src, torch.uint8), ("src_off", src_off, torch.int64), ("results", results, torch.uint8)]
+    if dst_off is not None:
+        named.append(("dst_off", dst_off, torch.int64))
+    for name, t, dt in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, not %s" % (name, dt, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous 1-d tensor" % name)
+    if src_off.numel() < 1:
+        raise ValueError("src_off must hold n+1 offsets (got %d)" % src_off.numel())
+    if dst_off is not None and dst_off.numel() != src_off.numel():
+        raise ValueError("src_off and dst_off must both hold n+1 offsets (got %d and %d)" % (src_off.numel(), dst_off.numel()))
+    n = src_off.numel() - 1
+    if n >= 1 << 32:
+        raise ValueError("too many frames for one call")
+    if results.numel() < n * rec_bytes:
+        raise ValueError("results must hold %d bytes for %d frames (got %d)" % (n * rec_bytes, n, results.numel()))
+    if not all(t.is_cuda for _, t, _ in named):
+        raise ValueError("the tensors of a batch must be in device memory")
+    if len({t.device for _, t, _ in named}) != 1:
+        raise ValueError("the tensors of a batch must be on one device")
+    return n
+
+
 def frame_windows(lengths, prefs: Preferences, gap: int = 0) -> "list[int]":
     """Window offsets for Engine.compress_frames_async: n+1 cumulative offsets, window i being
     lz4f_mi355x_compressFrameBound(lengths[i], prefs) bytes - which always suffice for input i's frame - plus `gap` spare bytes
@@ -163,6 +191,21 @@ class Engine:
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
         _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
                                                             dst_off.data_ptr(), results.data_ptr()))
+
+    def measure_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, results: torch.Tensor, dst_off: "torch.Tensor | None" = None):
+        """Enqueue a measurement: what frame i, the first frame in src[src_off[i]:src_off[i+1]], decodes to - its size from the tokens,
+        consumed, n_blocks and flags as decompress_frames_async reports them - lands in its record; nothing is decoded and nothing
+        else written.  dst_off (int64 device tensor of n+1 elements, optional) receives the offsets of windows that
+        decompress_frames_async accepts for these frames, the total in dst_off[n]: a frame of short flushed blocks needs more than its
+        size, a frame that fails gets an empty window.  Match offsets and checksums are not looked at: the decode may still reject a
+        frame for those.  Nothing is read back: no synchronisation.  The pipeline for frames of unknown size, on one stream:
+
+            eng.measure_frames_async(src, src_off, results, dst_off)
+            dst = torch.empty(capacity, dtype=torch.uint8, device=src.device)      # capacity >= dst_off[-1] (the one read-back, if there is no bound)
+            eng.decompress_frames_async(src, src_off, dst, dst_off, results)"""
+        n = _check_measure_args(src, src_off, results, dst_off, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_measureFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(),
+                                                         dst_off.data_ptr() if dst_off is not None else None, results.data_ptr()))
 
     def compress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, prefs: Preferences,
                               results: torch.Tensor):

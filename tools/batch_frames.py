@@ -7,6 +7,9 @@ For every case and input, a child process (its own time limit) compresses the fr
   batch  one decompress_frames_async call for all frames
   loop   one dev_decompressFrame per frame (each reads its header back to the host)
   one    the same blocks as ONE frame through dev_decompressFrame, where the framing allows it
+and measures them
+  measure  (the case "measure" only, which skips loop and one) one measure_frames_async call for all frames - sizes and decode
+           windows, nothing decoded - its records and offsets checked against the batch decode's
 timed with torch events on the engine's stream (best of a few runs; the loop: one run), every output checked against the input.
 Prints one JSON line per case and input: ms and GiB/s (of decoded bytes) for each way."""
 import argparse
@@ -25,6 +28,7 @@ CASES = {
     "4k_x65536": (65536, 4 << 10, 4, False, False, 0),     # (blocks shorter than the block size in the middle of a frame: not one frame of them)
     "1m_linked64k_x1024": (1024, 1 << 20, 4, True, True, 0),
     "4m_x256": (256, 4 << 20, 7, False, True, 0),
+    "measure": (4096, 64 << 10, 4, False, False, 0),        # the measure call beside the batch decode (no loop, no single frame)
     "64k_x64_in_4g": (64, 64 << 10, 4, False, False, 64 << 20),   # a small batch into a big destination buffer (windows 64 MiB apart)
 }
 
@@ -95,6 +99,19 @@ def child(case: str, data: str, runs: int) -> dict:
     assert all(r.status == 0 and r.size == fb for r in rr) and all((r.flags >> 12) == 0x1000 for r in rr), "batch: a frame failed"
     assert same(), "batch: output differs"
     out["batch"] = rate(ms)
+
+    if case == "measure":
+        # the measure call on the same frames: every size, and windows the batch decoder takes as they are
+        mres, moff = eng.new_results(n), torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        timed(lambda: eng.measure_frames_async(frames, so_t, mres, moff), 1)                   # (warm-up: the workspace)
+        ms = timed(lambda: eng.measure_frames_async(frames, so_t, mres, moff), runs)
+        mm = eng.frame_results(mres)
+        assert all(m.status == 0 and (m.size, m.consumed, m.n_blocks, m.flags) == (r.size, r.consumed, r.n_blocks, r.flags) for m, r in zip(mm, rr)), "measure: a record differs"
+        assert torch.equal(moff, torch.arange(0, n + 1, dtype=torch.int64, device=dev) * fb), "measure: windows differ from the sizes"
+        out["measure"] = rate(ms)
+        out["measure_over_batch"] = round(out["measure"]["ms"] / out["batch"]["ms"], 3)
+        eng.close()
+        return out
 
     def loop():
         for i in range(n):
