@@ -1,15 +1,15 @@
 // decode_batch.cuh -- many independent frames in one call (lz4f_mi355x_dev_decompressFrames), no host read in between.
 //
 // The single-frame call reads the header back to the host to pick its plan; here every frame carries its own plan on the
-// device, and every kernel takes all frames at once:
-//   k_bf_head    a thread per frame: the span and the window checked against the buffers, then the frame's grammar (frame_format.hpp:
-//                skippable frames, header, size words, EndMark, content checksum word) -> a BatchFrame record and a block count
-//   k_bf_place   one workgroup: exclusive scan of the counts -> each frame's slice of the block table.  Independent frames get one;
-//                the table is sized n_frames + dstBytes / 64 KiB + 1 by the host, so the workspace needs no read-back.  A walked frame
-//                has n_blocks <= window / 64 KiB + 1 (every block's provisional place, b * maxBlockSize, lies inside its window), so
-//                frames whose windows do not overlap always fit; only windows that overlap can overflow the table, and a frame
-//                behind the overflow is decoded by k_bf_serial instead - it still decodes as it would alone
-//   k_bf_table   a thread per placed frame walks its size words again and writes its entries
+// device, and every kernel takes all frames at once.  The scan, the record's core, the frame head, the walks, the slice check and
+// the slice verdict are batch_common.cuh's; what is this file's own:
+//   k_bf_head    a thread per frame: the span and the window checked against the buffers, then batch_frame_head held to the window
+//                (every block's provisional place, b * maxBlockSize, inside it) -> a BatchFrame record and a block count
+//   (k_batch_place<BatchFrame> then gives the independent frames their slices of the block table.  The host sizes the table
+//                n_frames + dstBytes / 64 KiB + 1, so the workspace needs no read-back.  A walked frame has n_blocks <=
+//                window / 64 KiB + 1, so frames whose windows do not overlap always fit; only windows that overlap can overflow
+//                the table, and a frame behind the overflow is decoded by k_bf_serial instead - it still decodes as it would alone)
+//   k_bf_table   a thread per placed frame writes its entries (batch_table_walk)
 //   k_bf_blocks  a wave per entry: block checksum, then the block decoded as k_decode_blocks does (wave_decode_block_win), its
 //                readable bound the frame's span end
 //   k_bf_serial  a wave per frame that has no table slice (linked frames; independent frames behind a table overflow): checksums
@@ -21,44 +21,20 @@
 #pragma once
 #include "common.cuh"
 #include "decode.cuh"
-#include "frame_dev.cuh"
+#include "batch_common.cuh"
 
 namespace lz4f {
 
-constexpr uint32_t BF_NONE = 0xFFFFFFFFu;
 constexpr uint32_t BF_SHARE = 65536;       // table entries per frame: window / BF_SHARE + 1
 
-struct BatchFrame {                         // per frame (device workspace, 80 bytes)
-    uint64_t src, span;                     // the frame's span in d_src
+struct BatchFrame : BatchCore {             // per frame (device workspace, 80 bytes); tbl_at == BF_NONE: k_bf_serial decodes it
     uint64_t dst, win;                      // its window in d_dst
-    uint64_t consumed, size;                // as the result record (size: the declared content size until the verdict)
-    uint32_t status, flags, n_blocks, first_bad;
-    uint32_t bs, hsize, tbl_at, pad;        // tbl_at: first table entry, BF_NONE: k_bf_serial decodes it
 };
 struct BatchBlk {                           // block table entry (40 bytes)
     uint64_t src, dst;                      // payload in d_src, block's place in d_dst (block b of its frame at b * maxBlockSize)
     uint32_t word, room, frame, ck;         // size word, bytes of the window from dst on (<= maxBlockSize), frame, checksum failed
     int32_t got, pad;                       // decoded bytes; -1 malformed, -2 does not fit
 };
-
-// The walk over a frame's size words, from `pos` (the first word) to behind the EndMark: each(w, csz, at) for block b with size
-// word w and csz payload bytes at f + at; what it returns, if not ST_OK, ends the walk and is the walk's status, as the grammar's
-// own errors are.  b: the blocks walked (on an error: the block it ended at).  UNI: a wave walks (the words are wave-uniform).
-template <bool UNI, typename F>
-__device__ __forceinline__ uint32_t bf_walk(const uint8_t* __restrict__ f, uint64_t cap, uint64_t& pos, uint32_t& b, uint32_t bs, uint32_t bck, F&& each)
-{
-    for (b = 0;; b++) {
-        if (!frame_word_fits(cap - pos)) return ST_INCOMPLETE;
-        const uint32_t w = UNI ? uni(rd32le(f + pos)) : rd32le(f + pos);
-        pos += 4;
-        if (is_endmark(w)) return ST_OK;
-        uint32_t csz; uint64_t step;
-        if (const uint32_t st = frame_block_word(w, bs, bck, cap - pos, csz, step)) return st;
-        const uint64_t at = pos;
-        pos += step;                                              // (first: nothing of this hop is alive while `each` works)
-        if (const uint32_t st = each(w, csz, at)) return st;
-    }
-}
 
 // wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
 // decodes but not into wlim
@@ -98,96 +74,42 @@ __global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_frames) return;
     BatchFrame r;
-    r.src = soff[i]; r.span = 0; r.dst = doff[i]; r.win = 0; r.consumed = 0; r.size = 0;
-    r.status = 0; r.flags = 0; r.n_blocks = 0; r.first_bad = BF_NONE; r.bs = 0; r.hsize = 0; r.tbl_at = BF_NONE; r.pad = 0;
+    batch_core_init(r, soff[i]);
+    r.dst = doff[i]; r.win = 0;
     const uint64_t s1 = soff[i + 1], d1 = doff[i + 1];
     uint32_t count = 0;
     auto put = [&](uint32_t st) { r.status = st; frames[i] = r; counts[i] = count; };
     if (r.src > s1 || s1 > src_bytes) { r.src = 0; r.dst = 0; return put(ST_SRCPTR); }      // nothing is read or written
     if (r.dst > d1 || d1 > dst_bytes) { r.src = 0; r.dst = 0; return put(ST_DSTSMALL); }
     r.span = s1 - r.src; r.win = d1 - r.dst;
-    // the single call's walk (k_walk_frame), check for check
-    const uint8_t* f = src + r.src;
     const uint64_t cap = r.span, win = r.win;
-    if (cap < 7) return put(ST_INCOMPLETE);
-    if (is_skippable(rd32le(f))) {                                                      // no output
-        if (const uint32_t st = skippable_span(f, cap, r.consumed)) { r.consumed = 0; return put(st); }
-        r.flags = FLAG_SKIPPABLE;
-        return put(ST_OK);
-    }
-    FrameHead h;
-    if (const uint32_t st = frame_head_parse(f, cap, h)) return put(st);
-    r.flags = h.flg; r.bs = h.bs; r.hsize = h.hsize;
-    uint64_t tcap = win / h.bs + 2, by_src = cap / 5 + 2;                                // the single call's table bound
-    if (by_src < tcap) tcap = by_src;
-    if (tcap > 0x7FFFFFFFull) tcap = 0x7FFFFFFFull;
-    uint64_t pos = h.hsize, out = 0;
-    uint32_t n = 0;
-    if (const uint32_t st = bf_walk<false>(f, cap, pos, n, h.bs, h.bck, [&](uint32_t, uint32_t, uint64_t) -> uint32_t {
-            if (n >= tcap || out >= win) return ST_DSTSMALL;
-            out += h.bs;
+    uint64_t out = 0;
+    const uint32_t st = batch_frame_head(src, r,
+        [&](uint32_t bs) { const uint64_t by_dst = win / bs + 2, by_src = cap / 5 + 2; return by_src < by_dst ? by_src : by_dst; },    // the single call's table bound
+        [&](uint32_t bs) -> uint32_t {
+            if (out >= win) return ST_DSTSMALL;
+            out += bs;
             return ST_OK;
-        })) return put(st);
-    uint32_t tail;
-    if (const uint32_t st = frame_end(h.flg, cap - pos, tail)) return put(st);
-    r.n_blocks = n; r.consumed = pos + tail; r.size = h.content;
-    if (flg_indep(h.flg)) count = n;                                                    // (<= win / BF_SHARE + 1: out < win held for every block)
-    put(ST_OK);
-}
-
-// one workgroup: exclusive scan of the counts; a frame whose slice would end beyond the table (only windows that overlap can do
-// that) is left to k_bf_serial.  ctl[0]: the entries in use
-__global__ __launch_bounds__(1024) void k_bf_place(const uint32_t* __restrict__ counts, uint32_t n_frames, BatchFrame* __restrict__ frames,
-                                                   uint64_t table_cap, uint32_t* __restrict__ ctl)
-{
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry_s;
-    const uint32_t t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_frames; base += 1024) {
-        const uint32_t i = base + t;
-        const uint64_t c = i < n_frames ? counts[i] : 0u;
-        uint64_t incl = c;
-        for (uint32_t d = 1; d < WAVE; d <<= 1) { const uint64_t x = __shfl_up(incl, d); if (lane >= d) incl += x; }
-        if (lane == WAVE - 1) wsum[wv] = incl;
-        __syncthreads();
-        uint64_t before = carry_s;
-        for (uint32_t k = 0; k < wv; k++) before += wsum[k];
-        const uint64_t at = before + incl - c;
-        if (c && at + c <= table_cap) frames[i].tbl_at = (uint32_t)at;
-        __syncthreads();
-        if (t == 1023) carry_s = before + incl;
-        __syncthreads();
-    }
-    if (t == 0) ctl[0] = (uint32_t)(carry_s < table_cap ? carry_s : table_cap);
+        });
+    if (st == ST_OK && flg_indep(r.flags)) count = r.n_blocks;                          // (<= win / BF_SHARE + 1: out < win held for every block)
+    put(st);
 }
 
 __global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ src, const BatchFrame* __restrict__ frames, uint32_t n_frames,
                                                   BatchBlk* __restrict__ table)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_frames) return;
-    const BatchFrame r = frames[i];
-    if (r.status != 0 || r.tbl_at == BF_NONE) return;
-    const uint8_t* f = src + r.src;
-    uint64_t pos = r.hsize;
-    uint32_t b;
-    bf_walk<false>(f, r.span, pos, b, r.bs, flg_bck(r.flags), [&](uint32_t w, uint32_t, uint64_t at) -> uint32_t {
-        if (b >= r.n_blocks) return ST_GENERIC;                 // (k_bf_head walked this frame: it has n_blocks of them)
+    batch_table_walk(src, frames, n_frames, [&](uint32_t i, const BatchFrame& r, uint32_t b, uint32_t w, uint64_t at) {
         const uint64_t out = (uint64_t)b * r.bs;
         BatchBlk e;
         e.src = r.src + at; e.dst = r.dst + out; e.word = w;
         e.room = (uint32_t)(r.win - out < r.bs ? r.win - out : r.bs);
         e.frame = i; e.ck = 0; e.got = 0; e.pad = 0;
         table[r.tbl_at + b] = e;
-        return ST_OK;
     });
 }
 
-// the grid is sized by the host's bound on the table, capped at BF_BLOCKS_GRID workgroups: the waves stride over the entries in
+// the grid is sized by the host's bound on the table, capped (engine.hip: BATCH_GRID): the waves stride over the entries in
 // use (ctl[0]), so a small batch into a big destination buffer does not launch a workgroup per 64 KiB of it
-constexpr uint32_t BF_BLOCKS_GRID = 8192;
 template <int W>
 __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
                                                         uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
@@ -199,8 +121,7 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restri
         const BatchBlk e = table[w];
         const uint32_t fi = uni(e.frame);
         if (fi >= n_frames) continue;
-        const uint32_t at = uni(frames[fi].tbl_at), nb = uni(frames[fi].n_blocks);
-        if (at == BF_NONE || w < at || w - at >= nb) continue;     // (an entry of this call: its frame's slice holds it)
+        if (!slice_holds(uni(frames[fi].tbl_at), uni(frames[fi].n_blocks), w)) continue;
         const uint64_t span_end = uni64(frames[fi].src + frames[fi].span);
         const uint32_t flg = uni(frames[fi].flags);
         const uint64_t so = uni64(e.src), dof = uni64(e.dst);
@@ -292,20 +213,15 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
         if (uni((uint32_t)last) >> 31 && !word_stored(lw) && lcsz && win % bs != 0 && win - last_at < bs)
             last = bf_redo_tight(src + uni64(t[n - 1].src), lcsz, o + last_at, bs, uni(t[n - 1].room), 0);
         last = (int32_t)uni((uint32_t)last);
-        uint32_t bad = BF_NONE, ck = BF_NONE; int32_t kind = 0; bool moves = false; uint64_t sum = 0;
-        for (uint32_t b0 = 0; b0 < n; b0 += WAVE) {
-            const uint32_t b = b0 + lane;
+        uint32_t bad, ck = BF_NONE; int32_t kind; bool moves = false; uint64_t sum;
+        slice_verdict(n, bad, kind, sum, [&](uint32_t b) -> int32_t {
             const bool in = b < n;
             const int32_t g = !in ? 0 : b + 1 == n ? last : t[b].got;
-            const uint64_t fm = __ballot(in && g < 0), cm = __ballot(in && t[b].ck);
-            if (fm && bad == BF_NONE) { bad = b0 + (uint32_t)__builtin_ctzll(fm); kind = (int32_t)__shfl((uint32_t)g, (int)(bad - b0)); }
-            if (cm && ck == BF_NONE) ck = b0 + (uint32_t)__builtin_ctzll(cm);
+            const uint64_t cm = __ballot(in && t[b].ck);
+            if (cm && ck == BF_NONE) ck = b - lane + (uint32_t)__builtin_ctzll(cm);
             if (__ballot(in && b + 1 < n && g != (int32_t)bs)) moves = true;
-            uint64_t s = in && g > 0 ? (uint64_t)g : 0u;
-#pragma unroll
-            for (int sft = 1; sft < 64; sft <<= 1) s += __shfl_xor(s, sft);
-            sum += s;
-        }
+            return g;
+        });
         if (ck != BF_NONE && ck <= bad) { status = ST_BLOCKCK; first_bad = ck; }
         else if (bad != BF_NONE) { status = block_fail_status(kind, (uint64_t)bad * bs, win, bs); first_bad = bad; }
         else {

@@ -1,7 +1,7 @@
 // encode_batch.cuh -- many independent inputs, one frame each, in one call (lz4f_mi355x_dev_compressFrames), no host read in between.
 //
-// The mirror image of decode_batch.cuh.  The single-frame call makes its plan on the host from one input's length; here every frame's
-// geometry is made on the device, and every kernel takes all frames at once:
+// The single-frame call makes its plan on the host from one input's length; here every frame's geometry is made on the device,
+// and every kernel takes all frames at once (the scan and the slice check are batch_common.cuh's, shared with the batch decoder):
 //   k_bc_head      a thread per frame: the span and the window checked against the buffers; blocks, chunks and records counted
 //   k_bc_place     one workgroup: exclusive scans of the three counts -> each frame's slice of the block table, of the chunk table
 //                  (and of the ChunkInfo array beside it) and of the record pool.  The host sizes them from the call's arguments alone:
@@ -32,14 +32,13 @@
 #include "encode.cuh"
 #include "encode_solo.cuh"
 #include "encode_hc.cuh"
-#include "frame_dev.cuh"
+#include "batch_common.cuh"
 
 namespace lz4f {
 
-constexpr uint32_t BC_NONE = 0xFFFFFFFFu;
+constexpr uint32_t BC_NONE = BF_NONE;
 constexpr uint32_t BC_CHUNK = 65536;        // pick_chunk_size() of every valid block size
 constexpr uint32_t BC_CHUNK_RECS = BC_CHUNK / 4 + 1;
-constexpr uint32_t BC_GRID = 8192;          // workgroups at most of the kernels that stride over a table
 
 struct BcFrame {                            // per frame (device workspace, 72 bytes)
     uint64_t src, len;                      // the input's span in d_src
@@ -64,18 +63,14 @@ struct BcPrefs {
     uint32_t hc_attempts, hc_lazy;          // levels 3-12 (0: level <= 2)
 };
 
-// an entry of this call: its frame is alive and its slice holds the entry (what a smaller batch before left in the table is not)
+// an entry of this call: its frame is alive and its slice holds the entry
 __device__ __forceinline__ bool bc_chunk_live(const BcFrame* __restrict__ frames, uint32_t n_frames, uint32_t fi, uint32_t w)
 {
-    if (fi >= n_frames) return false;
-    const uint32_t at = uni(frames[fi].chk_at), n = uni(frames[fi].n_chunks);
-    return uni(frames[fi].status) == 0 && at != BC_NONE && w >= at && w - at < n;
+    return fi < n_frames && uni(frames[fi].status) == 0 && slice_holds(uni(frames[fi].chk_at), uni(frames[fi].n_chunks), w);
 }
 __device__ __forceinline__ bool bc_blk_live(const BcFrame* __restrict__ frames, uint32_t n_frames, uint32_t fi, uint32_t w)
 {
-    if (fi >= n_frames) return false;
-    const uint32_t at = uni(frames[fi].blk_at), n = uni(frames[fi].n_blocks);
-    return uni(frames[fi].status) == 0 && at != BC_NONE && w >= at && w - at < n;
+    return fi < n_frames && uni(frames[fi].status) == 0 && slice_holds(uni(frames[fi].blk_at), uni(frames[fi].n_blocks), w);
 }
 
 __global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
@@ -109,39 +104,21 @@ __global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint6
 __global__ __launch_bounds__(1024) void k_bc_place(BcFrame* __restrict__ frames, uint32_t n_frames, uint64_t blk_cap, uint64_t chk_cap,
                                                    uint64_t rec_cap, uint32_t* __restrict__ ctl)
 {
-    __shared__ uint64_t wsum[3][16];
-    __shared__ uint64_t carry_s[3];
-    const uint32_t t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-    if (t < 3) carry_s[t] = 0;
-    __syncthreads();
+    __shared__ WgScan<3> s;
+    wg_scan_begin(s);
     for (uint32_t base = 0; base < n_frames; base += 1024) {
-        const uint32_t i = base + t;
+        const uint32_t i = base + threadIdx.x;
         const bool in = i < n_frames && frames[i].status == 0;
         const uint64_t c[3] = {in ? frames[i].n_blocks : 0u, in ? frames[i].n_chunks : 0u, in ? frames[i].rec_at : 0ull};
-        uint64_t incl[3] = {c[0], c[1], c[2]};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            for (uint32_t d = 1; d < WAVE; d <<= 1) { const uint64_t x = __shfl_up(incl[k], d); if (lane >= d) incl[k] += x; }
-            if (lane == WAVE - 1) wsum[k][wv] = incl[k];
-        }
-        __syncthreads();
         uint64_t at[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            uint64_t before = carry_s[k];
-            for (uint32_t q = 0; q < wv; q++) before += wsum[k][q];
-            at[k] = before + incl[k] - c[k];
-        }
+        wg_scan_tile(c, at, s);
         if (in && c[1]) {
             if (at[0] + c[0] <= blk_cap && at[1] + c[1] <= chk_cap && at[2] + c[2] <= rec_cap) {
                 frames[i].blk_at = (uint32_t)at[0]; frames[i].chk_at = (uint32_t)at[1]; frames[i].rec_at = at[2];
             } else frames[i].status = ST_SRCLARGE;
         }
-        __syncthreads();
-        if (t == 1023) { carry_s[0] = at[0] + c[0]; carry_s[1] = at[1] + c[1]; carry_s[2] = at[2] + c[2]; }
-        __syncthreads();
     }
-    if (t == 0) { ctl[0] = (uint32_t)(carry_s[1] < chk_cap ? carry_s[1] : chk_cap); ctl[1] = (uint32_t)(carry_s[0] < blk_cap ? carry_s[0] : blk_cap); }
+    if (threadIdx.x == 0) { ctl[0] = (uint32_t)(s.carry[1] < chk_cap ? s.carry[1] : chk_cap); ctl[1] = (uint32_t)(s.carry[0] < blk_cap ? s.carry[0] : blk_cap); }
 }
 
 // a wave per frame: its block entries and its chunk entries

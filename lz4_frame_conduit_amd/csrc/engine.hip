@@ -21,7 +21,7 @@ using namespace lz4f;
 
 static_assert(sizeof(ChunkInfo) == 32, "chunk info layout");
 static_assert(sizeof(BatchFrame) == 80 && sizeof(BatchBlk) == 40, "batch workspace layout");
-static_assert(sizeof(MeasFrame) == 64 && sizeof(MeasBlk) == 24, "batch measure workspace layout");
+static_assert(sizeof(BatchCore) == 64 && sizeof(MeasBlk) == 24, "batch measure workspace layout");
 static_assert(sizeof(BcFrame) == 72 && sizeof(BcBlk) == 32 && sizeof(BcChunk) == 64, "batch encode workspace layout");
 
 namespace lz4f {
@@ -960,6 +960,42 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
 
 // ------------------------------------------------------------------------------------------------
 // C ABI: engine + device-pointer entry points
+// ---- the batch calls: many frames, one call, no host read ----
+constexpr uint32_t BATCH_GRID = 8192;       // workgroups at most of a kernel that strides over a table's entries in use
+
+// what every batch call begins with, once its own argument checks are through: its pointers, the device, and the work an earlier
+// call left on the aux stream (aux_pending is set here only after launch_decompress's error path failed to join it)
+static size_t batch_begin(lz4f_mi355x_engine* e, const char* call, bool pointers_ok)
+{
+    if (!pointers_ok) { set_last_error("%s: null pointer", call); return make_err(LZ4F_ERROR_GENERIC); }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (e->aux_pending) { HIP_TRY(hipStreamWaitEvent((hipStream_t)e->stream, (hipEvent_t)e->ev_join, 0)); e->aux_pending = false; }
+    return 0;
+}
+static size_t batch_end(const char* call)
+{
+    if (hipGetLastError() != hipSuccess) { set_last_error("%s: launch failed", call); return make_err(LZ4F_ERROR_GENERIC); }
+    return 0;
+}
+// a table's entries, from the call's arguments alone (a slice's place is a 32-bit entry number)
+static uint64_t batch_table_cap(uint32_t n_frames, uint64_t shared)
+{
+    return std::min<uint64_t>((uint64_t)n_frames + shared + 1, 0xFFFFFFF0ull);
+}
+// the grid of a kernel that strides over up to `items` table entries, `per_wg` to a workgroup at a time
+static dim3 batch_grid(uint64_t items, uint32_t per_wg, uint32_t most = BATCH_GRID)
+{
+    return dim3((uint32_t)std::min<uint64_t>((items + per_wg - 1) / per_wg, most));
+}
+// a DevBuf carved into arrays: take() them in order, ensure(), then at()
+struct Carve {
+    DevBuf& buf;
+    size_t end = 0;
+    size_t take(size_t bytes, size_t align = 1) { const size_t at = (end + align - 1) & ~(align - 1); end = at + bytes; return at; }
+    int ensure() { return buf.ensure(end); }
+    template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
+};
+
 extern "C" {
 
 const char* lz4f_mi355x_last_error(void) { return lz4f::last_error(); }
@@ -1147,32 +1183,28 @@ size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     if (n_frames == 0) return 0;
-    if (!d_src || !d_src_off || !d_dst || !d_dst_off || !d_results) { set_last_error("dev_decompressFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
-    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results)) return r;
     hipStream_t st = (hipStream_t)e->stream;
-    if (e->aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)e->ev_join, 0)); e->aux_pending = false; }      // (an earlier call's forked work first)
     // the block table: a frame of full blocks never needs more than window / 64 KiB + 1 entries, so this bound needs nothing read back
-    uint64_t table_cap = (uint64_t)n_frames + dstBytes / BF_SHARE + 1;
-    if (table_cap > 0xFFFFFFF0ull) table_cap = 0xFFFFFFF0ull;
-    const size_t counts_at = (size_t)n_frames * sizeof(BatchFrame), ctl_at = (counts_at + (size_t)n_frames * 4 + 255) & ~(size_t)255;
-    if (e->bframes.ensure(ctl_at + 256) || e->btable.ensure((size_t)table_cap * sizeof(BatchBlk))) return make_err(LZ4F_ERROR_allocation_failed);
-    BatchFrame* frames = (BatchFrame*)e->bframes.p;
-    uint32_t* counts = (uint32_t*)((uint8_t*)e->bframes.p + counts_at);
-    uint32_t* ctl = (uint32_t*)((uint8_t*)e->bframes.p + ctl_at);
+    const uint64_t table_cap = batch_table_cap(n_frames, dstBytes / BF_SHARE);
+    Carve ws{e->bframes};
+    const size_t frames_at = ws.take((size_t)n_frames * sizeof(BatchFrame)), counts_at = ws.take((size_t)n_frames * 4), ctl_at = ws.take(256, 256);
+    if (ws.ensure() || e->btable.ensure((size_t)table_cap * sizeof(BatchBlk))) return make_err(LZ4F_ERROR_allocation_failed);
+    BatchFrame* frames = ws.at<BatchFrame>(frames_at);
+    uint32_t* counts = ws.at<uint32_t>(counts_at);
+    uint32_t* ctl = ws.at<uint32_t>(ctl_at);
     BatchBlk* table = (BatchBlk*)e->btable.p;
     const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
     hipLaunchKernelGGL(k_bf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts);
-    hipLaunchKernelGGL(k_bf_place, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
+    hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
     hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
-    hipLaunchKernelGGL((k_bf_blocks<W>), dim3((uint32_t)std::min<uint64_t>((table_cap + W - 1) / W, BF_BLOCKS_GRID)), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table,
-                       (const uint32_t*)ctl);
+    hipLaunchKernelGGL((k_bf_blocks<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table, (const uint32_t*)ctl);
     hipLaunchKernelGGL((k_bf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames);
     hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
                        e->sw.no_content_check ? 0u : 1u);
-    if (hipGetLastError() != hipSuccess) { set_last_error("dev_decompressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
-    return 0;
+    return batch_end("dev_decompressFrames");
 }
 
 size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
@@ -1180,34 +1212,30 @@ size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, c
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     if (n_frames == 0) return 0;
-    if (!d_src || !d_src_off || !d_results) { set_last_error("dev_measureFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
-    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (const size_t r = batch_begin(e, "dev_measureFrames", d_src && d_src_off && d_results)) return r;
     hipStream_t st = (hipStream_t)e->stream;
-    if (e->aux_pending) { HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t)e->ev_join, 0)); e->aux_pending = false; }      // (an earlier call's forked work first)
     // the block table: sized from the call's arguments alone; frames behind an overflow are measured a wave per frame
-    uint64_t table_cap = (uint64_t)n_frames + srcBytes / MF_SHARE + 1;
-    if (table_cap > 0xFFFFFFF0ull) table_cap = 0xFFFFFFF0ull;
-    const size_t wins_at = (size_t)n_frames * sizeof(MeasFrame), counts_at = wins_at + (size_t)n_frames * 8,
-                 ctl_at = (counts_at + (size_t)n_frames * 4 + 255) & ~(size_t)255;
-    if (e->mframes.ensure(ctl_at + 256) || e->mtable.ensure((size_t)table_cap * sizeof(MeasBlk))) return make_err(LZ4F_ERROR_allocation_failed);
-    MeasFrame* frames = (MeasFrame*)e->mframes.p;
-    uint64_t* wins = (uint64_t*)((uint8_t*)e->mframes.p + wins_at);
-    uint32_t* counts = (uint32_t*)((uint8_t*)e->mframes.p + counts_at);
-    uint32_t* ctl = (uint32_t*)((uint8_t*)e->mframes.p + ctl_at);
+    const uint64_t table_cap = batch_table_cap(n_frames, srcBytes / MF_SHARE);
+    Carve ws{e->mframes};
+    const size_t frames_at = ws.take((size_t)n_frames * sizeof(MeasFrame)), wins_at = ws.take((size_t)n_frames * 8),
+                 counts_at = ws.take((size_t)n_frames * 4), ctl_at = ws.take(256, 256);
+    if (ws.ensure() || e->mtable.ensure((size_t)table_cap * sizeof(MeasBlk))) return make_err(LZ4F_ERROR_allocation_failed);
+    MeasFrame* frames = ws.at<MeasFrame>(frames_at);
+    uint64_t* wins = ws.at<uint64_t>(wins_at);
+    uint32_t* counts = ws.at<uint32_t>(counts_at);
+    uint32_t* ctl = ws.at<uint32_t>(ctl_at);
     MeasBlk* table = (MeasBlk*)e->mtable.p;
     const uint8_t* src = (const uint8_t*)d_src;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
     hipLaunchKernelGGL(k_mf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, n_frames, frames, counts);
-    hipLaunchKernelGGL(k_mf_place, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
+    hipLaunchKernelGGL(k_batch_place<MeasFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
     hipLaunchKernelGGL(k_mf_table, dim3(g256), dim3(256), 0, st, src, (const MeasFrame*)frames, n_frames, table);
-    hipLaunchKernelGGL((k_mf_blocks<W>), dim3((uint32_t)std::min<uint64_t>((table_cap + W - 1) / W, MF_BLOCKS_GRID)), dim3(64 * W), 0, st, src, (const MeasFrame*)frames, n_frames,
-                       table, (const uint32_t*)ctl);
+    hipLaunchKernelGGL((k_mf_blocks<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, (const MeasFrame*)frames, n_frames, table, (const uint32_t*)ctl);
     hipLaunchKernelGGL((k_mf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, frames, n_frames);
     hipLaunchKernelGGL((k_mf_finish<W>), dim3(gw), dim3(64 * W), 0, st, (const MeasFrame*)frames, n_frames, (const MeasBlk*)table, (ResultRec*)d_results, wins);
     if (d_dst_off) hipLaunchKernelGGL(k_mf_scan, dim3(1), dim3(1024), 0, st, (const uint64_t*)wins, n_frames, d_dst_off);
-    if (hipGetLastError() != hipSuccess) { set_last_error("dev_measureFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
-    return 0;
+    return batch_end("dev_measureFrames");
 }
 
 size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
@@ -1221,8 +1249,7 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
     if (n_frames == 0) return 0;
-    if (!d_src || !d_src_off || !d_dst || !d_dst_off || !d_results) { set_last_error("dev_compressFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
-    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results)) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
@@ -1237,17 +1264,17 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     }
     // the tables and the pool, from the call's arguments alone: chunks are 64 KiB whatever the block size (pick_chunk_size), so spans
     // that do not overlap have at most n_frames + srcBytes / 64 KiB chunks, no more blocks, and a record per 4 bytes + one per chunk
-    uint64_t cap = (uint64_t)n_frames + srcBytes / BC_CHUNK + 1;
-    if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+    const uint64_t cap = batch_table_cap(n_frames, srcBytes / BC_CHUNK);
     const uint64_t rec_cap = (uint64_t)srcBytes / 4 + cap;
-    const size_t ctl_at = ((size_t)n_frames * sizeof(BcFrame) + 255) & ~(size_t)255;
+    Carve ws{e->cframes};
+    const size_t frames_at = ws.take((size_t)n_frames * sizeof(BcFrame)), ctl_at = ws.take(256, 256);
     const size_t recs_had = e->recs.cap;
-    if (e->cframes.ensure(ctl_at + 256) || e->cblocks.ensure((size_t)cap * sizeof(BcBlk)) || e->cchunks.ensure((size_t)cap * sizeof(BcChunk)) ||
+    if (ws.ensure() || e->cblocks.ensure((size_t)cap * sizeof(BcBlk)) || e->cchunks.ensure((size_t)cap * sizeof(BcChunk)) ||
         e->info.ensure((size_t)cap * sizeof(ChunkInfo)) || e->recs.ensure(64 + (size_t)rec_cap * 8))
         return make_err(LZ4F_ERROR_allocation_failed);
     if (e->recs.cap != recs_had) e->recs_ctl_clean = nullptr;          // (a new pool: the single call's control words in its first 64 bytes are not zero yet)
-    BcFrame* frames = (BcFrame*)e->cframes.p;
-    uint32_t* ctl = (uint32_t*)((uint8_t*)e->cframes.p + ctl_at);
+    BcFrame* frames = ws.at<BcFrame>(frames_at);
+    uint32_t* ctl = ws.at<uint32_t>(ctl_at);
     BcBlk* blocks = (BcBlk*)e->cblocks.p;
     BcChunk* chunks = (BcChunk*)e->cchunks.p;
     ChunkInfo* info = (ChunkInfo*)e->info.p;
@@ -1258,29 +1285,28 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
-    const uint32_t g_ent = (uint32_t)std::min<uint64_t>((cap + W - 1) / W, BC_GRID);      // (a wave per entry, striding over the entries in use)
+    const dim3 g_ent = batch_grid(cap, W);                             // (a wave per entry, striding over the entries in use)
     hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
     hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
     hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
     if (hc)
-        hipLaunchKernelGGL(k_bc_find_hc, dim3((uint32_t)std::min<uint64_t>(cap, BC_GRID / 4)), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
+        hipLaunchKernelGGL(k_bc_find_hc, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
     else
-        hipLaunchKernelGGL(k_bc_find_solo, dim3((uint32_t)std::min<uint64_t>(cap, BC_GRID * 2)), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
+        hipLaunchKernelGGL(k_bc_find_solo, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool);
-    hipLaunchKernelGGL((k_bc_layout<W>), dim3(g_ent), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
+    hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
     hipLaunchKernelGGL((k_bc_frames<W>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results);
-    hipLaunchKernelGGL((k_bc_emit<W>), dim3(g_ent), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
+    hipLaunchKernelGGL((k_bc_emit<W>), g_ent, dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
                        (const ChunkInfo*)info, (const uint64_t*)pool);
     if (pf.block_checksum) {
         if (bs > (256u << 10))                                         // (few big blocks: the four-lane chain, as the single call's k_xxh32_blocks4)
-            hipLaunchKernelGGL((k_bc_blockck<W, true>), dim3(g_ent), dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+            hipLaunchKernelGGL((k_bc_blockck<W, true>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
         else
-            hipLaunchKernelGGL((k_bc_blockck<W, false>), dim3(g_ent), dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+            hipLaunchKernelGGL((k_bc_blockck<W, false>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
     }
     if (pf.content_checksum) hipLaunchKernelGGL((k_bc_content<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames);
-    if (hipGetLastError() != hipSuccess) { set_last_error("dev_compressFrames: launch failed"); return make_err(LZ4F_ERROR_GENERIC); }
-    return 0;
+    return batch_end("dev_compressFrames");
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

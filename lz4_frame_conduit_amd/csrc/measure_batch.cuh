@@ -2,13 +2,14 @@
 // decoded size from its tokens, the verdict the batch decoder gives without looking at decoded bytes, and the window
 // lz4f_mi355x_dev_decompressFrames needs for it.  Nothing is written but the records, the offsets and the engine's workspace.
 //
-// The kernels follow decode_batch.cuh, with no window to bound anything:
-//   k_mf_head    a thread per frame: the span against the buffer, then the frame's grammar (frame_format.hpp, through bf_walk) -> a
-//                MeasFrame record and a block count
-//   k_mf_place   one workgroup: exclusive scan of the counts -> each frame's slice of the block table.  Linked frames get one too:
-//                a block's size needs no history.  The table holds n_frames + srcBytes / 256 + 1 entries (the host's bound, from
-//                the call's arguments alone); a frame behind an overflow - 5 bytes of source can be a whole block - goes to k_mf_serial
-//   k_mf_table   a thread per placed frame walks its size words again and writes its entries
+// The batch decoder's shape with no window to bound anything (batch_common.cuh: the scan, the record, the frame head, the walks, the
+// slice check and the slice verdict); what is this file's own:
+//   k_mf_head    a thread per frame: the span against the buffer, then batch_frame_head with the span's bound alone -> a MeasFrame
+//                record and a block count
+//   (k_batch_place<MeasFrame> then gives every frame a slice of the block table, linked frames too: a block's size needs no
+//                history.  The table holds n_frames + srcBytes / 256 + 1 entries (the host's bound, from the call's arguments
+//                alone); a frame behind an overflow - 5 bytes of source can be a whole block - goes to k_mf_serial)
+//   k_mf_table   a thread per placed frame writes its entries (batch_table_walk)
 //   k_mf_blocks  a wave per entry, striding: mf_measure_block, the lanes finding the tokens (decode_indexed.cuh:
 //                k_selfindex_walk_wave) under the DECODER's end-of-block rules (decode.cuh: wave_decode_block_lim) judged against
 //                room = maxBlockSize.  The two offset bytes of a match are stepped over, never looked at; nothing is hashed
@@ -31,19 +32,14 @@
 // ones: W == size when every block but the last decodes to bs and the last one to something, and W <= n * bs always.
 #pragma once
 #include "common.cuh"
-#include "decode_batch.cuh"
+#include "batch_common.cuh"
 #include "decode_indexed.cuh"
 
 namespace lz4f {
 
 constexpr uint32_t MF_SHARE = 256;          // table entries: n_frames + srcBytes / MF_SHARE + 1
 
-struct MeasFrame {                          // per frame (device workspace, 64 bytes)
-    uint64_t src, span;                     // the frame's span in d_src
-    uint64_t consumed, size;                // as the result record (size: the declared content size until the verdict)
-    uint32_t status, flags, n_blocks, first_bad;
-    uint32_t bs, hsize, tbl_at, last;       // tbl_at: first table entry, BF_NONE: k_mf_serial measures it; last: what the last block decodes to (k_mf_serial)
-};
+using MeasFrame = BatchCore;                // per frame (64 bytes).  tbl_at == BF_NONE: k_mf_serial measures it, and leaves what the last block decodes to in `last`
 struct MeasBlk {                            // block table entry (24 bytes)
     uint64_t src;                           // payload in d_src
     uint32_t word, frame;                   // size word, frame
@@ -130,89 +126,30 @@ __global__ __launch_bounds__(256) void k_mf_head(const uint8_t* __restrict__ src
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_frames) return;
     MeasFrame r;
-    r.src = soff[i]; r.span = 0; r.consumed = 0; r.size = 0;
-    r.status = 0; r.flags = 0; r.n_blocks = 0; r.first_bad = BF_NONE; r.bs = 0; r.hsize = 0; r.tbl_at = BF_NONE; r.last = 0;
+    batch_core_init(r, soff[i]);
     const uint64_t s1 = soff[i + 1];
     uint32_t count = 0;
     auto put = [&](uint32_t st) { r.status = st; frames[i] = r; counts[i] = count; };
     if (r.src > s1 || s1 > src_bytes) { r.src = 0; return put(ST_SRCPTR); }                 // nothing is read
-    r.span = s1 - r.src;
-    const uint8_t* f = src + r.src;
-    const uint64_t cap = r.span;
-    if (cap < 7) return put(ST_INCOMPLETE);
-    if (is_skippable(rd32le(f))) {
-        if (const uint32_t st = skippable_span(f, cap, r.consumed)) { r.consumed = 0; return put(st); }
-        r.flags = FLAG_SKIPPABLE;
-        return put(ST_OK);
-    }
-    FrameHead h;
-    if (const uint32_t st = frame_head_parse(f, cap, h)) return put(st);
-    r.flags = h.flg; r.bs = h.bs; r.hsize = h.hsize;
+    const uint64_t cap = r.span = s1 - r.src;
     // k_bf_head's bound on the blocks of a span, the part of it that no window changes: more size words than a block per 5 bytes
     // of span (only empty stored blocks, 4 bytes each, get there) is dstMaxSize_tooSmall to the decoder in any window, so here too
-    uint64_t tcap = cap / 5 + 2;
-    if (tcap > 0x7FFFFFFFull) tcap = 0x7FFFFFFFull;
-    uint64_t pos = h.hsize;
-    uint32_t n = 0;
-    if (const uint32_t st = bf_walk<false>(f, cap, pos, n, h.bs, h.bck, [&](uint32_t, uint32_t, uint64_t) -> uint32_t {
-            return n >= tcap ? (uint32_t)ST_DSTSMALL : (uint32_t)ST_OK;
-        })) return put(st);
-    uint32_t tail;
-    if (const uint32_t st = frame_end(h.flg, cap - pos, tail)) return put(st);
-    r.n_blocks = n; r.consumed = pos + tail; r.size = h.content;
-    count = n;
-    put(ST_OK);
-}
-
-// one workgroup: exclusive scan of the counts (k_bf_place); a frame whose slice would end beyond the table is left to k_mf_serial.
-// ctl[0]: the entries in use
-__global__ __launch_bounds__(1024) void k_mf_place(const uint32_t* __restrict__ counts, uint32_t n_frames, MeasFrame* __restrict__ frames,
-                                                   uint64_t table_cap, uint32_t* __restrict__ ctl)
-{
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry_s;
-    const uint32_t t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t base = 0; base < n_frames; base += 1024) {
-        const uint32_t i = base + t;
-        const uint64_t c = i < n_frames ? counts[i] : 0u;
-        uint64_t incl = c;
-        for (uint32_t d = 1; d < WAVE; d <<= 1) { const uint64_t x = __shfl_up(incl, d); if (lane >= d) incl += x; }
-        if (lane == WAVE - 1) wsum[wv] = incl;
-        __syncthreads();
-        uint64_t before = carry_s;
-        for (uint32_t k = 0; k < wv; k++) before += wsum[k];
-        const uint64_t at = before + incl - c;
-        if (c && at + c <= table_cap) frames[i].tbl_at = (uint32_t)at;
-        __syncthreads();
-        if (t == 1023) carry_s = before + incl;
-        __syncthreads();
-    }
-    if (t == 0) ctl[0] = (uint32_t)(carry_s < table_cap ? carry_s : table_cap);
+    const uint32_t st = batch_frame_head(src, r, [&](uint32_t) { return cap / 5 + 2; }, [](uint32_t) -> uint32_t { return ST_OK; });
+    if (st == ST_OK) count = r.n_blocks;
+    put(st);
 }
 
 __global__ __launch_bounds__(256) void k_mf_table(const uint8_t* __restrict__ src, const MeasFrame* __restrict__ frames, uint32_t n_frames,
                                                   MeasBlk* __restrict__ table)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_frames) return;
-    const MeasFrame r = frames[i];
-    if (r.status != 0 || r.tbl_at == BF_NONE) return;
-    const uint8_t* f = src + r.src;
-    uint64_t pos = r.hsize;
-    uint32_t b;
-    bf_walk<false>(f, r.span, pos, b, r.bs, flg_bck(r.flags), [&](uint32_t w, uint32_t, uint64_t at) -> uint32_t {
-        if (b >= r.n_blocks) return ST_GENERIC;                 // (k_mf_head walked this frame: it has n_blocks of them)
+    batch_table_walk(src, frames, n_frames, [&](uint32_t i, const MeasFrame& r, uint32_t b, uint32_t w, uint64_t at) {
         MeasBlk e;
         e.src = r.src + at; e.word = w; e.frame = i; e.got = 0; e.pad = 0;
         table[r.tbl_at + b] = e;
-        return ST_OK;
     });
 }
 
 // the grid is sized by the host's bound on the table, capped: the waves stride over the entries in use (ctl[0])
-constexpr uint32_t MF_BLOCKS_GRID = 8192;
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_mf_blocks(const uint8_t* __restrict__ src, const MeasFrame* __restrict__ frames, uint32_t n_frames,
                                                       MeasBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
@@ -223,8 +160,7 @@ __global__ __launch_bounds__(64 * W) void k_mf_blocks(const uint8_t* __restrict_
         const MeasBlk e = table[w];
         const uint32_t fi = uni(e.frame);
         if (fi >= n_frames) continue;
-        const uint32_t at = uni(frames[fi].tbl_at), nb = uni(frames[fi].n_blocks);
-        if (at == BF_NONE || w < at || w - at >= nb) continue;     // (an entry of this call: its frame's slice holds it)
+        if (!slice_holds(uni(frames[fi].tbl_at), uni(frames[fi].n_blocks), w)) continue;
         const uint64_t span_end = uni64(frames[fi].src + frames[fi].span);
         const uint64_t so = uni64(e.src);
         const int32_t got = mf_measure_word(src + so, uni(e.word), span_end - so, uni(frames[fi].bs));
@@ -275,17 +211,8 @@ __global__ __launch_bounds__(64 * W) void k_mf_finish(const MeasFrame* __restric
         size = 0;
     } else if (status == 0 && tbl_at != BF_NONE) {                 // the placed frames: the verdict on the table slice
         const MeasBlk* t = table + tbl_at;
-        uint32_t bad = BF_NONE; uint64_t sum = 0;
-        for (uint32_t b0 = 0; b0 < n; b0 += WAVE) {
-            const uint32_t b = b0 + lane;
-            const int32_t g = b < n ? t[b].got : 0;
-            const uint64_t fm = __ballot(g < 0);
-            if (fm && bad == BF_NONE) bad = b0 + (uint32_t)__builtin_ctzll(fm);
-            uint64_t s = g > 0 ? (uint64_t)g : 0u;
-#pragma unroll
-            for (int sft = 1; sft < 64; sft <<= 1) s += __shfl_xor(s, sft);
-            sum += s;
-        }
+        uint32_t bad; int32_t kind; uint64_t sum;
+        slice_verdict(n, bad, kind, sum, [&](uint32_t b) -> int32_t { return b < n ? t[b].got : 0; });
         if (bad != BF_NONE) { status = ST_GENERIC; first_bad = bad; }
         else {
             last = uni((uint32_t)t[n - 1].got);
@@ -312,26 +239,16 @@ __global__ __launch_bounds__(64 * W) void k_mf_finish(const MeasFrame* __restric
 // one workgroup: off[i] = wins[0] + .. + wins[i - 1], off[n_frames] the total
 __global__ __launch_bounds__(1024) void k_mf_scan(const uint64_t* __restrict__ wins, uint32_t n_frames, uint64_t* __restrict__ off)
 {
-    __shared__ uint64_t wsum[16];
-    __shared__ uint64_t carry_s;
-    const uint32_t t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
+    __shared__ WgScan<1> s;
+    wg_scan_begin(s);
     for (uint32_t base = 0; base < n_frames; base += 1024) {
-        const uint32_t i = base + t;
-        const uint64_t c = i < n_frames ? wins[i] : 0u;
-        uint64_t incl = c;
-        for (uint32_t d = 1; d < WAVE; d <<= 1) { const uint64_t x = __shfl_up(incl, d); if (lane >= d) incl += x; }
-        if (lane == WAVE - 1) wsum[wv] = incl;
-        __syncthreads();
-        uint64_t before = carry_s;
-        for (uint32_t k = 0; k < wv; k++) before += wsum[k];
-        if (i < n_frames) off[i] = before + incl - c;
-        __syncthreads();
-        if (t == 1023) carry_s = before + incl;
-        __syncthreads();
+        const uint32_t i = base + threadIdx.x;
+        const uint64_t c[1] = {i < n_frames ? wins[i] : 0u};
+        uint64_t at[1];
+        wg_scan_tile(c, at, s);
+        if (i < n_frames) off[i] = at[0];
     }
-    if (t == 0) off[n_frames] = carry_s;
+    if (threadIdx.x == 0) off[n_frames] = s.carry[0];
 }
 
 }  // namespace lz4f

@@ -268,7 +268,13 @@ def test_more_blocks_than_the_decoder_takes(eng):
 
 
 def test_many_frames_measure_then_decode(eng):
-    n, fb = 4096, 4096
+    """Compress, measure, decode: three one-workgroup scans over the frames in tiles of 1024, with the last tile full, holding one
+    frame, and one short of full."""
+    for n, fb in ((4096, 4096), (2049, 1024), (2047, 1024)):
+        _many_frames_measure_then_decode(eng, n, fb)
+
+
+def _many_frames_measure_then_decode(eng, n, fb):
     data = synth50_device(n * fb, 7, DEV)
     p = conduit.make_preferences(blockSizeID=4, blockMode=1)
     wo = frame_windows([fb] * n, p)
