@@ -12,6 +12,7 @@
 // Same accept/reject rules as the oracle (oracle/orc_lz4block.c: orc_lz4_decompress_safe).
 #pragma once
 #include "common.cuh"
+#include "lz4_seq.cuh"
 
 namespace lz4f {
 
@@ -192,19 +193,7 @@ __device__ __forceinline__ int32_t wave_decode_block_win(const uint8_t* __restri
     };
     auto fetch = [&](uint32_t qq) -> uint64_t {                              // 8 payload bytes from qq on
         ensure(qq);
-        const uint32_t rel = qq - wb, l = rel >> 3, sh8 = (rel & 7u) * 8u;
-        const uint64_t lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.x, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.y, l) << 32);
-        const uint64_t hi = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.z, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.w, l) << 32);
-        return (lo >> sh8) | ((hi << 1) << (63u - sh8));
-    };
-    auto ext_slow = [&](uint32_t at, uint32_t& after, bool& bad) -> uint32_t {   // length bytes that run on beyond one read
-        uint32_t add = 0;
-        for (;;) {
-            if (at >= csize || add > 0x7FFF0000u) { bad = true; after = at; return add; }
-            const uint32_t b = uni((uint32_t)in[at]);
-            add += b; at++;
-            if (b != 255) { after = at; return add; }
-        }
+        return win_fetch8(win, wb, qq);
     };
     uint32_t pos = 0, op = 0;
     DBP(unsigned long long a_top = 0, a_parse = 0, a_lit = 0, a_rounds = 0, a_ord = 0, a_seq = 0, n_win = 0, n_round = 0, n_ord = 0, n_seq = 0;)
@@ -216,11 +205,10 @@ __device__ __forceinline__ int32_t wave_decode_block_win(const uint8_t* __restri
         uint32_t lit = token >> 4, p = pos + 1;
         bool bad = false;
         if (lit == 15) {
-            const uint64_t x = w >> 8;                                       // 7 candidate length bytes, top byte 0 (never 0xFF)
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-            lit = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-            p = pos + 2 + k;
-            if (k == 7) lit = 15u + ext_slow(pos + 1, p, bad);
+            const LenExt e = len_ext(w >> 8);                                // 7 candidate length bytes, top byte 0 (never 0xFF)
+            lit = 15u + e.add;
+            p = pos + 2 + e.k;
+            if (e.k == 7) lit = 15u + len_ext_slow<true>(in, csize, pos + 1, 0u, 0x7FFF0000u, p, bad);
         }
         if (bad || p > csize) return -1;
         const uint32_t in_left = csize - p, out_left = cap - op;
@@ -242,11 +230,10 @@ __device__ __forceinline__ int32_t wave_decode_block_win(const uint8_t* __restri
         const uint32_t offset = (uint32_t)w & 0xFFFF;
         uint32_t mlen = token & 15, npos = qo + 2;
         if (mlen == 15) {
-            const uint64_t x = w >> 16;                                      // 6 candidate length bytes
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-            mlen = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-            npos = qo + 3 + k;
-            if (k == 6) mlen = 15u + ext_slow(qo + 2, npos, bad);
+            const LenExt e = len_ext(w >> 16);                               // 6 candidate length bytes
+            mlen = 15u + e.add;
+            npos = qo + 3 + e.k;
+            if (e.k == 6) mlen = 15u + len_ext_slow<true>(in, csize, qo + 2, 0u, 0x7FFF0000u, npos, bad);
             if (npos + 4 >= csize) bad = true;
         }
         mlen += 4;
@@ -266,32 +253,22 @@ __device__ __forceinline__ int32_t wave_decode_block_win(const uint8_t* __restri
         // never makes more than 64 + 21 * 18 = 442; with 96 payload bytes and 1 KiB of room left none of its sequences can be the
         // last one or run into the end-of-block rules)
         if (VEC && pos <= csize && csize - pos >= 96u && cap - op >= 1024u) {
-            typedef uint32_t u32_ua1 __attribute__((aligned(1)));
             DBP(const unsigned long long y0 = clock64();)
-            const uint32_t d = dnext_pos == pos ? dnext : *(const u32_ua1*)(in + pos + lane);
+            const uint32_t d = dnext_pos == pos ? dnext : *(const u32_ua*)(in + pos + lane);
             DBP(asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long y1 = clock64(); a_top += y1 - y0;)
             // (a literal length of 15..269 - one extension byte - is still a lane's own business: the byte is in its dword.  Longer
             // ones, and tokens with match-length bytes, go to one_sequence.)
-            const uint32_t t = d & 0xFFu, litn = t >> 4, ml = t & 15u, e1 = (d >> 8) & 0xFFu;
-            const uint32_t hdr = litn == 15u ? 2u : 1u, lit = litn == 15u ? 15u + e1 : litn;      // bytes in front of the literals; literals
-            const bool easy = ml != 15u && !(litn == 15u && e1 == 255u) && lane + hdr + lit + 2u <= 64u;
-            const uint32_t nx = easy ? lane + hdr + lit + 2u : 255u;
-            // the serial part: one hop per token (v_readlane, s_bitset1, two moves, compare, branch).  A token is marked before its
-            // end is known; the last one is taken back if it does not end inside the window.
-            uint64_t mask = 0;
-            uint32_t s = 0, sp = 0, n;
-            do {
-                n = (uint32_t)__builtin_amdgcn_readlane((int)nx, (int)s);
-                asm("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(s));
-                sp = s; s = n;
-            } while (n < 64u);
-            if (n > 64u) { mask &= ~(1ull << sp); s = sp; }
+            const LaneTok tk = lane_token(d);
+            const uint32_t hdr = tk.hdr, lit = tk.lit, ml = tk.ml;            // bytes in front of the literals; literals; match nibble
+            const bool easy = ml != 15u && !(hdr == 2u && tk.e1 == 255u) && lane + hdr + lit + 2u <= 64u;
+            uint32_t s;
+            const uint64_t mask = hop_tokens(easy ? lane + hdr + lit + 2u : 255u, s);
             if (mask) {
                 // the next window's bytes are asked for as soon as it is known where it starts: they travel while this window's
                 // literals and matches are stored (memory operations of a wave return in order: by the time a match's bytes are
                 // there, so are these)
                 dnext_pos = pos + s;
-                if (csize - dnext_pos >= 96u) dnext = *(const u32_ua1*)(in + dnext_pos + lane); else dnext_pos = NONE;
+                if (csize - dnext_pos >= 96u) dnext = *(const u32_ua*)(in + dnext_pos + lane); else dnext_pos = NONE;
                 const bool is_tok = (mask >> lane) & 1ull;
                 const uint32_t mlen = ml + 4u;
                 const uint32_t d2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane + hdr + lit) << 2), (int)d);   // the dword of the lane the offset starts in

@@ -140,21 +140,8 @@ __device__ __forceinline__ void fz_parser(FzShared<C>& sh, const uint8_t* __rest
     };
     auto fetch = [&](uint32_t qq) -> uint64_t {
         uint32_t rel = qq - wb;
-        if (rel >= 504u) { reload(qq); rel = qq - wb; }                    // lanes 0..62 serve reads at rel 0..503
-        const uint32_t l = rel >> 3, sh8 = (rel & 7u) * 8u;
-        const uint64_t lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.x, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.y, l) << 32);
-        const uint64_t hi = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.z, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.w, l) << 32);
-        return (lo >> sh8) | ((hi << 1) << (63u - sh8));
-    };
-    // length bytes that do not end inside the 8-byte read that found them (runs of >= 6 x 0xFF): rare, byte by byte
-    auto ext_slow = [&](uint32_t pos, uint32_t& after) -> uint32_t {
-        uint32_t add = 0;
-        for (;;) {
-            if (pos >= csize || add > 0x7FFF0000u) { status = 1; after = pos; return add; }
-            const uint32_t b = uni((uint32_t)in[pos]);
-            add += b; pos++;
-            if (b != 255) { after = pos; return add; }
-        }
+        if (qq - wb >= 504u) reload(qq);                                   // lanes 0..62 serve reads at rel 0..503
+        return win_fetch8(win, wb, qq);
     };
     // The serial part of a sequence is only what the NEXT token's position depends on - the two lengths - and it is written for
     // the scalar unit, which a wave reaches once every ~4.7 cycles whatever the instruction (tools/probe/chain_rates.hip): every
@@ -201,11 +188,8 @@ __device__ __forceinline__ void fz_parser(FzShared<C>& sh, const uint8_t* __rest
     };
     // the first 8 bytes of the window lane that holds `qq` (enough for a token; `fetch` gives 8 bytes from qq on)
     auto fetch_byte = [&](uint32_t qq) -> uint32_t {
-        uint32_t rel = qq - wb;
-        if (rel >= 504u) { reload(qq); rel = qq - wb; }
-        const uint32_t l = rel >> 3, sh8 = (rel & 7u) * 8u;
-        const uint64_t lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.x, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.y, l) << 32);
-        return (uint32_t)(lo >> sh8) & 0xFFu;
+        if (qq - wb >= 504u) reload(qq);
+        return (uint32_t)win_fetch_lo(win, wb, qq) & 0xFFu;
     };
 
     uint32_t pos = 0;
@@ -217,12 +201,11 @@ __device__ __forceinline__ void fz_parser(FzShared<C>& sh, const uint8_t* __rest
         uint32_t p = pos + 1;                                                // first literal byte
         uint32_t bad = 0;
         if (lit == 15) {
-            const uint64_t x = fetch(pos) >> 8;                              // 7 candidate length bytes, top byte 0 (never 0xFF)
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x);
-            const uint32_t k = f >> 3;
-            lit = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-            p = pos + 2 + k;
-            if (k == 7) { lit = 15u + ext_slow(pos + 1, p); bad |= status; }
+            const LenExt e = len_ext(fetch(pos) >> 8);                       // 7 candidate length bytes, top byte 0 (never 0xFF)
+            lit = 15u + e.add;
+            p = pos + 2 + e.k;
+            // (length bytes that do not end inside the 8-byte read that found them, runs of >= 6 x 0xFF: rare, byte by byte)
+            if (e.k == 7) { bool sb = false; lit = 15u + len_ext_slow<true>(in, csize, pos + 1, 0u, 0x7FFF0000u, p, sb); if (sb) status = 1; bad |= status; }
         }
         bad |= p > csize ? 1u : 0u;
         const uint32_t in_left = csize - p;
@@ -234,12 +217,10 @@ __device__ __forceinline__ void fz_parser(FzShared<C>& sh, const uint8_t* __rest
             mlen = token & 15;
             npos = qo + 2;
             if (mlen == 15) {
-                const uint64_t x = fetch(qo) >> 16;                          // 6 candidate length bytes
-                const uint32_t f = (uint32_t)__builtin_ctzll(~x);
-                const uint32_t k = f >> 3;
-                mlen = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-                npos = qo + 3 + k;
-                if (k == 6) { mlen = 15u + ext_slow(qo + 2, npos); bad |= status; }
+                const LenExt e = len_ext(fetch(qo) >> 16);                   // 6 candidate length bytes
+                mlen = 15u + e.add;
+                npos = qo + 3 + e.k;
+                if (e.k == 6) { bool sb = false; mlen = 15u + len_ext_slow<true>(in, csize, qo + 2, 0u, 0x7FFF0000u, npos, sb); if (sb) status = 1; bad |= status; }
                 bad |= npos + 4 >= csize ? 1u : 0u;
             }
             mlen += 4;

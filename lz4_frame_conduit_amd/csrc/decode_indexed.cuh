@@ -29,28 +29,13 @@
 //   k_trace_copy      the same origins hop by hop, for when that scratch cannot be had
 #pragma once
 #include "common.cuh"
+#include "lz4_seq.cuh"
 #include "decode.cuh"
 #include "decode_fused.cuh"
 #include "decode_linked.cuh"
 #include "encode.cuh"
 
 namespace lz4f {
-
-// 8 payload bytes at `pos`, never touching memory at or beyond in + readable
-__device__ __forceinline__ uint64_t pt_load8(const uint8_t* __restrict__ in, uint32_t pos, uint64_t readable)
-{
-    if ((uint64_t)pos + 8 <= readable) { typedef uint64_t u64u __attribute__((aligned(1))); return *(const u64u*)(in + pos); }
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < 8; i++) if ((uint64_t)pos + i < readable) v |= (uint64_t)in[pos + i] << (8 * i);
-    return v;
-}
-
-// 16 payload bytes at `pos` (same rule)
-__device__ __forceinline__ void pt_load16(const uint8_t* __restrict__ in, uint32_t pos, uint64_t readable, uint64_t& lo, uint64_t& hi)
-{
-    if ((uint64_t)pos + 16 <= readable) { typedef uint64_t u64u __attribute__((aligned(1))); lo = *(const u64u*)(in + pos); hi = *(const u64u*)(in + pos + 8); return; }
-    lo = pt_load8(in, pos, readable); hi = pt_load8(in, pos + 8, readable);
-}
 
 // The index header is checked on the device (no host round trip on this path): usable at all, made for this geometry, its
 // tables inside the buffer the caller named, its sequences inside the descriptor workspace the engine has.  flags[0] != 0
@@ -117,6 +102,7 @@ __device__ __forceinline__ bool parse_run(const uint8_t* __restrict__ in, uint32
     // (The descriptor of sequence i is stored BEHIND the load of sequence i + 1: loads and stores share one counter and come back in issue
     // order, so a store in front of the load would put a write's round trip on the chain as well - in the feeder that parses for itself
     // that was 9.6 k cycles per sequence instead of one memory latency.)
+    // (hand-written walker, not seq_lit / seq_match of lz4_seq.cuh: through them k_copy_selffed spills more registers)
     uint64_t w, w_hi;
     SeqDesc pend{0u, 0u, 0u, 0u};
     pt_load16(in, pos, readable, w, w_hi);
@@ -125,9 +111,8 @@ __device__ __forceinline__ bool parse_run(const uint8_t* __restrict__ in, uint32
         const uint32_t token = (uint32_t)w & 0xFF;
         uint32_t lit = token >> 4, p = pos + 1;
         if (lit == 15) {
-            const uint64_t x = w >> 8;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-            if (k < 7) { lit += 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF); p += k + 1; }
+            const LenExt e = len_ext(w >> 8);
+            if (e.k < 7) { lit += e.add; p += e.k + 1; }
             else { for (;;) { if (p >= csize || lit > (1u << 24)) { bad = true; break; } const uint32_t v = in[p++]; lit += v; if (v != 255) break; } if (bad) break; }
         }
         if (p > csize || lit >= (1u << 24)) { bad = true; break; }
@@ -148,9 +133,8 @@ __device__ __forceinline__ bool parse_run(const uint8_t* __restrict__ in, uint32
             mlen = token & 15; uint32_t pn = q + 2;
             bool reload = false;
             if (mlen == 15) {
-                const uint64_t x = w2 >> 16;
-                const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-                if (k < 6) { mlen += 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF); pn += k + 1; }
+                const LenExt e = len_ext(w2 >> 16);
+                if (e.k < 6) { mlen += e.add; pn += e.k + 1; }
                 else { reload = true; for (;;) { if (pn >= csize || mlen > (1u << 24)) { bad = true; break; } const uint32_t v = in[pn++]; mlen += v; if (v != 255) break; } if (bad) break; }
                 if (pn + 4 >= csize) { bad = true; break; }
             }
@@ -297,44 +281,27 @@ __global__ __launch_bounds__(256) void k_selfindex_walk(const uint8_t* __restric
     IxEntry* ent = nullptr;
     if (MODE == 1) { const IxBlock bk = ix_blocks((const void*)ix)[b]; ent = (IxEntry*)((uint8_t*)ix + ix_entries_at(n, ((const IxHeader*)ix)->chunks_per_block)) + bk.entry_base; }
     const uint32_t total = MODE == 1 ? cnt[b] : 0u;
-    uint32_t pos = 0, op = 0, k = 0;
+    uint32_t op = 0, k = 0;
     bool bad = false;
-    uint64_t w, w_hi;
-    pt_load16(in, pos, readable, w, w_hi);
+    SeqCur c{0, 0};
+    seq_begin(in, readable, c);
     for (;;) {
-        if (pos >= csize) { bad = true; break; }
+        if (c.pos >= csize) { bad = true; break; }
         if (MODE == 1 && (k % IX_STRIDE) == 0) {
             const uint32_t ns = total - k < IX_STRIDE ? total - k : IX_STRIDE;
-            ent[k / IX_STRIDE] = IxEntry{pos, op, k, ns | (b << 8)};
+            ent[k / IX_STRIDE] = IxEntry{c.pos, op, k, ns | (b << 8)};
         }
-        const uint32_t token = (uint32_t)w & 0xFF;
-        uint32_t lit = token >> 4, p = pos + 1;
-        if (lit == 15) {
-            const uint64_t x = w >> 8;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 7) { lit += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); p += kk + 1; }
-            else { for (;;) { if (p >= csize || lit > (1u << 24)) { bad = true; break; } const uint32_t v = in[p++]; lit += v; if (v != 255) break; } if (bad) break; }
-        }
-        if (p > csize || lit >= (1u << 24)) { bad = true; break; }
+        uint32_t token, lit, p, mlen;
+        if (!seq_lit(in, csize, c, token, lit, p) || p > csize || lit >= (1u << 24)) { bad = true; break; }
         const uint32_t in_left = csize - p;
         k++;
         if (lit + 8 > in_left) { if (lit != in_left) bad = true; op += lit; break; }       // the block's last sequence
         const uint32_t q = p + lit;
         uint64_t w2, w2_hi;
         pt_load16(in, q, readable, w2, w2_hi);
-        uint32_t mlen = token & 15, pn = q + 2;
-        bool reload = false;
-        if (mlen == 15) {
-            const uint64_t x = w2 >> 16;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 6) { mlen += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); pn += kk + 1; }
-            else { reload = true; for (;;) { if (pn >= csize || mlen > (1u << 24)) { bad = true; break; } const uint32_t v = in[pn++]; mlen += v; if (v != 255) break; } if (bad) break; }
-        }
+        if (!seq_match(in, csize, readable, c, token, q, w2, w2_hi, mlen)) { bad = true; break; }
         op += lit + mlen + 4;
-        pos = pn;
         if (op > (1u << 23)) { bad = true; break; }
-        if (reload) pt_load16(in, pos, readable, w, w_hi);
-        else { const uint32_t sh = (pn - q) * 8u; w = sh >= 64 ? w2_hi : ((w2 >> sh) | (w2_hi << (64u - sh))); }
     }
     if (bad || (MODE == 1 && k != total)) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
     if (MODE == 0) { cnt[b] = k; osz[b] = op; }
@@ -370,24 +337,16 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_selfindex_walk_wave(const
     const uint32_t total = MODE == 1 ? cnt[b] : 0u;
     uint32_t pos = 0, op = 0, k = 0;
     bool bad = false;
-    typedef uint32_t u32_ua1 __attribute__((aligned(1)));
     for (;;) {
         if (pos >= csize) { bad = true; break; }
         // ---- the lanes' path (see wave_decode_block_win): tokens with at most one literal-length byte, ending inside the window ----
         if (csize - pos >= 96u && op < (1u << 23)) {
-            const uint32_t d = *(const u32_ua1*)(in + pos + lane);
-            const uint32_t t = d & 0xFFu, litn = t >> 4, ml = t & 15u, e1 = (d >> 8) & 0xFFu;
-            const uint32_t hdr = litn == 15u ? 2u : 1u, lit = litn == 15u ? 15u + e1 : litn;
-            const bool easy = ml != 15u && !(litn == 15u && e1 == 255u) && lane + hdr + lit + 2u <= 64u;
-            const uint32_t nx = easy ? lane + hdr + lit + 2u : 255u;
-            uint64_t mask = 0;
-            uint32_t s = 0, sp = 0, nn;
-            do {
-                nn = (uint32_t)__builtin_amdgcn_readlane((int)nx, (int)s);
-                asm("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(s));
-                sp = s; s = nn;
-            } while (nn < 64u);
-            if (nn > 64u) { mask &= ~(1ull << sp); s = sp; }
+            const uint32_t d = *(const u32_ua*)(in + pos + lane);
+            const LaneTok tk = lane_token(d);
+            const uint32_t hdr = tk.hdr, lit = tk.lit, ml = tk.ml;
+            const bool easy = ml != 15u && !(hdr == 2u && tk.e1 == 255u) && lane + hdr + lit + 2u <= 64u;
+            uint32_t s;
+            const uint64_t mask = hop_tokens(easy ? lane + hdr + lit + 2u : 255u, s);
             if (mask) {
                 const bool is_tok = (mask >> lane) & 1ull;
                 const uint32_t tout = is_tok ? lit + ml + 4u : 0u;
@@ -409,32 +368,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_selfindex_walk_wave(const
             const uint32_t ns = total - k < IX_STRIDE ? total - k : IX_STRIDE;
             ent[k / IX_STRIDE] = IxEntry{pos, op, k, ns | (b << 8)};
         }
-        uint64_t w, w_hi;
-        pt_load16(in, pos, readable, w, w_hi);
-        const uint32_t token = (uint32_t)w & 0xFF;
-        uint32_t lit = token >> 4, p = pos + 1;
-        if (lit == 15) {
-            const uint64_t x = w >> 8;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 7) { lit += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); p += kk + 1; }
-            else { for (;;) { if (p >= csize || lit > (1u << 24)) { bad = true; break; } const uint32_t v = in[p++]; lit += v; if (v != 255) break; } if (bad) break; }
-        }
-        if (p > csize || lit >= (1u << 24)) { bad = true; break; }
+        SeqCur c{pos, 0};                                                     // (no carried window: the next step may be the lanes')
+        seq_begin(in, readable, c);
+        uint32_t token, lit, p, mlen;
+        if (!seq_lit(in, csize, c, token, lit, p) || p > csize || lit >= (1u << 24)) { bad = true; break; }
         const uint32_t in_left = csize - p;
         k++;
         if (lit + 8 > in_left) { if (lit != in_left) bad = true; op += lit; break; }       // the block's last sequence
         const uint32_t q = p + lit;
         uint64_t w2, w2_hi;
         pt_load16(in, q, readable, w2, w2_hi);
-        uint32_t mlen = token & 15, pn = q + 2;
-        if (mlen == 15) {
-            const uint64_t x = w2 >> 16;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 6) { mlen += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); pn += kk + 1; }
-            else { for (;;) { if (pn >= csize || mlen > (1u << 24)) { bad = true; break; } const uint32_t v = in[pn++]; mlen += v; if (v != 255) break; } if (bad) break; }
-        }
+        if (!seq_match(in, csize, readable, c, token, q, w2, w2_hi, mlen)) { bad = true; break; }
         op += lit + mlen + 4;
-        pos = pn;
+        pos = c.pos;
         if (op > (1u << 23)) { bad = true; break; }
     }
     if (bad || (MODE == 1 && k != total)) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }

@@ -149,21 +149,8 @@ __device__ __forceinline__ void lk_parser(LkShared& sh, LkRing& rg, uint32_t p, 
             wb = qq & ~7u;
         };
         auto fetch = [&](uint32_t qq) -> uint64_t {
-            uint32_t rel = qq - wb;
-            if (rel >= 504u) { reload(qq); rel = qq - wb; }
-            const uint32_t l = rel >> 3, sh8 = (rel & 7u) * 8u;
-            const uint64_t lo = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.x, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.y, l) << 32);
-            const uint64_t hi = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.z, l) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane(win.w, l) << 32);
-            return (lo >> sh8) | ((hi << 1) << (63u - sh8));
-        };
-        auto ext_slow = [&](uint32_t pos, uint32_t& after) -> uint32_t {
-            uint32_t add = 0;
-            for (;;) {
-                if (pos >= csize || add > 0x7FFF0000u) { status = 1; after = pos; return add; }
-                const uint32_t v = uni((uint32_t)in[pos]);
-                add += v; pos++;
-                if (v != 255) { after = pos; return add; }
-            }
+            if (qq - wb >= 504u) reload(qq);
+            return win_fetch8(win, wb, qq);
         };
         uint32_t pos = 0;
         uint32_t fin = status;
@@ -174,14 +161,11 @@ __device__ __forceinline__ void lk_parser(LkShared& sh, LkRing& rg, uint32_t p, 
             uint32_t pl = pos + 1;
             uint32_t bad = 0;
             {
-                const uint64_t x = w >> 8;
-                const uint32_t f = (uint32_t)__builtin_ctzll(~x);
-                const uint32_t k = f >> 3;
-                const uint32_t ext = 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
+                const LenExt e = len_ext(w >> 8);
                 const bool is15 = lit == 15;
-                lit = is15 ? 15u + ext : lit;
-                pl = is15 ? pos + 2 + k : pl;
-                if (is15 && k == 7) { lit = 15u + ext_slow(pos + 1, pl); bad |= status; }
+                lit = is15 ? 15u + e.add : lit;
+                pl = is15 ? pos + 2 + e.k : pl;
+                if (is15 && e.k == 7) { bool sb = false; lit = 15u + len_ext_slow<true>(in, csize, pos + 1, 0u, 0x7FFF0000u, pl, sb); if (sb) status = 1; bad |= status; }
             }
             bad |= pl > csize ? 1u : 0u;
             const uint32_t in_left = csize - pl;
@@ -193,14 +177,11 @@ __device__ __forceinline__ void lk_parser(LkShared& sh, LkRing& rg, uint32_t p, 
                 const uint64_t w2 = fetch(qo);
                 off = (uint32_t)w2 & 0xFFFF;
                 bad |= off == 0 ? 1u : 0u;                                   // (offset reach is checked by the chain wave: it knows absolute positions)
-                const uint64_t x = w2 >> 16;
-                const uint32_t f = (uint32_t)__builtin_ctzll(~x);
-                const uint32_t k = f >> 3;
-                const uint32_t ext = 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
+                const LenExt e = len_ext(w2 >> 16);
                 const bool is15 = (token & 15) == 15;
-                mlen = is15 ? 15u + ext : (token & 15);
-                npos = is15 ? qo + 3 + k : qo + 2;
-                if (is15 && k == 6) { mlen = 15u + ext_slow(qo + 2, npos); bad |= status; }
+                mlen = is15 ? 15u + e.add : (token & 15);
+                npos = is15 ? qo + 3 + e.k : qo + 2;
+                if (is15 && e.k == 6) { bool sb = false; mlen = 15u + len_ext_slow<true>(in, csize, qo + 2, 0u, 0x7FFF0000u, npos, sb); if (sb) status = 1; bad |= status; }
                 bad |= (is15 && npos + 4 >= csize) ? 1u : 0u;
                 mlen += 4;
                 bad |= mlen + 5 > cap - (op + lit) ? 1u : 0u;

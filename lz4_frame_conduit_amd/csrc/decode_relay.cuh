@@ -382,20 +382,13 @@ __device__ __forceinline__ void relay_producer(const uint32_t w, const uint8_t* 
         if (!(etv >> 31)) {
             const uint32_t d = lds32(pos + lane);
             DBP(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long y2 = clock64();)
-            const uint32_t t = d & 0xFFu, litn = t >> 4, ml = t & 15u, e1 = (d >> 8) & 0xFFu;
-            const uint32_t hdr = litn == 15u ? 2u : 1u, lit = litn == 15u ? 15u + e1 : litn;
+            const LaneTok tk = lane_token(d);
+            const uint32_t hdr = tk.hdr, lit = tk.lit, ml = tk.ml;
             const uint32_t d2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane + hdr + lit) << 2), (int)d);   // offset, match-length byte (of a token whose sequence ends inside the window)
             const uint32_t ext = (d2 >> 16) & 0xFFu, len = hdr + lit + 2u + (ml == 15u ? 1u : 0u);
-            const bool easy = (ml != 15u || ext <= RL_EXT_MAX) && !(litn == 15u && e1 == 255u) && lane + len <= 64u;
-            const uint32_t nx = easy ? lane + len : 255u;
-            uint64_t mask = 0;
-            uint32_t s = 0, sp = 0, n;
-            do {
-                n = (uint32_t)__builtin_amdgcn_readlane((int)nx, (int)s);
-                asm("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(s));
-                sp = s; s = n;
-            } while (n < 64u);
-            if (n > 64u) { mask &= ~(1ull << sp); s = sp; }
+            const bool easy = (ml != 15u || ext <= RL_EXT_MAX) && !(hdr == 2u && tk.e1 == 255u) && lane + len <= 64u;
+            uint32_t s;
+            const uint64_t mask = hop_tokens(easy ? lane + len : 255u, s);
             if (!mask) { verdict(-1); return; }                              // (cannot be: the speculators walk by the same rules)
             {
                 const bool is_tok = (mask >> lane) & 1ull;
@@ -522,15 +515,6 @@ __device__ __forceinline__ void relay_producer(const uint32_t w, const uint8_t* 
             if (sh) v |= (uint64_t)w2 << (64u - sh);
             return v;
         };
-        auto ext_slow = [&](uint32_t at, uint32_t& after, bool& bad) -> uint32_t {   // length bytes that run on beyond one read
-            uint32_t add = 0;
-            for (;;) {
-                if (at >= csize || add > 0x7FFF0000u) { bad = true; after = at; return add; }
-                const uint32_t b = uni((uint32_t)in[at]);
-                add += b; at++;
-                if (b != 255) { after = at; return add; }
-            }
-        };
         // a copy longer than a wave goes to memory directly: the service wave has to be done with everything in front of it first
         auto memory_is_current = [&]() -> bool {
             if (lane == 0) RL_V32(lds->flush_req) = 1u;
@@ -557,11 +541,10 @@ __device__ __forceinline__ void relay_producer(const uint32_t w, const uint8_t* 
         uint32_t lit = token >> 4, p = pos + 1;
         bool bad = false;
         if (lit == 15) {
-            const uint64_t x = wv >> 8;                                      // 7 candidate length bytes, top byte 0 (never 0xFF)
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-            lit = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-            p = pos + 2 + k;
-            if (k == 7) lit = 15u + ext_slow(pos + 1, p, bad);
+            const LenExt e = len_ext(wv >> 8);                               // 7 candidate length bytes, top byte 0 (never 0xFF)
+            lit = 15u + e.add;
+            p = pos + 2 + e.k;
+            if (e.k == 7) lit = 15u + len_ext_slow<true>(in, csize, pos + 1, 0u, 0x7FFF0000u, p, bad);
         }
         if (bad || p > csize) { verdict(-1); return; }
         const uint32_t in_left = csize - p, out_left = cap - op;
@@ -591,11 +574,10 @@ __device__ __forceinline__ void relay_producer(const uint32_t w, const uint8_t* 
         const uint32_t offset = (uint32_t)wv & 0xFFFF;
         uint32_t mlen = token & 15, npos = qo + 2;
         if (mlen == 15) {
-            const uint64_t x = wv >> 16;                                     // 6 candidate length bytes
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), k = f >> 3;
-            mlen = 15u + 255u * k + (uint32_t)((x >> (f & 56u)) & 0xFF);
-            npos = qo + 3 + k;
-            if (k == 6) mlen = 15u + ext_slow(qo + 2, npos, bad);
+            const LenExt e = len_ext(wv >> 16);                              // 6 candidate length bytes
+            mlen = 15u + e.add;
+            npos = qo + 3 + e.k;
+            if (e.k == 6) mlen = 15u + len_ext_slow<true>(in, csize, qo + 2, 0u, 0x7FFF0000u, npos, bad);
             if (npos + 4 >= csize) bad = true;
         }
         mlen += 4;

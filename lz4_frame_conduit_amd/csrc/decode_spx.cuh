@@ -48,39 +48,22 @@ struct SpxPoint { uint32_t pos, seq, out; };                    // a token posit
 // One sequence of the payload in[0, csize) at c.pos: lengths only (the walk that finds out WHERE sequences are; parse_run checks
 // what they say).  Returns 0: went on to the next token; 1: that was the block's last sequence (c.pos = csize); 2: not a sequence
 // this payload can hold.  One dependent 16-byte load per sequence (the word at the match offset holds the next token as well).
-struct SpxCur { uint32_t pos, seq, out; uint64_t w, w_hi; };
-__device__ __forceinline__ void spx_begin(const uint8_t* __restrict__ in, uint64_t readable, SpxCur& c) { pt_load16(in, c.pos, readable, c.w, c.w_hi); }
+struct SpxCur : SeqCur { uint32_t seq, out; };
+__device__ __forceinline__ void spx_begin(const uint8_t* __restrict__ in, uint64_t readable, SpxCur& c) { seq_begin(in, readable, c); }
 __device__ __forceinline__ int spx_step(const uint8_t* __restrict__ in, uint32_t csize, uint64_t readable, SpxCur& c)
 {
     if (c.pos >= csize) return 2;
-    const uint32_t token = (uint32_t)c.w & 0xFF;
-    uint32_t lit = token >> 4, p = c.pos + 1;
-    if (lit == 15) {
-        const uint64_t x = c.w >> 8;
-        const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-        if (kk < 7) { lit += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); p += kk + 1; }
-        else { for (;;) { if (p >= csize || lit > (1u << 24)) return 2; const uint32_t v = in[p++]; lit += v; if (v != 255) break; } }
-    }
-    if (p > csize || lit >= (1u << 24)) return 2;
+    uint32_t token, lit, p, mlen;
+    if (!seq_lit(in, csize, c, token, lit, p) || p > csize || lit >= (1u << 24)) return 2;
     const uint32_t in_left = csize - p;
     c.seq++;
     if (lit + 8 > in_left) { if (lit != in_left) return 2; c.out += lit; c.pos = csize; return 1; }
     const uint32_t q = p + lit;
     uint64_t w2, w2_hi;
     pt_load16(in, q, readable, w2, w2_hi);
-    uint32_t mlen = token & 15, pn = q + 2;
-    bool reload = false;
-    if (mlen == 15) {
-        const uint64_t x = w2 >> 16;
-        const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-        if (kk < 6) { mlen += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); pn += kk + 1; }
-        else { reload = true; for (;;) { if (pn >= csize || mlen > (1u << 24)) return 2; const uint32_t v = in[pn++]; mlen += v; if (v != 255) break; } }
-    }
+    if (!seq_match(in, csize, readable, c, token, q, w2, w2_hi, mlen)) return 2;
     c.out += lit + mlen + 4;
-    c.pos = pn;
     if (c.out > (1u << 23)) return 2;
-    if (reload) pt_load16(in, c.pos, readable, c.w, c.w_hi);
-    else { const uint32_t sh = (pn - q) * 8u; c.w = sh >= 64 ? w2_hi : ((w2 >> sh) | (w2_hi << (64u - sh))); }
     return 0;
 }
 
@@ -95,7 +78,7 @@ __device__ __forceinline__ uint32_t spx_lanes(uint32_t csize)
 // Is `at` a likely token?  Its sequence must lead to the payload's end or to another token that announces a long literal run.
 __device__ __forceinline__ bool spx_likely_token(const uint8_t* __restrict__ in, uint32_t csize, uint64_t readable, uint32_t at)
 {
-    SpxCur c{at, 0, 0, 0, 0};
+    SpxCur c{{at, 0}, 0, 0};
     spx_begin(in, readable, c);
     const int r = spx_step(in, csize, readable, c);
     if (r == 1) return true;
@@ -206,7 +189,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
         if (s_g[u] != SPX_NONE) {
             uint32_t stop = SPX_NONE;                                        // the next lane that has a start (none: this lane walks to the end)
             for (uint32_t k = u + 1; k < nl; k++) if (s_g[k] != SPX_NONE && s_g[k] > s_g[u]) { stop = s_g[k]; break; }
-            SpxCur c{s_g[u], 0, 0, 0, 0};
+            SpxCur c{{s_g[u], 0}, 0, 0};
             spx_begin(in, readable, c);
             // (a lane that started without a pair to go by - none in SPX_SCAN bytes - may stand in a literal run longer than that, where its
             // chain crawls ~20 bytes per hop: if it makes less than an eighth of the way per hop that the probe saw sequences make in this
@@ -281,7 +264,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
                 if (kn < nl && (s_g[kn] == SPX_NONE || s_g[kn] < nx.pos)) { kn++; continue; }      // (a lane without a start, or one whose start lies behind us already)
                 const uint32_t stop = kn < nl ? s_g[kn] : SPX_NONE;
                 atomicAdd(&flags[2], 1u);                                    // (how often: a developer's number, LZ4F_MI355X_PROF prints it)
-                SpxCur c{nx.pos, nx.seq, nx.out, 0, 0};
+                SpxCur c{{nx.pos, 0}, nx.seq, nx.out};
                 spx_begin(in, readable, c);
                 for (;;) {
                     if (c.pos >= stop) break;

@@ -33,7 +33,7 @@
 #pragma once
 #include "common.cuh"
 #include "batch_common.cuh"
-#include "decode_indexed.cuh"
+#include "lz4_seq.cuh"
 
 namespace lz4f {
 
@@ -58,18 +58,11 @@ __device__ __forceinline__ int32_t mf_measure_block(const uint8_t* __restrict__ 
         // ---- the lanes' path (wave_decode_block_win's condition: none of a window's sequences can be the block's last or come near room) ----
         if (csize - pos >= 96u && room - op >= 1024u) {
             const uint32_t d = *(const u32_ua*)(in + pos + lane);
-            const uint32_t t = d & 0xFFu, litn = t >> 4, ml = t & 15u, e1 = (d >> 8) & 0xFFu;
-            const uint32_t hdr = litn == 15u ? 2u : 1u, lit = litn == 15u ? 15u + e1 : litn;
-            const bool easy = ml != 15u && !(litn == 15u && e1 == 255u) && lane + hdr + lit + 2u <= 64u;
-            const uint32_t nx = easy ? lane + hdr + lit + 2u : 255u;
-            uint64_t mask = 0;
-            uint32_t s = 0, sp = 0, nn;
-            do {
-                nn = (uint32_t)__builtin_amdgcn_readlane((int)nx, (int)s);
-                asm("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(s));
-                sp = s; s = nn;
-            } while (nn < 64u);
-            if (nn > 64u) { mask &= ~(1ull << sp); s = sp; }
+            const LaneTok tk = lane_token(d);
+            const uint32_t hdr = tk.hdr, lit = tk.lit, ml = tk.ml;
+            const bool easy = ml != 15u && !(hdr == 2u && tk.e1 == 255u) && lane + hdr + lit + 2u <= 64u;
+            uint32_t s;
+            const uint64_t mask = hop_tokens(easy ? lane + hdr + lit + 2u : 255u, s);
             if (mask) {
                 const bool is_tok = (mask >> lane) & 1ull;
                 const uint32_t incl = dpp_incl_scan_add(is_tok ? lit + ml + 4u : 0u);
@@ -79,18 +72,11 @@ __device__ __forceinline__ int32_t mf_measure_block(const uint8_t* __restrict__ 
             }
         }
         // ---- one sequence, wave-uniformly, under the decoder's rules ----
-        uint64_t w, w_hi;
-        pt_load16(in, pos, readable, w, w_hi);
-        w = uni64(w);
-        const uint32_t token = (uint32_t)w & 0xFF;
-        uint32_t lit = token >> 4, p = pos + 1;
-        if (lit == 15) {
-            const uint64_t x = w >> 8;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 7) { lit += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); p += kk + 1; }
-            else for (;;) { if (p >= csize || lit > (1u << 24)) return -1; const uint32_t v = uni((uint32_t)in[p]); p++; lit += v; if (v != 255) break; }
-        }
-        if (p > csize || lit > (1u << 24)) return -1;             // (a length byte beyond the payload; more literals than any payload has)
+        SeqCur c{pos, 0};                                         // (no carried window: the next step may be the lanes')
+        seq_begin(in, readable, c);
+        c.w = uni64(c.w);
+        uint32_t token, lit, p, mlen;
+        if (!seq_lit<true>(in, csize, c, token, lit, p) || p > csize || lit > (1u << 24)) return -1;     // (a length byte beyond the payload; more literals than any payload has)
         const uint32_t in_left = csize - p, out_left = room - op;
         if (lit + 12 > out_left || lit + 8 > in_left) {           // must be the last sequence: its literals end exactly at the payload's end
             if (lit != in_left || lit > out_left) return -1;
@@ -98,20 +84,14 @@ __device__ __forceinline__ int32_t mf_measure_block(const uint8_t* __restrict__ 
         }
         op += lit;
         const uint32_t q = p + lit;                               // the offset's two bytes: stepped over
-        uint32_t mlen = token & 15, pn = q + 2;
-        if (mlen == 15) {
-            uint64_t w2, w2_hi;
-            pt_load16(in, q, readable, w2, w2_hi);
-            const uint64_t x = uni64(w2) >> 16;
-            const uint32_t f = (uint32_t)__builtin_ctzll(~x), kk = f >> 3;
-            if (kk < 6) { mlen += 255u * kk + (uint32_t)((x >> (f & 56u)) & 0xFF); pn += kk + 1; }
-            else for (;;) { if (pn >= csize || mlen > (1u << 24)) return -1; const uint32_t v = uni((uint32_t)in[pn]); pn++; mlen += v; if (v != 255) break; }
-            if (pn + 4 >= csize) return -1;                       // length bytes stop before iend - 4
-        }
+        uint64_t w2 = 0, w2_hi = 0;
+        if ((token & 15) == 15) { pt_load16(in, q, readable, w2, w2_hi); w2 = uni64(w2); }
+        if (!seq_match<true>(in, csize, readable, c, token, q, w2, w2_hi, mlen)) return -1;
+        if ((token & 15) == 15 && c.pos + 4 >= csize) return -1;          // length bytes stop before iend - 4
         mlen += 4;
         if ((uint64_t)mlen + 5 > (uint64_t)(room - op)) return -1;    // the last 5 bytes must be literals
         op += mlen;
-        pos = pn;
+        pos = c.pos;
     }
 }
 __device__ __forceinline__ int32_t mf_measure_word(const uint8_t* __restrict__ in, uint32_t word, uint64_t readable, uint32_t room)

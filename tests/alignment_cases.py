@@ -110,13 +110,14 @@ def frame_for(dst_res: int, turn: int = 0) -> int:
     return (11 * dst_res + 2 + 5 * turn) % 16
 
 
-# one accepted and one rejected case of each family of lz4_grammar.corpus() (mext has no rejected case: every extension it
-# writes is valid); small frames, so that every switch set can meet every destination residue
+# one accepted and one rejected case of each family of lz4_grammar.corpus() (mext and lext have no rejected case: every extension
+# they write is valid); small frames, so that every switch set can meet every destination residue
 GRAMMAR_SUBSET = {
     "end": ("end/dense/full/M8/k5", "end/dense/full/M8/k4"),
     "lit": ("lit/mid/L270", "lit/cut/short_by_one"),
     "off": ("off/reach/mid/L4/+0", "off/reach/mid/L4/+1"),
     "mext": ("mext/align3", None),
+    "lext": ("lext/align5", None),
     "link": ("link/bsid4/hist_1000+3000+7/+0", "link/bsid4/hist_1000+3000+7/+1"),
     "blk": ("blk/indep/short_mid/bck1_cck1", "blk/stored_bs/bsid4/+1"),
     "carrier": ("carrier/linked4/dense/k5", "carrier/indep4/sparse/k4"),

@@ -18,6 +18,7 @@ Families (the name's first word):
   lit       literal runs of 0, 14, 15, 269, 270, 65836 bytes, as a block's first sequence and in its middle; a cut extension
   off       offsets 1..16, 31..33, 63..65, 127, 128, 65535 with match lengths 4, 19, 64, 1000, 70000; op + hist and one more
   mext      match-length extensions of 255s at every alignment against the 8-byte words the parsers fetch
+  lext      literal-length extensions likewise, on both sides of what one 8-byte fetch decides (7 length bytes)
   link      linked frames: history from one full block, 2-4 short blocks, a stored block; op + hist and one more
   blk       payload of exactly maxBlockSize and one byte more; stored blocks of maxBlockSize and one byte more; a 1-byte payload
             (0x00) and short blocks in the middle of a frame; block and content checksums
@@ -200,6 +201,11 @@ def _fill(b: Block, kind: str, target: int):
 def mlen_with_ext(e: int) -> int:
     """A match length whose encoding has exactly e length bytes (e = 0: none)."""
     return 15 if e == 0 else 4 + 15 + 255 * (e - 1) + 7
+
+
+def lit_with_ext(e: int, last: int) -> int:
+    """A literal length whose encoding has exactly e length bytes (e >= 1), the last one `last` (0..254)."""
+    return 15 + 255 * (e - 1) + last
 
 
 END_M = [4, 8, 18, 19, mlen_with_ext(2), mlen_with_ext(5), mlen_with_ext(6)]
@@ -389,6 +395,21 @@ def _frames():
     for i in range(40):
         b = fr.block(); b.s(8, 4, 8); b.dense(fr.bs - 8 - 4 - 8); b.s(8, 4, 1 + i).end(8)
     yield nm, fr
+    # ---- literal-length extensions across the parsers' 8-byte words: every alignment, 1..10 length bytes (11 for the last run), the
+    # last byte 0 and 254.  Seven bytes (6 x 0xFF and one more, L = 1545..1799) are the most one 8-byte read decides; from 7 x 0xFF
+    # on (L >= 1800) the parsers go byte by byte.  (Behind all other families: slices of the corpus keep their picks.)
+    for align in range(8):
+        nm = "lext/align%d" % align
+        fr = Frame(4, rng=_rng(nm)); b = fr.block(); b.dense(1000)
+        for e in range(1, 11):
+            for last in (0, 254):
+                b.s(lit_with_ext(e, last), 4 + e % 3, 1 + e * 3)
+                b.s(align, 4, 7)
+        b.s(lit_with_ext(11, 0), 4, 9)                       # 15 + 255 * 10
+        b.s(align, 4, 7)
+        assert b.op + 300 <= fr.bs, b.op
+        b.dense(b.op + 200).end(12)
+        yield nm, fr
 
 
 def corpus():

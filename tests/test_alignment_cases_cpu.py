@@ -143,7 +143,7 @@ def test_grammar_subset_is_in_the_golden_file():
     with open(os.path.join(GOLDEN_DIR, "grammar.json")) as f:
         g = json.load(f)["cases"]
     cmap = {n: (f, m) for n, f, m in corpus()}
-    assert set(ac.GRAMMAR_SUBSET) == {n.split("/")[0] for n in g} == {"end", "lit", "off", "mext", "link", "blk", "carrier"}
+    assert set(ac.GRAMMAR_SUBSET) == {n.split("/")[0] for n in g} == {"end", "lit", "off", "mext", "lext", "link", "blk", "carrier"}
     for fam, (good, bad) in ac.GRAMMAR_SUBSET.items():
         assert good.startswith(fam + "/") and g[good]["once"]["error"] is None and not good.startswith("off/zero/"), good
         f, m = cmap[good]
