@@ -20,6 +20,7 @@ from conftest import golden_file
 from lz4_frame_conduit_amd import _ffi, conduit, datagen
 from lz4_frame_conduit_amd.device import Engine
 from lz4_grammar import END_K
+from lz4_writer_rules import audit
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -286,12 +287,13 @@ def _edge_inputs():
 
 def test_grammar_edges(L):
     """Inputs at the LZ4 block grammar's edges at levels 3 and 12: each frame round-trips through the oracle (and through the device
-    decoder), in 64 KiB and 4 MiB blocks, independent and linked."""
+    decoder) and breaks no writer rule (lz4_writer_rules.audit), in 64 KiB and 4 MiB blocks, independent and linked."""
     for name, data in _edge_inputs().items():
         for lvl in (3, 12):
             for kw in (dict(bsid=4, indep=1), dict(bsid=4, indep=0), dict(bsid=7, indep=1)):
                 frame = dev_compress(data, prefs(lvl, **kw))
                 oracle_ok(frame, data)
+                assert audit(frame, data, dict(bsid=kw["bsid"], linked=not kw["indep"], bck=False, cck=False)) == [], (name, lvl, kw)
                 if data:
                     assert dev_decompress(frame, len(data)) == data, (name, lvl, kw)
                 if name == "random":
