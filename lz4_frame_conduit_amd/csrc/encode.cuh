@@ -179,6 +179,15 @@ static_assert(64 * E1_WAVES >= E1_NSLICE, "a thread per slice when the lists are
 #ifndef E1_V4
 #define E1_V4 1
 #endif
+// Round 5 (fewer instructions per long-sequence helping; each 0: the form before).  E1_V5: what a tile fixes is worked out once per tile,
+// and a sparse tile's helpings take their slices on a path of their own.
+#ifndef E1_V5
+#define E1_V5 1
+#endif
+// E1_V6: long helpings that are claimed behind single slices end on a multiple of their size (see the loop).
+#ifndef E1_V6
+#define E1_V6 1
+#endif
 // Round 4.  Sparse data (long sequences: the mode word says so) is searched from stride 4 on instead of 1: a grab of the bench input is
 // 512 random bytes and a 512-byte copy, and strides 1, 2 / 3, 4 / 5, 6 took 2.8 probe iterations to get across the random half where
 // 4, 5 / 6, 7 take 1.2 - the match is found a few bytes late and the backward extension recovers its start, as it does for liblz4's
@@ -206,6 +215,7 @@ static_assert(64 * E1_WAVES >= E1_NSLICE, "a thread per slice when the lists are
 #define E1_STEP_HIT 1
 #endif
 constexpr uint32_t E1_GRAB_SPARSE = E1_GRAB, E1_GRAB_DENSE = E1_GRAB_D, E1_PROBE_SLICES = 16, E1_DENSE_HITS = 24;
+static_assert((E1_GRAB_SPARSE & (E1_GRAB_SPARSE - 1u)) == 0, "a long helping's size is a power of two: its claims are aligned by masking");
 
 // 4 / 8 bytes at any byte position of the ring.  (A byte-unaligned ds_read_b32 / _b64 is legal on gfx950 but keeps the LDS busy
 // for ~20 cycles per wave instruction - measured: SQ_LDS_IDX_ACTIVE / SQ_INSTS_LDS - so the reads are dword-aligned and the
@@ -526,37 +536,18 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
         const uint32_t end_lim = (te < bend - LASTLIT) ? te : bend - LASTLIT;
         E1DBG(uint32_t dq = 0; unsigned long long a_deq = 0, a_probe = 0, a_hit = 0, n_step = 0, n_hit = 0, n_deq = 0;)
         bool fresh = true;
-        for (;;) {
-            if ((g.e1_solo & 1u) && tid >= WAVE) break;
-            E1DBG(const unsigned long long z0 = clock64(); n_deq++;)
-            E1DBG(if (++dq > 100000) { if (lane == 0) atomicAdd((unsigned long long*)&scratch[E1_DBG_AT + 0], 1ull); break; })
-            // How many 128-byte slices to take: four where sequences are long (fewer restarts of the search, and of the stride), one
-            // where they are short - the waves then work within 2 KiB of each other, and what a position's nearest earlier
-            // occurrence usually is (text) has been indexed when it is probed.  A tile's first 2 KiB decide for a run's first tile,
-            // the later tiles go by the ones before.
-            // (deterministic parse: the mode word is written by the merge wave whenever it gets there, so it is looked at once per tile,
-            // between the tile's two closing barriers, where the merge of the tile before has long finished)
-            uint32_t mode = (g.e1_solo & 1u) ? mode_tile : uni(__hip_atomic_load(&sh.mode, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-            // The tile's first slice goes to the first wave alone, and the others start when it is through (a poll with a budget:
-            // going ahead without it costs ratio, nothing else).  Where the tile begins inside a long or periodic match - one hot
-            // table slot per distinct four bytes, always holding a position of whoever is furthest ahead - that slice finds it,
-            // publishes its end, and nobody searches what it covers.
-            // (E1_ALIGN, round 4: only a tile that is waited for has an opener.  Otherwise the first wave takes a helping like everybody - the
-            // helpings then start at multiples of their size instead of one slice behind: on the bench input, rows of 512 bytes, a helping
-            // began 128 bytes into a random row and ended 128 bytes into the next one, which cost a second probe step per helping, at stride 1)
-            const bool opener = fresh && wave == 0 && (!E1_ALIGN || hold);
-            const uint32_t grab = opener ? 1u : mode == 1 ? E1_GRAB_SPARSE : mode == 2 ? E1_GRAB_DENSE : 1u;
-            uint32_t si = 0;
-            if (E1_ALIGN && opener) si = uni(atomicAdd(lane == 0 ? &sh.next : &sh.idle[lane], grab));      // (the others wait for sh.first: this is slice 0)
-            if (!opener) {
-                if (fresh && E1_OPENER && ((E1_OPENER == 1 && !E1_ALIGN) || hold)) for (uint32_t spin = 0; spin < 4096 && uni(__hip_atomic_load(&sh.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0; spin++) __builtin_amdgcn_s_sleep(2);
-                si = uni(atomicAdd(lane == 0 ? &sh.next : &sh.idle[lane], grab));
-            }
-            fresh = false;
-            if (si >= nslice) { *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = 0xFFFFFFFFu; break; }
-            *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = si;
-            // The part of the window that every wave has left behind is where the next tile goes: once in a while, ask what the
-            // hindmost wave is at and request the 4 KiB pieces that have become free since (the atomic hands each piece to one wave).
+        E1DBG(unsigned long long z0 = 0;)
+#if E1_V5
+        // Round 5.  What a helping needs and the tile fixes, once per tile instead of once per helping: whether the block may hold a match
+        // at all and the two tile-wide clamps of last_start as ONE limit (0: no position of this tile may start a match), and whether the
+        // tile is sparse from its first helping on - then its mode word, its grab and its first stride are compile-time constants below.
+        const uint32_t lim_t = (!(g.e1_solo & 2u) && blen >= MFLIMIT + 1) ? ((te - MINMATCH < bend - MFLIMIT) ? te - MINMATCH : bend - MFLIMIT) : 0u;
+        const bool tile_plain = !(E1_ALIGN && mode_tile == 1u && !(g.e1_solo & 1u));      // (the mode word as the merge of the tile before last left it: the
+        bool plain = tile_plain || hold;                                                // merge wave's write during this tile counts from the next tile on)
+#endif
+        // the part of the window that every wave has left behind is where the next tile goes: once in a while, ask what the
+        // hindmost wave is at and request the 4 KiB pieces that have become free since (the atomic hands each piece to one wave).
+        auto release = [&](const uint32_t si, const uint32_t grab) __attribute__((always_inline)) {
             if (nlen_full && (si & 31u) < grab) {
                 uint32_t mn = lane < E1_WAVES ? __hip_atomic_load(&sh.cur[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0xFFFFFFFFu;
                 mn = wave_min16(mn);
@@ -565,24 +556,26 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
                 const uint32_t had = uni(atomicMax(lane == 0 ? &sh.pieces[par] : &sh.idle[lane], ok_p));
                 for (uint32_t pc = had; pc < ok_p; pc++) e1_dma_piece(sh, src, org, ts + E1_TILE, pc);
             }
-            // (decided when slice 2 x 16 is handed out: the sixteen waves take the first sixteen together, and their counts arrive when
-            // they are through - deciding at slice 16 saw no hits yet and called every run's first tile sparse)
-            if (mode == 0 && si >= 2 * E1_PROBE_SLICES) {
-                mode = uni(__hip_atomic_load(&sh.hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) > E1_DENSE_HITS ? 2u : 1u;
-                *(lane == 0 ? &sh.mode : &sh.idle[lane]) = mode;
-                mode_tile = mode;
-            }
+        };
+        // ---- one helping: slices si .. si + grab - 1, searched from what the others have covered (ip: sh.cov as read when the helping began) ----
+        auto helping = [&](const uint32_t si, uint32_t ip, const uint32_t mode, const uint32_t grab, const bool opener) __attribute__((always_inline)) {
             const uint32_t cs = ts + si * E1_SLICE;
-            const uint32_t ce = (cs + grab * E1_SLICE < te) ? cs + grab * E1_SLICE : te;
             uint64_t* myrec = spec_t + si * E1_REC_PER_SLICE;
             E1DBG(a_deq += clock64() - z0;)
             uint32_t nrec = 0, anchor = cs;
-            uint32_t ip = uni(__hip_atomic_load(&sh.cov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));      // (a match published by another wave may reach into this slice, or over it)
             if (ip < cs) ip = cs;
+#if E1_V5
+            {
+                // (ip <= last_start says all that the three tests in front of the loop said: ip + MINMATCH <= te, ip + MFLIMIT <= bend, ip < ce)
+                uint32_t last_start = cs + grab * E1_SLICE - 1u;
+                if (lim_t < last_start) last_start = lim_t;
+#else
+            const uint32_t ce = (cs + grab * E1_SLICE < te) ? cs + grab * E1_SLICE : te;
             if (!(g.e1_solo & 2u) && blen >= MFLIMIT + 1 && ip + MINMATCH <= te && ip + MFLIMIT <= bend && ip < ce) {
                 uint32_t last_start = ce - 1;
                 if (te - MINMATCH < last_start) last_start = te - MINMATCH;
                 if (bend - MFLIMIT < last_start) last_start = bend - MFLIMIT;
+#endif
                 const uint32_t floor_b = ip;                               // backward extension stops here
                 uint32_t step = (E1_STEP0 > 1 && mode == 1 && !opener) ? (uint32_t)E1_STEP0 : 1u, two = opener ? 0u : 1u;
                 E1DBG(uint32_t it = 0;)
@@ -829,6 +822,80 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
             *(mine_s ? &sh.s_n[par][si + lane] : (uint8_t*)&sh.idle[lane]) = (uint8_t)(lane == 0 ? nrec : 0u);
             if (mode == 0) atomicAdd(lane == 0 ? &sh.hits : &sh.idle[lane], nrec);
             if (opener) *(lane == 0 ? &sh.first : &sh.idle[lane]) = 1u;
+        };
+        for (;;) {
+            if ((g.e1_solo & 1u) && tid >= WAVE) break;
+            E1DBG(z0 = clock64(); n_deq++;)
+            E1DBG(if (++dq > 100000) { if (lane == 0) atomicAdd((unsigned long long*)&scratch[E1_DBG_AT + 0], 1ull); break; })
+#if E1_V5
+            if (!plain) {
+                // A sparse tile's helpings after its opening: the claim and what the others have covered are asked for together and waited for
+                // once (one LDS round trip on the chain instead of three: mode word, claim, cover), and nothing about the mode is decided here.
+                const uint32_t a = atomicAdd(lane == 0 ? &sh.next : &sh.idle[lane], E1_GRAB_SPARSE);
+                const uint32_t cv = __hip_atomic_load(&sh.cov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __builtin_amdgcn_sched_barrier(0);
+                const uint32_t si = uni(a);
+                if (si >= nslice) { *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = 0xFFFFFFFFu; break; }
+                *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = si;
+                release(si, E1_GRAB_SPARSE);
+                helping(si, uni(cv), 1u, E1_GRAB_SPARSE, false);
+                continue;
+            }
+            plain = tile_plain;                                              // (a tile that is waited for: only its first helpings are special)
+#endif
+            // How many 128-byte slices to take: four where sequences are long (fewer restarts of the search, and of the stride), one
+            // where they are short - the waves then work within 2 KiB of each other, and what a position's nearest earlier
+            // occurrence usually is (text) has been indexed when it is probed.  A tile's first 2 KiB decide for a run's first tile,
+            // the later tiles go by the ones before.
+            // (deterministic parse: the mode word is written by the merge wave whenever it gets there, so it is looked at once per tile,
+            // between the tile's two closing barriers, where the merge of the tile before has long finished)
+            uint32_t mode = (g.e1_solo & 1u) ? mode_tile : uni(__hip_atomic_load(&sh.mode, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+            // The tile's first slice goes to the first wave alone, and the others start when it is through (a poll with a budget:
+            // going ahead without it costs ratio, nothing else).  Where the tile begins inside a long or periodic match - one hot
+            // table slot per distinct four bytes, always holding a position of whoever is furthest ahead - that slice finds it,
+            // publishes its end, and nobody searches what it covers.
+            // (E1_ALIGN, round 4: only a tile that is waited for has an opener.  Otherwise the first wave takes a helping like everybody - the
+            // helpings then start at multiples of their size instead of one slice behind: on the bench input, rows of 512 bytes, a helping
+            // began 128 bytes into a random row and ended 128 bytes into the next one, which cost a second probe step per helping, at stride 1)
+            const bool opener = fresh && wave == 0 && (!E1_ALIGN || hold);
+            uint32_t grab = opener ? 1u : mode == 1 ? E1_GRAB_SPARSE : mode == 2 ? E1_GRAB_DENSE : 1u;
+            uint32_t si = 0;
+            if (E1_ALIGN && opener) si = uni(atomicAdd(lane == 0 ? &sh.next : &sh.idle[lane], grab));      // (the others wait for sh.first: this is slice 0)
+            if (!opener) {
+                if (fresh && E1_OPENER && ((E1_OPENER == 1 && !E1_ALIGN) || hold)) for (uint32_t spin = 0; spin < 4096 && uni(__hip_atomic_load(&sh.first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0; spin++) __builtin_amdgcn_s_sleep(2);
+                bool got = false;
+#if E1_V6
+                // Round 5.  A long helping claimed here - behind the single slices of a run's first tile, behind an opener - ends on a multiple
+                // of its size, so that the helpings after it begin on one (E1_ALIGN's reason; where the single slices end is a matter of timing).
+                // On rows of 512 bytes a helping that began inside a copy row probed it BEFORE the random row behind it, while the helping that
+                // holds its source, begun the same way, had not indexed that yet: every copy row with a source inside the 16 KiB the waves search
+                // at one time went out as literals, in a run's whole first tile, in about every second run (a 70 KiB input: 12 % bigger).
+                // (compare-and-swap with a budget: who runs out of it claims a full helping wherever it begins, as before)
+                if (E1_ALIGN && mode == 1) {
+                    uint32_t n = uni(__hip_atomic_load(&sh.next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    for (uint32_t t = 0; t < 64 && !got; t++) {
+                        const uint32_t tgt = (n & ~(E1_GRAB_SPARSE - 1u)) + E1_GRAB_SPARSE;
+                        const uint32_t old = uni(atomicCAS(lane == 0 ? &sh.next : &sh.idle[lane], n, tgt));
+                        if (old == n) { got = true; si = n; grab = tgt - n; }
+                        n = old;
+                    }
+                }
+#endif
+                if (!got) si = uni(atomicAdd(lane == 0 ? &sh.next : &sh.idle[lane], grab));
+            }
+            fresh = false;
+            if (si >= nslice) { *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = 0xFFFFFFFFu; break; }
+            *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = si;
+            release(si, grab);
+            // (decided when slice 2 x 16 is handed out: the sixteen waves take the first sixteen together, and their counts arrive when
+            // they are through - deciding at slice 16 saw no hits yet and called every run's first tile sparse)
+            if (mode == 0 && si >= 2 * E1_PROBE_SLICES) {
+                mode = uni(__hip_atomic_load(&sh.hits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) > E1_DENSE_HITS ? 2u : 1u;
+                *(lane == 0 ? &sh.mode : &sh.idle[lane]) = mode;
+                mode_tile = mode;
+            }
+            // (a match published by another wave may reach into this helping, or over it)
+            helping(si, uni(__hip_atomic_load(&sh.cov, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)), mode, grab, opener);
         }
         E1DBG(const unsigned long long q2 = clock64();)
         __builtin_amdgcn_s_waitcnt(0);                                   // my slice lists are written
