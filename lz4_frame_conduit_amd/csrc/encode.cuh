@@ -188,6 +188,15 @@ static_assert(64 * E1_WAVES >= E1_NSLICE, "a thread per slice when the lists are
 #ifndef E1_V6
 #define E1_V6 1
 #endif
+// Round 6 (fewer LDS bank conflicts per match; each 0: the form before).  E1_V7: a found match is measured forwards in rows - lane i
+// looks at the four bytes 256 r + 4 i on, E1_ROWS rows per round - so that every read is of consecutive dwords (see e1_rows_ld).
+// Rows per round, on the bench input (tools/ab_run.py, the parent's 2.36 ms): 2: 2.13-2.14 ms, 3: 2.21, 4: 2.25-2.26.
+#ifndef E1_V7
+#define E1_V7 1
+#endif
+#ifndef E1_ROWS
+#define E1_ROWS 2
+#endif
 // Round 4.  Sparse data (long sequences: the mode word says so) is searched from stride 4 on instead of 1: a grab of the bench input is
 // 512 random bytes and a 512-byte copy, and strides 1, 2 / 3, 4 / 5, 6 took 2.8 probe iterations to get across the random half where
 // 4, 5 / 6, 7 take 1.2 - the match is found a few bytes late and the backward extension recovers its start, as it does for liblz4's
@@ -234,6 +243,43 @@ __device__ __forceinline__ uint64_t e1_ld64(const uint8_t* ring, uint32_t pos)
     const e1_w3 w = *(const e1_w3*)(ring + (i & ~3u));
     return (uint64_t)__builtin_amdgcn_alignbyte(w.b, w.a, i & 3u) | ((uint64_t)__builtin_amdgcn_alignbyte(w.c, w.b, i & 3u) << 32);
 }
+#if E1_V7
+// Round 6.  Two places of the ring compared in rows of 256 bytes: lane i of row r has the four bytes at base + 256 r + 4 i and those
+// d bytes in front of them.  A wave's dword reads then go to 64 consecutive dwords - every bank once per group of 32 lanes, no
+// conflict - where 16 bytes per lane (a stride of four dwords) put 32 lanes on 8 banks, 4-way on each of ten dword reads: 80 LDS-array
+// cycles per match instead of 8 per row.  Both byte phases are the wave's, so v_alignbyte takes them from scalar registers.
+// (Each row's addresses are masked by themselves: a round may cross the ring's end; the 16 bytes behind it cover a pair's second dword.)
+static_assert(E1_ROWS >= 1 && E1_ROWS <= 8, "rows per round");
+constexpr uint32_t E1_ROW_BYTES = 4 * 64, E1_ROUND_BYTES = E1_ROWS * E1_ROW_BYTES;
+struct e1_rows { e1_w2 s1[E1_ROWS], s2[E1_ROWS]; };
+__device__ __forceinline__ e1_rows e1_rows_ld(const uint8_t* ring, uint32_t base, uint32_t d, uint32_t lane)
+{
+    e1_rows w;
+#pragma unroll
+    for (uint32_t r = 0; r < E1_ROWS; r++) {
+        const uint32_t a = base + r * E1_ROW_BYTES + lane * 4u;
+        w.s1[r] = *(const e1_w2*)(ring + ((a & E1_RMASK) & ~3u));
+        w.s2[r] = *(const e1_w2*)(ring + (((a - d) & E1_RMASK) & ~3u));
+    }
+    return w;
+}
+// how many bytes of a round agree, from the first on (E1_ROUND_BYTES: all).  k1, k2: the two places' byte phases (wave-uniform).
+// The rows are looked at in order: the first row with a difference, its first lane with one (a ballot and a scalar find-first), that
+// lane's first differing byte.  No branch: where nothing differs lane 63 of the last row answers "4 more".
+__device__ __forceinline__ uint32_t e1_rows_same(const e1_rows& w, uint32_t k1, uint32_t k2)
+{
+    uint32_t xs = 0, off = 0; uint64_t bs = 0;
+#pragma unroll
+    for (int r = E1_ROWS - 1; r >= 0; r--) {
+        const uint32_t x = __builtin_amdgcn_alignbyte(w.s1[r].b, w.s1[r].a, k1) ^ __builtin_amdgcn_alignbyte(w.s2[r].b, w.s2[r].a, k2);
+        const uint64_t b = __ballot(x != 0u);
+        if (r == E1_ROWS - 1 || b) { xs = x; bs = b; off = (uint32_t)r * E1_ROW_BYTES; }
+    }
+    const uint32_t f = (uint32_t)__builtin_ctzll(bs | (1ull << 63));
+    const uint32_t xv = (uint32_t)__builtin_amdgcn_readlane((int)xs, (int)f);
+    return off + f * 4u + (xv ? (uint32_t)(__builtin_ctz(xv) >> 3) : 4u);
+}
+#else
 // five dwords from the dword at or below pos: 16 bytes at any byte position, picked with v_alignbyte by the caller
 struct __attribute__((aligned(4))) e1_w5 { uint32_t a, b, c, d, e; };
 __device__ __forceinline__ e1_w5 e1_ld5(const uint8_t* ring, uint32_t pos)
@@ -250,6 +296,7 @@ __device__ __forceinline__ uint32_t e1_same16(const e1_w5& s1, const e1_w5& s2, 
     const uint64_t lo = (uint64_t)x0 | ((uint64_t)x1 << 32), hi = (uint64_t)x2 | ((uint64_t)x3 << 32);
     return lo ? (uint32_t)(__builtin_ctzll(lo) >> 3) : hi ? 8u + (uint32_t)(__builtin_ctzll(hi) >> 3) : 16u;
 }
+#endif
 __device__ __forceinline__ uint32_t e1_mix(uint32_t v) { return v * 2654435761u; }
 __device__ __forceinline__ uint32_t e1_slot(uint32_t hv) { return hv >> (32 - E1_HASH_LOG); }
 __device__ __forceinline__ uint32_t e1_tag(uint32_t hv) { return (hv >> (24 - E1_HASH_LOG)) & 0xFFu; }
@@ -744,6 +791,18 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
                     {
                         const uint32_t kb = lane + 1;
                         const uint32_t b1 = sh.ring[(mp - kb) & E1_RMASK], b2 = sh.ring[(mp - d - kb) & E1_RMASK];
+#if E1_V7
+                        // (round 6: forwards in rows of consecutive dwords, E1_ROWS x 256 bytes per round - a 512-byte copy of the bench input, found a
+                        // few bytes in, ends in the round it begins in; the limit is one scalar minimum on the count.  Bytes past end_lim are read
+                        // and not counted.)
+                        const e1_rows w = e1_rows_ld(sh.ring, mp, d, lane);
+                        __builtin_amdgcn_sched_barrier(0);
+                        const uint64_t ne = __ballot(b1 != b2 || kb > room);
+                        nb = ne ? (uint32_t)__builtin_ctzll(ne) : WAVE;
+                        const uint32_t n = e1_rows_same(w, mp & 3u, (mp - d) & 3u), cap = end_lim - mp;      // (a match that was found has mp + 4 <= end_lim)
+                        fw = (n == E1_ROUND_BYTES && n < cap) ? (n | 0x80000000u) : (n < cap ? n : cap);      // (all agree and there is more: goes on)
+                    }
+#else
                         const uint32_t a0 = mp + lane * 16;
                         const e1_w5 s1 = e1_ld5(sh.ring, a0), s2 = e1_ld5(sh.ring, a0 - d);
                         __builtin_amdgcn_sched_barrier(0);
@@ -755,6 +814,7 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
                         if (stop) { const uint32_t f = (uint32_t)__builtin_ctzll(stop); fw = f * 16 + (uint32_t)__builtin_amdgcn_readlane(g0, f); }
                         else fw = WAVE * 16 | 0x80000000u;                       // (goes on)
                     }
+#endif
                     for (bool more = nb == WAVE; more;) {                        // (rare: more than 64 bytes backwards)
                         E1DBG(if (++itb > 100000) { if (lane == 0) { atomicAdd((unsigned long long*)&scratch[E1_DBG_AT + 2], 1ull); scratch[E1_DBG_AT + 10] = ((uint64_t)room << 32) | nb; } break; })
                         const uint32_t kb = nb + lane + 1;
@@ -768,6 +828,13 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
                     while (fw >> 31) {
                         fw &= 0x7FFFFFFFu;
                         E1DBG(if (++itf > 100000) { if (lane == 0) { atomicAdd((unsigned long long*)&scratch[E1_DBG_AT + 3], 1ull); scratch[E1_DBG_AT + 11] = ((uint64_t)mp << 32) | fw; scratch[E1_DBG_AT + 12] = ((uint64_t)end_lim << 32) | d; } break; })
+#if E1_V7
+                        const uint32_t a0 = mp + fw;
+                        const e1_rows w = e1_rows_ld(sh.ring, a0, d, lane);
+                        const uint32_t n = e1_rows_same(w, a0 & 3u, (a0 - d) & 3u), cap = end_lim - mp;
+                        fw += n;
+                        fw = (n == E1_ROUND_BYTES && fw < cap) ? (fw | 0x80000000u) : (fw < cap ? fw : cap);
+#else
                         const uint32_t a0 = mp + fw + lane * 16;
                         const e1_w5 s1 = e1_ld5(sh.ring, a0), s2 = e1_ld5(sh.ring, a0 - d);
                         uint32_t g0 = e1_same16(s1, s2, a0 & 3u, (a0 - d) & 3u);
@@ -775,6 +842,7 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
                         const uint64_t stop = __ballot(g0 < 16);
                         if (stop) { const uint32_t f = (uint32_t)__builtin_ctzll(stop); fw += f * 16 + (uint32_t)__builtin_amdgcn_readlane(g0, f); }
                         else fw = (fw + WAVE * 16) | 0x80000000u;
+#endif
                     }
 #else
                     for (;;) {
