@@ -342,7 +342,9 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_index_size(size_t srcSize, const LZ4F_pre
 #define LZ4F_MI355X_INBAND ((size_t)-1)
 /* result.flags: bits 0..7 the frame's FLG byte, bit 8 a skippable frame was skipped; bits 12.. say which way a decompress call
  * went - a pure function of the call's arguments, the frame's header and trailer and the switches the engine was made with,
- * never of earlier calls (tests/test_gpu_parity.py: test_decode_path_by_input_class) */
+ * never of earlier calls (tests/test_gpu_parity.py: test_decode_path_by_input_class).  TRAILER and PARALLEL_WALK say which list
+ * walk was PLANNED; whether its list was the chain of the frame's own size words, and so became the table, is WALK_DELIVERED
+ * (tests/test_gpu_walks.py) */
 #define LZ4F_MI355X_PATH_TABLE_GIVEN   0x001u   /* the caller's block table: no walk */
 #define LZ4F_MI355X_PATH_TRAILER       0x002u   /* the size words' positions came from the frame's trailer (checked link by link) */
 #define LZ4F_MI355X_PATH_PARALLEL_WALK 0x004u   /* the size words were looked for in parallel (small blocks) */
@@ -355,6 +357,7 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_index_size(size_t srcSize, const LZ4F_pre
 #define LZ4F_MI355X_PATH_WAVE_PER_BLOCK 0x200u  /* small independent blocks: a wave per block */
 #define LZ4F_MI355X_PATH_WORKGROUP_PER_BLOCK 0x800u /* few big independent blocks that may be dense: a workgroup per block with the window in LDS was launched beside the fused ones (the payload's density decides on the device which of the two decodes) */
 #define LZ4F_MI355X_PATH_INDEX_DROPPED 0x400u   /* set on the device: the indexed kernels refused the index, the generic ones decoded */
+#define LZ4F_MI355X_PATH_WALK_DELIVERED 0x2000u /* set on the device: the block table and this record's walk came from a list that was accepted link by link (the trailer's, the parallel or the seeded walk's); clear with a caller's table, a serial walk, or a list that was declined and walked again serially */
 /* compress calls, result.flags bit 9: the encoder's record workspace (sized for a sequence per 5.3 input bytes on average - dense text has
  * one per 6..8 - instead of the format's worst case of one per 4: lz4f_mi355x_dev_workspace_size) was used up, and the 64 KiB tiles that
  * found it empty went out as literals.  The frame is valid and decodes to the input, it is only bigger than it could be.

@@ -613,7 +613,7 @@ size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p
         }
         if (list) {
             hipLaunchKernelGGL(k_walk_link, dim3(lgrid), dim3(256), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, list, tbl, n_max);
-            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, list, n_max, res);
+            hipLaunchKernelGGL(k_walk_verdict, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, j.dst_cap, ws, list, n_max, res, p.walk == DecodePlan::WALK_TRAILER ? 1u : 0u);
             WalkState h;
             if (sw.prof && p.walk == DecodePlan::WALK_PARALLEL && prof_read(st, &h, ws, sizeof(h))) fprintf(stderr, "parallel walk: done %u overflow %u candidates %u first_end %u first_break %u (header ok %u, hsize %u, block %u)\n", h.done, h.overflow, h.total, h.first_end, h.first_break, h.head_ok, h.hsize, h.bs);
             if (sw.prof && p.walk == DecodePlan::WALK_SEEDED && prof_read(st, &h, ws, sizeof(h))) fprintf(stderr, "seeded walk: done %u overflow %u entries %u first_end %u first_break %u\n", h.done, h.overflow, h.total, h.first_end, h.first_break);

@@ -619,8 +619,8 @@ __global__ __launch_bounds__(256) void k_walk_link(const uint8_t* __restrict__ f
 
 // the verdict: is the list, from the first byte behind the header to its first EndMark, one unbroken chain?
 __global__ void k_walk_verdict(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint64_t dst_cap, WalkState* __restrict__ ws,
-                               const uint64_t* __restrict__ list, uint32_t table_cap, ResultRec* __restrict__ res)
-{
+                               const uint64_t* __restrict__ list, uint32_t table_cap, ResultRec* __restrict__ res, uint32_t exact = 0)
+{   // exact (a trailer's list): the list must END where the chain ends - a trailer that names more blocks than the frame has is a lying one
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (!ws->head_ok || ws->overflow) return;
     const uint32_t hsize = ws->hsize, bs = ws->bs, bck = ws->bck, flg = ws->flg;
@@ -628,19 +628,22 @@ __global__ void k_walk_verdict(const uint8_t* __restrict__ frame, uint64_t frame
     if (ws->total == 0 || list[0] != hsize) {
         // no block at all?  then the EndMark follows the header
         if (frame_cap - pos < 4 || *(const u32_ua*)(frame + pos) != 0) return;
+        if (exact && ws->total) return;
         pos += 4;
     } else {
         const uint32_t e = ws->first_end;
         if (e == 0xFFFFFFFFu || ws->first_break <= e || e >= table_cap) return;
         if ((uint64_t)e * bs >= dst_cap) return;                      // (no room: k_walk_frame says so)
         n = e + 1;
+        if (exact && n != ws->total) return;
         const uint64_t p = list[e];
         pos = p + 4 + word_size(*(const u32_ua*)(frame + p)) + 4 * bck + 4;           // behind the EndMark
     }
     uint32_t tail;                                                                   // content checksum
     if (frame_end(flg, frame_cap - pos, tail)) return;
     pos += tail;
-    ResultRec r; r.size = ws->content; r.consumed = pos; r.status = ST_OK; r.n_blocks = n; r.first_bad_block = 0xFFFFFFFFu; r.flags = flg;
+    ResultRec r; r.size = ws->content; r.consumed = pos; r.status = ST_OK; r.n_blocks = n; r.first_bad_block = 0xFFFFFFFFu;
+    r.flags = flg | (LZ4F_MI355X_PATH_WALK_DELIVERED << 12);          // (k_finish_decode keeps this one path bit: the list was the walk)
     *res = r;
     ws->done = 1;
 }
@@ -895,7 +898,8 @@ __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __
                                                       uint64_t dst_cap = ~0ull)
 {   // check_here (n_max <= 64): what k_finish_check leaves in bad_ck[1], [2], [4..5] is worked out by this wave itself - a launch less for calls of a few blocks
     // which way the call went (lz4f_mi355x.h: LZ4F_MI355X_PATH_*): what the host launched, and whether the indexed kernels gave up
-    if (lane_id() == 0) res->flags = (res->flags & 0xFFFu) | (plan << 12) | ((ix_flags && *ix_flags) ? (LZ4F_MI355X_PATH_INDEX_DROPPED << 12) : 0u);
+    // (and whether a list walk's list became the table: k_walk_verdict's bit, the only one that comes in with the record)
+    if (lane_id() == 0) res->flags = (res->flags & (0xFFFu | (LZ4F_MI355X_PATH_WALK_DELIVERED << 12))) | (plan << 12) | ((ix_flags && *ix_flags) ? (LZ4F_MI355X_PATH_INDEX_DROPPED << 12) : 0u);
     if (res->status != ST_OK) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     uint32_t n_scan = n;

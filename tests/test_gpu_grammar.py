@@ -46,6 +46,7 @@ PATH = dict(table=0x001, parallel_walk=0x004, indexed=0x008, self_index=0x010, d
             wave_per_block=0x200, workgroup_per_block=0x800)
 GUARD = 4096
 DROPPED = 0x400                  # the indexed kernels gave up and the generic ones decoded
+WALK_DELIVERED = 0x2000          # a guessed list of size words was accepted: names no decoder, so not in PATH (tests/test_gpu_walks.py pins it)
 PIECES_MAX = 300 << 10           # frames fed in 1..300-byte pieces: up to this size (the rest is thousands of calls each)
 
 
@@ -225,7 +226,7 @@ def test_every_decoder_on_the_grammar_corpus(L, cases, ei):
         L.lz4f_mi355x_release_engines()
     SEEN[ei] = seen
     print("grammar corpus under %s: %d cases x entry points = %d decodes; path bits: %s"
-          % (env or "{}", len(cases), runs, " ".join(sorted(k for k, v in PATH.items() if seen & v))))
+          % (env or "{}", len(cases), runs, " ".join(sorted(k for k, v in PATH.items() if seen & v)) + (" walk_delivered" if seen & WALK_DELIVERED else "")))
     for (entry, err), n in sorted(collections.Counter((e.split("@")[0], x) for _, e, x in bad).items()):
         print("  disagreement: %-14s %-45s x%d" % (entry, err, n))
     for b in bad:

@@ -56,7 +56,7 @@ PREF_SETS = {"default": {}, "cli": dict(bsid=7, indep=1, cck=1), "cli_bck": dict
              "indep64k_bck": dict(bsid=4, indep=1, bck=1), "linked256k_cck": dict(bsid=5, indep=0, cck=1)}
 # result.flags >> 12 (include/lz4f_mi355x.h: LZ4F_MI355X_PATH_*)
 PATH = dict(table=0x001, trailer=0x002, parallel_walk=0x004, indexed=0x008, self_index=0x010, doubling=0x020, hops=0x040, window=0x080, fused=0x100,
-            wave_per_block=0x200, dropped=0x400, workgroup_per_block=0x800)
+            wave_per_block=0x200, dropped=0x400, workgroup_per_block=0x800, walk_delivered=0x2000)
 SMALL_INPUTS = ["hello20", "empty", "rep42", "ints", "hello100k", "tiny12", "tiny13"]
 
 
@@ -869,6 +869,11 @@ def test_parallel_walk_of_device_frames(L, monkeypatch):
                 r = en.result()
                 assert r.size == src.numel() and r.consumed == len(ref) and torch.equal(back, src), (name, kw, serial)
                 assert bool((r.flags >> 12) & PATH["parallel_walk"]) == (not serial and len(ref) >= (1 << 20)), (name, kw, serial, hex(r.flags))
+                # whether the list delivered is reported (tests/test_gpu_walks.py pins it on planted frames; for these inputs either is right):
+                # never on the serial engine, never without a list walk
+                delivered = bool((r.flags >> 12) & PATH["walk_delivered"])
+                assert not delivered or (not serial and len(ref) >= (1 << 20)), (name, kw, serial, hex(r.flags))
+                if not serial: print("parallel walk of %s %s: %s" % (name, kw, "delivered" if delivered else "left to the serial walk"))
                 results.append((int(r.n_blocks), int(r.consumed)))
             assert results[0] == results[1], (name, kw, results)
     eng.close(); eng_serial.close()
