@@ -402,6 +402,28 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, u
                                                         const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                         void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
                                                         lz4f_mi355x_result* d_results);
+/* The same with a SHARED DICTIONARY: one dictionary for the whole batch, as LZ4F_decompress_usingDict applies one to a frame.  The history
+ * in front of a frame's output (linked blocks), or in front of every block (independent blocks), is the dictionary: a match offset is
+ * valid if and only if 0 < offset <= bytes in front in that scope + dictSize, and a match may begin in the dictionary and run on into
+ * the output (and into the bytes it writes itself).  Frames that liblz4 made with LZ4F_compressFrame_usingCDict /
+ * LZ4F_compressBegin_usingCDict decode here with the same dictionary, and the frames of lz4f_mi355x_dev_compressFrames_usingDict.
+ *   - d_dict: dictSize bytes of DEVICE memory at any byte address, read only; it must stay valid until the stream has run the call and
+ *     must not overlap d_dst.  Only the last 64 KiB of a longer dictionary are used (the pointer is advanced on the host).
+ *   - dictSize == 0 (d_dict may then be NULL) is lz4f_mi355x_dev_decompressFrames for the same arguments: the same bytes, the same records.
+ *     d_dict == NULL with dictSize > 0 and n_frames > 0 is a call error, like the other null pointers.
+ *   - The header's dictID is never interpreted and never checked (liblz4 does not check it either): matching IDs to dictionaries is the
+ *     caller's job.  A frame decoded with the wrong dictionary decodes to wrong bytes, caught only by a content checksum.
+ *   - Everything said above about the plain call holds: spans, windows, isolation, the offset checks (nothing is read outside
+ *     [d_dict, d_dict + dictSize) on the dictionary's behalf: the offset is checked before any read), the record's fields,
+ *     LZ4F_MI355X_PATH_BATCH, the workspace from the arguments alone, no host synchronisation, a launch count that does not depend on
+ *     n_frames, any byte alignment.  With a dictionary every block, independent ones too, goes through the wave-per-block decoder
+ *     that parses on the scalar unit.
+ *   - lz4f_mi355x_dev_measureFrames never looks at offsets: "measure, then decode with the dictionary" works with it as it is.
+ * Not covered: the single-frame device calls, the host-pointer and streaming LZ4F_* calls, the conduits. */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                                  const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                                  void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                                  lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize);
 #define LZ4F_MI355X_PATH_BATCH 0x1000u   /* result.flags bits 12..: the frame went through the batch decoder (dev_decompressFrames), or was made by the batch encoder (dev_compressFrames) */
 
 /* BATCH MEASURE: what n_frames frames decode to, and the windows lz4f_mi355x_dev_decompressFrames needs for them, without decoding:
@@ -443,7 +465,9 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, u
  *     blocks can overflow the table: the frames behind the overflow are measured a wave per frame, in order, with identical results.
  *   - The call itself fails only on a null engine, a null pointer with n_frames > 0 (d_dst_off excepted), or a failed allocation.
  *     n_frames == 0 returns 0 and enqueues nothing.
- * Every block of every frame, linked ones included (a size needs no history), is measured by a wave of its own. */
+ * Every block of every frame, linked ones included (a size needs no history), is measured by a wave of its own.
+ * Frames made with a dictionary measure like any other (offsets are not looked at): measure, then decode the same spans with
+ * lz4f_mi355x_dev_decompressFrames_usingDict and the d_dst_off this call wrote. */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames,
                                                      const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                      uint64_t* d_dst_off, lz4f_mi355x_result* d_results);
@@ -486,6 +510,29 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uin
                                                       const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                       void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
                                                       const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results);
+
+/* The same with a SHARED DICTIONARY (the batch's LZ4F_compressFrame_usingCDict): the match finder may reach into the dictionary as if
+ * it lay in front of every input (linked blocks), or in front of every block (independent blocks).  Small records, which have next to
+ * nothing in front of them to match against, are what this is for.  Frame i decodes to input i with the same dictionary, through
+ * lz4f_mi355x_dev_decompressFrames_usingDict and through liblz4's LZ4F_decompress_usingDict.
+ *   - d_dict / dictSize: as for lz4f_mi355x_dev_decompressFrames_usingDict - device memory at any byte address, read only, valid until
+ *     the stream has run the call, not overlapping d_dst; the last 64 KiB of a longer one; a dictionary of fewer than 4 bytes changes
+ *     nothing (as with LZ4_loadDict).  dictSize == 0 (d_dict may be NULL) is lz4f_mi355x_dev_compressFrames: the same bytes and records.
+ *     d_dict == NULL with dictSize > 0 and n_frames > 0 is a call error.
+ *   - prefs->frameInfo.dictID is written to the header as before and means nothing else to this library: it is not derived from the
+ *     dictionary and not checked on decode.  Matching IDs to dictionaries is the caller's job.
+ *   - compressionLevel 3-12 with dictSize > 0: the call returns ERROR_compressionLevel_invalid and enqueues nothing (the hash-chain
+ *     finder does not know the dictionary yet).  Levels <= 2 take it.
+ *   - Frame i is a function of input i, the dictionary and prefs alone: the same bytes in a batch of one and in a batch of many.  A
+ *     match is cut where the dictionary ends and the input begins (liblz4 may let one run across; the decoders take both).
+ *   - Everything said above about the plain call holds: spans, windows, isolation, the record's fields, LZ4F_MI355X_PATH_BATCH, the
+ *     workspace formula (the dictionary adds nothing to it), no host synchronisation, a launch count independent of n_frames.
+ * Every 64 KiB chunk's wave seeds its hash table from the dictionary: a small record pays for up to 64 KiB of seeding. */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                                const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                                void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                                const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
+                                                                const void* d_dict, size_t dictSize);
 
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,

@@ -46,9 +46,15 @@ __device__ __forceinline__ uint64_t fetch8(const uint8_t* __restrict__ in_al, ui
 // LIM (the batch decoder's tight last block, decode_batch.cuh): the block is judged by `cap` but only the first `wlim` (<= cap)
 // bytes may be written - a run that would end beyond wlim is not copied and the parse goes on, so that a block that decodes,
 // only not into wlim, returns -2 and one that does not decode at all -1.  Without LIM wlim is not looked at (wave_decode_block).
-template <bool LIM>
+// DICT (the batch decoder's shared dictionary, decode_batch.cuh): the history goes on in front of the `hist` bytes with the dict_len
+// bytes that end at dict_end - [dictionary | hist bytes | out].  An offset is valid iff it is <= op + hist + dict_len, checked before
+// anything is read; a match whose source begins k > 0 bytes in front of the hist bytes is copied in two parts: min(mlen, k) bytes from
+// the dictionary's end (disjoint), the rest as an ordinary match copy with the same offset - its source is then the first of the hist
+// bytes, so a match that crosses the seam, or runs through it into what it writes itself, falls out right.
+template <bool LIM, bool DICT = false>
 __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restrict__ in, uint32_t csize,
-                                                         uint8_t* out, uint32_t cap, uint32_t wlim, uint64_t hist)
+                                                         uint8_t* out, uint32_t cap, uint32_t wlim, uint64_t hist,
+                                                         const uint8_t* dict_end = nullptr, uint32_t dict_len = 0)
 {
     bool over = false;                         // (LIM: something was not written)
     auto fits = [&](uint32_t op, uint32_t len) -> bool {
@@ -67,6 +73,9 @@ __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restri
     const uint32_t oend = cap;
 
     for (;;) {
+        // (DICT: the two-part copy ends in a lane-predicated branch that the compiler joins at this loop's head, where it then takes the
+        // cursors for lane-dependent - and fetch8's scalar loads want them in scalar registers)
+        if constexpr (DICT) { ip = uni(ip); op = uni(op); }
         // ---- token + literal length -------------------------------------------------------
         uint64_t w = fetch8(in_al, ip, lim4);
         const uint32_t token = (uint32_t)w & 0xFF;
@@ -104,7 +113,7 @@ __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restri
         const uint32_t offset = (uint32_t)w & 0xFFFF;
         ip += 2;
         if (offset == 0) return -1;
-        if ((uint64_t)offset > (uint64_t)op + hist) return -1;
+        if ((uint64_t)offset > (uint64_t)op + hist + (DICT ? dict_len : 0u)) return -1;
         uint32_t mlen = token & 15;
         if (mlen == 15) {
             w >>= 16;
@@ -122,7 +131,14 @@ __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restri
         }
         mlen += 4;
         if ((uint64_t)mlen + 5 > (uint64_t)(oend - op)) return -1;       // last 5 bytes must be literals
-        if (fits(op, mlen)) wave_copy_match(out + op, offset, mlen);
+        if (DICT && (uint64_t)offset > (uint64_t)op + hist) {
+            const uint32_t k = (uint32_t)((uint64_t)offset - ((uint64_t)op + hist));      // (<= dict_len, by the check above)
+            const uint32_t n1 = mlen < k ? mlen : k;
+            if (fits(op, mlen)) {
+                wave_copy_disjoint(out + op, dict_end - k, n1);
+                if (mlen > n1) wave_copy_match(out + op + n1, offset, mlen - n1);
+            }
+        } else if (fits(op, mlen)) wave_copy_match(out + op, offset, mlen);
         op += mlen;
     }
 }

@@ -18,6 +18,13 @@
 //                every frame's content checksum - the chains of different frames run side by side - and the result record
 // Nothing is written outside a frame's window on its behalf: every decode is bounded by the block's room inside the window, and
 // the one decode that is judged against a whole block (the tight last block, k_redo_tight_block's rule) only writes what fits.
+//
+// THE SHARED DICTIONARY (lz4f_mi355x_dev_decompressFrames_usingDict).  One dictionary for the whole batch: the history in front of a
+// frame's output (linked blocks), or in front of every block (independent blocks), is the dictionary's last <= 64 KiB, as
+// LZ4F_decompress_usingDict has it.  The kernels that decode blocks exist a second time, k_bf_*_dict: the same bodies with DICT set,
+// every block through the scalar-parse decoder (wave_decode_block_lim<true, true>: the offset check and the two-part match copy are
+// there, decode.cuh) - independent blocks too, which the plain call gives to wave_decode_block_win.  The plain call's kernels are
+// the DICT = false instantiations: what they were.
 #pragma once
 #include "common.cuh"
 #include "decode.cuh"
@@ -38,10 +45,16 @@ struct BatchBlk {                           // block table entry (40 bytes)
 
 // wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
 // decodes but not into wlim
+struct BfDict {                              // the batch's dictionary: the len (<= 64 KiB) bytes that end at `end`
+    const uint8_t* end;
+    uint32_t len;
+};
+template <bool DICT = false>
 __device__ __forceinline__ int32_t bf_decode_block(const uint8_t* __restrict__ in, uint32_t csize, uint8_t* out, uint32_t cap, uint32_t wlim,
-                                                   uint64_t hist)
+                                                   uint64_t hist, const BfDict& dc = BfDict{nullptr, 0u})
 {
-    return wave_decode_block_lim<true>(in, csize, out, cap, wlim, hist);
+    if constexpr (DICT) return wave_decode_block_lim<true, true>(in, csize, out, cap, wlim, hist, (const uint8_t*)uni64((uint64_t)dc.end), uni(dc.len));
+    else return wave_decode_block_lim<true>(in, csize, out, cap, wlim, hist);
 }
 
 // dst[0..len) = src[0..len) with dst < src (a block of an independent frame moved down to where the blocks in front of it end)
@@ -61,9 +74,11 @@ __device__ __forceinline__ void bf_move_down(uint8_t* dst, const uint8_t* src, u
 }
 
 // the tight last block (k_redo_tight_block): judged against a whole block, written only if it fits.  -> size, -2 or -3
-__device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz, uint8_t* out, uint32_t bs, uint32_t room, uint64_t hist)
+template <bool DICT = false>
+__device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz, uint8_t* out, uint32_t bs, uint32_t room, uint64_t hist,
+                                                 const BfDict& dc = BfDict{nullptr, 0u})
 {
-    const int32_t g = bf_decode_block(in, csz, out, bs, room, hist);
+    const int32_t g = bf_decode_block<DICT>(in, csz, out, bs, room, hist, dc);
     return g == -1 ? -3 : g;
 }
 
@@ -110,11 +125,11 @@ __global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ sr
 
 // the grid is sized by the host's bound on the table, capped (engine.hip: BATCH_GRID): the waves stride over the entries in
 // use (ctl[0]), so a small batch into a big destination buffer does not launch a workgroup per 64 KiB of it
-template <int W>
-__global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
-                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
+template <int W, bool DICT>
+__device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
+                                               uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl,
+                                               uint32_t (*expand)[64], const BfDict& dc)
 {
-    __shared__ uint32_t expand[W][64];
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t total = uni(ctl[0]);
     for (uint32_t w = uni(blockIdx.x * W + wv); w < total; w += gridDim.x * W) {
@@ -135,16 +150,32 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restri
         if (word_stored(word)) {
             if (csz > room) got = -2;
             else { wave_copy_disjoint(dst + dof, src + so, csz); got = (int32_t)csz; }
+        } else if constexpr (DICT) {
+            got = bf_decode_block<true>(src + so, csz, dst + dof, room, room, 0, dc);
         } else {
             got = wave_decode_block_win<true>(src + so, csz, span_end - so, dst + dof, room, expand[wv]);
         }
         if (lane_id() == 0) { table[w].got = got; table[w].ck = ck; }
     }
 }
+template <int W>
+__global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
+                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
+{
+    __shared__ uint32_t expand[W][64];
+    bf_blocks_body<W, false>(src, dst, frames, n_frames, table, ctl, expand, BfDict{nullptr, 0u});
+}
+template <int W>
+__global__ __launch_bounds__(64 * W, 8) void k_bf_blocks_dict(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
+                                                             uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl, BfDict dc)
+{
+    bf_blocks_body<W, true>(src, dst, frames, n_frames, table, ctl, nullptr, dc);
+}
 
 // a wave per frame without a table slice: blocks in order
-template <int W>
-__global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
+template <int W, bool DICT>
+__device__ __forceinline__ void bf_serial_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                               const BfDict& dc)
 {
     const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
     if (i >= n_frames) return;
@@ -168,9 +199,9 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restri
             if (csz > room) got = -2;
             else { wave_copy_disjoint(o + at, in, csz); got = (int32_t)csz; }
         } else {
-            got = bf_decode_block(in, csz, o + at, room, room, linked ? at : 0);
+            got = bf_decode_block<DICT>(in, csz, o + at, room, room, linked ? at : 0, dc);
             if (got < 0 && b + 1 == n && csz && win % bs != 0 && win - at < bs)
-                got = bf_redo_tight(in, csz, o + at, bs, room, linked ? at : 0);
+                got = bf_redo_tight<DICT>(in, csz, o + at, bs, room, linked ? at : 0, dc);
         }
         if (got < 0) return block_fail_status(got, at, win, bs);
         if (at != out) bf_move_down(o + out, o + at, (uint32_t)got);
@@ -185,12 +216,23 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restri
         }
     }
 }
-
 template <int W>
-__global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                                      const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check)
+__global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
+    bf_serial_body<W, false>(src, dst, frames, n_frames, BfDict{nullptr, 0u});
+}
+template <int W>       // (held to 8 waves a SIMD, as k_bf_serial is, the two-part copy spills to scratch: 6 it is)
+__global__ __launch_bounds__(64 * W, 4) void k_bf_serial_dict(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                                             BfDict dc)
+{
+    bf_serial_body<W, true>(src, dst, frames, n_frames, dc);
+}
+
+template <int W, bool DICT>
+__device__ __forceinline__ void bf_finish_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                               const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
+                                               uint32_t (*park)[XXH_PARK / 4], const BfDict& dc)
+{
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t i = uni(blockIdx.x * W + wv);
     if (i >= n_frames) return;
@@ -211,7 +253,7 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
         const uint64_t last_at = (uint64_t)(n - 1) * bs;
         const uint32_t lw = uni(t[n - 1].word), lcsz = word_size(lw);
         if (uni((uint32_t)last) >> 31 && !word_stored(lw) && lcsz && win % bs != 0 && win - last_at < bs)
-            last = bf_redo_tight(src + uni64(t[n - 1].src), lcsz, o + last_at, bs, uni(t[n - 1].room), 0);
+            last = bf_redo_tight<DICT>(src + uni64(t[n - 1].src), lcsz, o + last_at, bs, uni(t[n - 1].room), 0, dc);
         last = (int32_t)uni((uint32_t)last);
         uint32_t bad, ck = BF_NONE; int32_t kind; bool moves = false; uint64_t sum;
         slice_verdict(n, bad, kind, sum, [&](uint32_t b) -> int32_t {
@@ -250,6 +292,21 @@ __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict_
         x.flags = (flg & 0xFFFu) | (LZ4F_MI355X_PATH_BATCH << 12);
         results[i] = x;
     }
+}
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                                      const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
+    bf_finish_body<W, false>(src, dst, frames, n_frames, table, results, content_check, park, BfDict{nullptr, 0u});
+}
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_bf_finish_dict(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
+                                                           const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
+                                                           BfDict dc)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
+    bf_finish_body<W, true>(src, dst, frames, n_frames, table, results, content_check, park, dc);
 }
 
 }  // namespace lz4f

@@ -17,6 +17,7 @@
 //   k_bc_find_*    the deterministic match finders over the chunk table: solo_find_chunk (encode_solo.cuh, a wave per chunk, levels
 //                  <= 2) or hc_find_chunk (encode_hc.cuh, a workgroup per chunk, levels 3-12) - the very functions the single call's
 //                  kernels run, so a frame's records are what they would be alone
+//                  (k_bc_find_solo_dict: the same finder with the call's shared dictionary in front of every low_abs)
 //   k_bc_layout    a wave per block: layout_block_chunks (pass S's per-block step: carries, raw fallback) -> the size word
 //   k_bc_frames    a wave per frame: the blocks placed behind the header, the window judged, then header (made here: content size and
 //                  HC byte are the frame's own), size words, EndMark, every chunk's place in the destination, the result record
@@ -174,6 +175,24 @@ __global__ __launch_bounds__(64) void k_bc_find_solo(const uint8_t* __restrict__
         if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
         const EncPlace pl = bc_place_of(e);
         solo_find_chunk(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), s_table, s_tag);
+    }
+}
+// the same with the batch's shared dictionary (lz4f_mi355x_dev_compressFrames_usingDict): the dict_len (<= 64 KiB) bytes that end at
+// dict_end lie in front of every chunk's low_abs (solo_find_chunk<true>).  The dictionary is the call's, not a chunk's: the chunk table
+// and the workspace are what they are without it
+__global__ __launch_bounds__(64) void k_bc_find_solo_dict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
+                                                          const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
+                                                          ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool,
+                                                          const uint8_t* __restrict__ dict_end, uint32_t dict_len)
+{
+    __shared__ uint16_t s_table[SOLO_HASH_SIZE];
+    __shared__ uint8_t s_tag[SOLO_HASH_SIZE];
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BcChunk e = chunks[w];
+        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
+        const EncPlace pl = bc_place_of(e);
+        solo_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), s_table, s_tag, dict_end, dict_len);
     }
 }
 

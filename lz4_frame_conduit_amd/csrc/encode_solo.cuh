@@ -10,6 +10,14 @@
 // shared between waves, so the records are a function of the input alone.  The history in front of a chunk (64 KiB, or back to the
 // block's start) is seeded into the table sparsely, its last KiB densely, so matches reach back across chunk boundaries.
 // Same record and ChunkInfo format as pass E1 of encode.cuh: passes S and E2 do not know the difference.
+//
+// DICT (the batch encoder's shared dictionary, encode_batch.cuh): what lies in front of low_abs is the dictionary's tail, so the window in
+// front of a chunk is [dictionary tail | input from low_abs] and `back` the smaller of 64 KiB and (bytes from low_abs + the dictionary's).
+// Positions below `seam` address the dictionary.  It is seeded by the same scheme (a seed whose four bytes would straddle the seam is
+// left out).  The seam policy: a match is CUT at the seam - a candidate in the dictionary extends backwards within the dictionary and
+// forwards up to the dictionary's end, a candidate in the input does not extend backwards into the dictionary - so a match's source
+// lies on one side, and no load straddles the two buffers.  A dictionary of fewer than 4 bytes is ignored (as LZ4_loadDict does).
+// Records carry distances only, and a distance may now exceed the position in the block: passes S and E2 never look at it.
 #pragma once
 #include "encode.cuh"
 
@@ -27,15 +35,27 @@ __device__ __forceinline__ uint32_t solo_slot(uint32_t hv) { return ((hv >> (32 
 // One chunk, one wave: the search itself, for a chunk whose place is resolved (EncPlace, encode.cuh) - by k_find_matches_solo from the
 // call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `table` / `tags`: the wave's own, in LDS; `rec`: the
 // chunk's record list (max_rec records of room; !rec_room: none, the chunk goes out as literals).
+template <bool DICT = false>
 __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
                                                 uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
-                                                uint16_t* table, uint8_t* tags)
+                                                uint16_t* table, uint8_t* tags, const uint8_t* dict_end = nullptr, uint32_t dict_len = 0)
 {
     const uint32_t lane = lane_id();
     const uint64_t bstart = pl.bstart, bend_abs = pl.bend_abs, cs_abs = pl.cs_abs, ce_abs = pl.ce_abs, low_abs = pl.low_abs;
-    const uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
-    const uint8_t* base = src + (cs_abs - back);                     // position 0
+    uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
+    uint32_t seam = 0;                                               // DICT: positions below it are the dictionary's
+    if constexpr (DICT) {
+        if (dict_len >= 4 && back < 65536u) { seam = 65536u - back < dict_len ? 65536u - back : dict_len; back += seam; }
+    }
+    const uint8_t* base = src + (cs_abs - back);                     // position 0 (DICT: positions from seam on)
+    const uint8_t* dbase = dict_end - seam;                          // DICT: position 0, for positions below seam
     const uint8_t* rd_end = src + pl.rd_end;                         // nothing is read at or beyond this
+    auto at_pos = [&](uint32_t p) -> const uint8_t* { return DICT && p < seam ? dbase + p : base + p; };
+    // 8 bytes of a match's source at position sp; in the dictionary: nothing at or beyond the seam (zeros instead)
+    auto src8 = [&](uint32_t sp, bool in_dict) -> uint64_t {
+        if (DICT && in_dict) return sp < seam ? ld64_guard(dbase + sp, dict_end) : 0ull;
+        return ld64_guard(base + sp, rd_end);
+    };
     const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
     const uint32_t bend = back + (uint32_t)(bend_abs - cs_abs);
 
@@ -44,7 +64,40 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
     // roughly the density the skip-accelerated search itself leaves behind), then the last SEED_DENSE bytes densely.
     for (uint32_t i = lane; i < SOLO_HASH_SIZE / 2; i += WAVE) ((uint32_t*)table)[i] = 0;
     for (uint32_t i = lane; i < SOLO_HASH_SIZE * sizeof(uint8_t) / 4; i += WAVE) ((uint32_t*)tags)[i] = 0;
-    if (back >= 4) {
+    if (DICT && seam) {
+        // the same scheme over [dictionary tail | input]: a lane's 16 bytes lie on one side of the seam, or its seeds go in one by one
+        const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
+        constexpr int SEED_IN_FLIGHT = 8;
+        auto ok4 = [&](uint32_t p) -> bool { return p + 4 <= seam || (p >= seam && p + 4 <= back); };
+        auto put = [&](uint32_t p, uint32_t v) { const uint32_t hv = v * 2654435761u; table[solo_slot(hv)] = (uint16_t)p; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); };
+        for (uint32_t q = 0; q < dense_from; q += SEED_IN_FLIGHT * 1024) {
+            uint4 vv[SEED_IN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < SEED_IN_FLIGHT; u++) {
+                const uint32_t p = q + u * 1024 + lane * 16;
+                vv[u] = uint4{0u, 0u, 0u, 0u};
+                if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) { const b16_ua t = *(const b16_ua*)at_pos(p); vv[u] = uint4{t.a, t.b, t.c, t.d}; }
+            }
+#pragma unroll
+            for (int u = 0; u < SEED_IN_FLIGHT; u++) {
+                const uint32_t p = q + u * 1024 + lane * 16;
+                if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) {
+                    const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+                    for (int k = 0; k < 4; k++) put(p + 4 * k, w[k]);
+                } else {
+                    for (uint32_t k = 0; k < 4; k++) { const uint32_t pk = p + 4 * k; if (pk < dense_from && ok4(pk)) put(pk, ld32(at_pos(pk))); }
+                }
+            }
+        }
+        for (uint32_t q = dense_from; q + 4 <= back; q += SEED_IN_FLIGHT * WAVE) {       // (inserted in position order: later ones win)
+            uint32_t vv[SEED_IN_FLIGHT];
+#pragma unroll
+            for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; vv[u] = ok4(p) ? ld32(at_pos(p)) : 0u; }
+#pragma unroll
+            for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; if (ok4(p)) put(p, vv[u]); }
+        }
+    } else if (back >= 4) {
         const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
         const uint32_t ss = SOLO_SEED_STRIDE;
         constexpr int SEED_IN_FLIGHT = 16;                                           // loads in flight per wave (registers are plentiful: LDS bounds the occupancy)
@@ -159,18 +212,27 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
             uint8_t bb0 = 0, bb1 = 1;
             uint64_t x0 = 0;
             uint32_t a0 = 0;
+            bool cd = false;
+            // DICT: the bytes a lane may count at source position sp
+            auto seam_cap = [&](uint32_t g, uint32_t sp) -> uint32_t {
+                if (!(DICT && cd)) return g;
+                const uint32_t lim = sp < seam ? seam - sp : 0u;
+                return g < lim ? g : lim;
+            };
             while (cA | cB) {
                 hitB = cA == 0;
                 if (!hitB) { L = (uint32_t)__builtin_ctzll(cA); cA &= cA - 1; } else { L = (uint32_t)__builtin_ctzll(cB); cB &= cB - 1; }
                 mp = __builtin_amdgcn_readlane(hitB ? pB : pA, L);
                 mc = __builtin_amdgcn_readlane(hitB ? candB : candA, L);
                 dist = mp - mc;
-                room = mp - anchor; if (mc < room) room = mc;
+                cd = DICT && mc < seam;                                          // a candidate in the dictionary: its match ends at the seam
+                if (cd && seam - mc < MINMATCH) continue;
+                room = mp - anchor; if (mc - (cd ? 0u : seam) < room) room = mc - (cd ? 0u : seam);
                 bb0 = 0; bb1 = 1;
-                if (kb <= room) { bb0 = base[mp - kb]; bb1 = base[mc - kb]; }
+                if (kb <= room) { bb0 = base[mp - kb]; bb1 = *at_pos(mc - kb); }
                 a0 = mp + lane * 8;
                 x0 = 0;
-                if (a0 < end_lim) x0 = ld64_guard(base + a0, rd_end) ^ ld64_guard(base + (a0 - dist), rd_end);
+                if (a0 < end_lim) x0 = ld64_guard(base + a0, rd_end) ^ src8(a0 - dist, cd);
                 if (__builtin_amdgcn_readlane((uint32_t)x0, 0) == 0) { found = true; break; }       // mp + 4 <= end_lim always
             }
             if (!found) {                                                           // both steps missed: advance two steps, top up the queue
@@ -200,7 +262,7 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
                     uint32_t r2 = room - WAVE, m2 = mp - WAVE, c2 = mc - WAVE;
                     while (r2) {
                         const bool in = kb <= r2;
-                        const bool eq = in && base[m2 - kb] == base[c2 - kb];
+                        const bool eq = in && base[m2 - kb] == *at_pos(c2 - kb);
                         const uint64_t ne2 = __ballot(!eq);
                         const uint32_t n2 = ne2 ? (uint32_t)__builtin_ctzll(ne2) : WAVE;
                         nb += n2; m2 -= n2; c2 -= n2; r2 -= n2;
@@ -210,7 +272,7 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
                 mp -= nb; mc -= nb; mlen += nb;
                 // forward: the first 512 bytes came with the verification; longer matches go on below
                 uint32_t g0 = 0;
-                if (a0 < end_lim) { g0 = x0 ? (uint32_t)(__builtin_ctzll(x0) >> 3) : 8; const uint32_t r = end_lim - a0; if (g0 > r) g0 = r; }
+                if (a0 < end_lim) { g0 = x0 ? (uint32_t)(__builtin_ctzll(x0) >> 3) : 8; const uint32_t r = end_lim - a0; if (g0 > r) g0 = r; g0 = seam_cap(g0, a0 - dist); }
                 const uint64_t stop0 = __ballot(g0 < 8);
                 bool more = false;
                 if (stop0) { const uint32_t f = (uint32_t)__builtin_ctzll(stop0); mlen += f * 8 + __builtin_amdgcn_readlane(g0, f); }
@@ -220,9 +282,9 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
                     // "for free" cost two more round trips - and a match of exactly 512 bytes, the end of the first window, is common)
                     const uint32_t b0 = mp + mlen + lane * 8;
                     uint64_t y0 = 0;
-                    if (b0 < end_lim) y0 = ld64_guard(base + b0, rd_end) ^ ld64_guard(base + (b0 - dist), rd_end);
+                    if (b0 < end_lim) y0 = ld64_guard(base + b0, rd_end) ^ src8(b0 - dist, cd);
                     uint32_t h0 = 0;
-                    if (b0 < end_lim) { h0 = y0 ? (uint32_t)(__builtin_ctzll(y0) >> 3) : 8; const uint32_t r = end_lim - b0; if (h0 > r) h0 = r; }
+                    if (b0 < end_lim) { h0 = y0 ? (uint32_t)(__builtin_ctzll(y0) >> 3) : 8; const uint32_t r = end_lim - b0; if (h0 > r) h0 = r; h0 = seam_cap(h0, b0 - dist); }
                     const uint64_t s0 = __ballot(h0 < 8);
                     if (s0) { const uint32_t f = (uint32_t)__builtin_ctzll(s0); mlen += f * 8 + __builtin_amdgcn_readlane(h0, f); break; }
                     mlen += WAVE * 8;

@@ -1178,12 +1178,22 @@ size_t lz4f_mi355x_dev_decompressBlocks(lz4f_mi355x_engine* e, void* d_dst, size
     return lz4f_mi355x_dev_decompressBlocksIndexed(e, d_dst, dstCapacity, d_frame, frameCapacity, d_table, n_blocks, info, nullptr, 0, d_result);
 }
 
-size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
-                                        void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
+// the batch's dictionary as the kernels take it: the last 64 KiB at most (dictSize 0: none)
+static void batch_dict_tail(const void* d_dict, size_t dictSize, const uint8_t*& end, uint32_t& len)
+{
+    len = (uint32_t)std::min<size_t>(dictSize, 65536);
+    end = len ? (const uint8_t*)d_dict + dictSize : nullptr;
+}
+
+static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results,
+                                const void* d_dict, size_t dictSize)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results)) return r;
+    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (d_dict || !dictSize))) return r;
+    BfDict dc;
+    batch_dict_tail(d_dict, dictSize, dc.end, dc.len);
     hipStream_t st = (hipStream_t)e->stream;
     // the block table: a frame of full blocks never needs more than window / 64 KiB + 1 entries, so this bound needs nothing read back
     const uint64_t table_cap = batch_table_cap(n_frames, dstBytes / BF_SHARE);
@@ -1200,11 +1210,30 @@ size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames
     hipLaunchKernelGGL(k_bf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts);
     hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
     hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
+    if (dc.len) {                                                      // (the dictionary's instantiations: every block through the scalar-parse decoder)
+        hipLaunchKernelGGL((k_bf_blocks_dict<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table, (const uint32_t*)ctl, dc);
+        hipLaunchKernelGGL((k_bf_serial_dict<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, dc);
+        hipLaunchKernelGGL((k_bf_finish_dict<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
+                           e->sw.no_content_check ? 0u : 1u, dc);
+        return batch_end("dev_decompressFrames");
+    }
     hipLaunchKernelGGL((k_bf_blocks<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table, (const uint32_t*)ctl);
     hipLaunchKernelGGL((k_bf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames);
     hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
                        e->sw.no_content_check ? 0u : 1u);
     return batch_end("dev_decompressFrames");
+}
+
+size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                        void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
+{
+    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, nullptr, 0);
+}
+size_t lz4f_mi355x_dev_decompressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                  void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results,
+                                                  const void* d_dict, size_t dictSize)
+{
+    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, d_dict, dictSize);
 }
 
 size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
@@ -1238,9 +1267,9 @@ size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, c
     return batch_end("dev_measureFrames");
 }
 
-size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
-                                      void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                                      lz4f_mi355x_result* d_results)
+static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                              void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
@@ -1248,8 +1277,12 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
+    // (levels 3-12 have no dictionary yet: hc_find_chunk does not know it.  Nothing is enqueued)
+    if (dictSize && p.compressionLevel >= 3) { set_last_error("dev_compressFrames_usingDict: levels 3-12 take no dictionary"); return make_err(LZ4F_ERROR_compressionLevel_invalid); }
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results)) return r;
+    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (d_dict || !dictSize))) return r;
+    const uint8_t* dict_end; uint32_t dict_len;
+    batch_dict_tail(d_dict, dictSize, dict_end, dict_len);
     hipStream_t st = (hipStream_t)e->stream;
     // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
@@ -1292,6 +1325,9 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     if (hc)
         hipLaunchKernelGGL(k_bc_find_hc, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
+    else if (dict_len)
+        hipLaunchKernelGGL(k_bc_find_solo_dict, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
+                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, dict_end, dict_len);
     else
         hipLaunchKernelGGL(k_bc_find_solo, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool);
@@ -1307,6 +1343,19 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
     }
     if (pf.content_checksum) hipLaunchKernelGGL((k_bc_content<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames);
     return batch_end("dev_compressFrames");
+}
+
+size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                      void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                                      lz4f_mi355x_result* d_results)
+{
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, nullptr, 0);
+}
+size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                                                lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
+{
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, d_dict, dictSize);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

@@ -183,12 +183,28 @@ class Engine:
         """Room for the result records of a batch of n frames (decompress_frames_async)."""
         return torch.zeros(n * self.RESULT_BYTES, dtype=torch.uint8, device="cuda:%d" % self.device)
 
-    def decompress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, results: torch.Tensor):
+    def _check_dictionary(self, dictionary) -> "tuple[int | None, int]":
+        """A batch call's dictionary: a uint8 tensor on the engine's device (one dimension, contiguous; it may be empty)."""
+        if (not isinstance(dictionary, torch.Tensor) or dictionary.dtype != torch.uint8 or not dictionary.is_cuda or dictionary.dim() != 1
+                or not dictionary.is_contiguous() or dictionary.device.index != self.device):
+            raise ValueError("dictionary must be a contiguous one-dimensional uint8 tensor on cuda:%d" % self.device)
+        return (dictionary.data_ptr() if dictionary.numel() else None), dictionary.numel()
+
+    def decompress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, results: torch.Tensor,
+                                dictionary: "torch.Tensor | None" = None):
         """Enqueue a batch: frame i is the first frame in src[src_off[i]:src_off[i+1]], its output goes to dst[dst_off[i]:dst_off[i+1]].
         src, dst: uint8 device tensors; src_off, dst_off: int64 device tensors of n+1 offsets; results: uint8 device tensor of
         32*n bytes (new_results).  Each frame's verdict lands in its record (frame_results) - a bad frame fails alone, the call
-        raises only for what is wrong with the call itself.  Nothing is read back: no synchronisation."""
+        raises only for what is wrong with the call itself.  Nothing is read back: no synchronisation.
+        dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch, as LZ4F_decompress_usingDict
+        applies it - the history in front of every frame (linked blocks) or every block (independent blocks); its last 64 KiB count.
+        It must stay alive until the stream has run the call.  The header's dictID is not looked at."""
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        if dictionary is not None:
+            d_ptr, d_len = self._check_dictionary(dictionary)
+            _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
+                                                                          dst.numel(), dst_off.data_ptr(), results.data_ptr(), d_ptr, d_len))
+            return
         _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
                                                             dst_off.data_ptr(), results.data_ptr()))
 
@@ -208,16 +224,25 @@ class Engine:
                                                          dst_off.data_ptr() if dst_off is not None else None, results.data_ptr()))
 
     def compress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, prefs: Preferences,
-                              results: torch.Tensor):
+                              results: torch.Tensor, dictionary: "torch.Tensor | None" = None):
         """Enqueue a batch: input i is src[src_off[i]:src_off[i+1]], its frame is written at dst[dst_off[i]] and may use
         dst[dst_off[i]:dst_off[i+1]] (this module's frame_windows gives offsets that always suffice).  One prefs for all frames; a non-zero
         prefs.frameInfo.contentSize means every header declares its own input's length.  Tensors as for decompress_frames_async,
         whose src / src_off the dst / dst_off of this call can be as they are.  Each frame is byte for byte what compress_async
         writes for its input alone on an engine with set_deterministic(True); its size and verdict land in its record
-        (frame_results) - a frame whose window is too small fails alone.  Nothing is read back: no synchronisation."""
+        (frame_results) - a frame whose window is too small fails alone.  Nothing is read back: no synchronisation.
+        dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch - the match finder reaches into
+        its last 64 KiB as if they lay in front of every input; decompress_frames_async(..., dictionary=) and liblz4's
+        LZ4F_decompress_usingDict decode the frames.  Levels 0-2 only (3-12 raise compressionLevel_invalid); prefs.frameInfo.dictID
+        is written as it is and means nothing else."""
         if not isinstance(prefs, Preferences):
             raise ValueError("prefs must be a Preferences")
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        if dictionary is not None:
+            d_ptr, d_len = self._check_dictionary(dictionary)
+            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
+                                                                        dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(), d_ptr, d_len))
+            return
         _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
                                                           dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr()))
 
