@@ -527,12 +527,41 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uin
  *     match is cut where the dictionary ends and the input begins (liblz4 may let one run across; the decoders take both).
  *   - Everything said above about the plain call holds: spans, windows, isolation, the record's fields, LZ4F_MI355X_PATH_BATCH, the
  *     workspace formula (the dictionary adds nothing to it), no host synchronisation, a launch count independent of n_frames.
- * Every 64 KiB chunk's wave seeds its hash table from the dictionary: a small record pays for up to 64 KiB of seeding. */
+ * Every 64 KiB chunk's wave seeds its hash table from the dictionary: a small record pays for up to 64 KiB of seeding.  A dictionary
+ * that serves many calls is better prepared once: lz4f_mi355x_dev_createCDict / lz4f_mi355x_dev_compressFrames_usingCDict below. */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames,
                                                                 const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
                                                                 const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
                                                                 const void* d_dict, size_t dictSize);
+
+/* A PREPARED DICTIONARY (liblz4's LZ4F_CDict for the batch encoder): the dictionary digested once, reused by every frame of every call.
+ * lz4f_mi355x_dev_createCDict copies the last min(dictSize, 64 KiB) bytes of d_dict (DEVICE memory at any byte address) into device
+ * memory of its own and seeds the match finder's hash table from them once (11 520 bytes: 3840 x (u16 position + u8 tag)); a scope's
+ * first chunk then copies that table where lz4f_mi355x_dev_compressFrames_usingDict reads the dictionary and seeds it again.
+ *   - The copy and one kernel are enqueued on the engine's stream; nothing synchronises with the host beyond what the allocation itself
+ *     does.  d_dict may be reused or freed once the stream has run the call.
+ *   - dictSize == 0 (d_dict may be NULL) makes an empty CDict.  A dictionary of 1-3 bytes is kept (the decoder honours it), the finder
+ *     ignores it.  A NULL e or out, or a NULL d_dict with dictSize > 0, is ERROR_GENERIC; a failed allocation
+ *     ERROR_allocation_failed; *out is then NULL and nothing is leaked.
+ *   - A CDict belongs to the engine that made it: it is used with that engine only (another one gets ERROR_GENERIC, "cdict belongs to
+ *     another engine", and nothing is enqueued) and freed before that engine is.  It is never written after its creation: one CDict
+ *     serves any number of calls.  lz4f_mi355x_dev_freeCDict waits for the engine's stream, then frees; NULL is accepted.
+ *   - lz4f_mi355x_cdict_data: the owned copy, DEVICE memory, its length in *size (size may be NULL) - what to hand to
+ *     lz4f_mi355x_dev_decompressFrames_usingDict.  NULL and 0 for a NULL or empty CDict.
+ * lz4f_mi355x_dev_compressFrames_usingCDict is lz4f_mi355x_dev_compressFrames_usingDict with the CDict's copy for d_dict / dictSize:
+ * every sentence above holds, and frame i and d_results[i] are byte for byte what that call writes for the same inputs, prefs and
+ * dictionary bytes.  A NULL or empty cdict is lz4f_mi355x_dev_compressFrames (the same kernels, the same bytes); compressionLevel 3-12
+ * with a non-empty one returns ERROR_compressionLevel_invalid and enqueues nothing. */
+typedef struct lz4f_mi355x_cdict lz4f_mi355x_cdict;
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_createCDict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c);
+LZ4F_MI355X_API const void* lz4f_mi355x_cdict_data(const lz4f_mi355x_cdict* c, size_t* size);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                                 const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                                 const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
+                                                                 const lz4f_mi355x_cdict* cdict);
 
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,

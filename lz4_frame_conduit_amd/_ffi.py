@@ -88,6 +88,9 @@ _SIGS = {
     "lz4f_mi355x_dev_compressFrames": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p]),
     "lz4f_mi355x_dev_decompressFrames_usingDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
     "lz4f_mi355x_dev_compressFrames_usingDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p, c_size_t]),
+    "lz4f_mi355x_dev_createCDict": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t]), "lz4f_mi355x_dev_freeCDict": (c_size_t, [c_void_p]),
+    "lz4f_mi355x_cdict_data": (c_void_p, [c_void_p, ctypes.POINTER(c_size_t)]),
+    "lz4f_mi355x_dev_compressFrames_usingCDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p]),
     "lz4f_mi355x_conduit_compress": (ctypes.c_int, [c_size_t, PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_compress_yield_immediately": (ctypes.c_int, [PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_decompress": (ctypes.c_int, [AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),

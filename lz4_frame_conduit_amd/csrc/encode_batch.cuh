@@ -17,7 +17,8 @@
 //   k_bc_find_*    the deterministic match finders over the chunk table: solo_find_chunk (encode_solo.cuh, a wave per chunk, levels
 //                  <= 2) or hc_find_chunk (encode_hc.cuh, a workgroup per chunk, levels 3-12) - the very functions the single call's
 //                  kernels run, so a frame's records are what they would be alone
-//                  (k_bc_find_solo_dict: the same finder with the call's shared dictionary in front of every low_abs)
+//                  (k_bc_find_solo_dict: the same finder with the call's shared dictionary in front of every low_abs;
+//                  k_bc_find_solo_cdict: with a prepared dictionary, whose digested table a scope's first chunk copies)
 //   k_bc_layout    a wave per block: layout_block_chunks (pass S's per-block step: carries, raw fallback) -> the size word
 //   k_bc_frames    a wave per frame: the blocks placed behind the header, the window judged, then header (made here: content size and
 //                  HC byte are the frame's own), size words, EndMark, every chunk's place in the destination, the result record
@@ -193,6 +194,27 @@ __global__ __launch_bounds__(64) void k_bc_find_solo_dict(const uint8_t* __restr
         if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
         const EncPlace pl = bc_place_of(e);
         solo_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), s_table, s_tag, dict_end, dict_len);
+    }
+}
+// the same with a prepared dictionary (lz4f_mi355x_dev_compressFrames_usingCDict): `digest` is the seeded table of a chunk that has
+// the dictionary alone in front of it (k_solo_digest_dict), and such a chunk - cs_abs == low_abs: every frame's first chunk, and every
+// independent block's - copies it into LDS, 11.25 KiB, where k_bc_find_solo_dict reads up to 64 KiB of dictionary and inserts some
+// 17 000 seeds.  (Chunks are 64 KiB, so a chunk behind the first of its scope has 64 KiB of input in front and no dictionary: it
+// seeds as ever.  The finder asks cs_abs == low_abs itself and does not lean on that.)  Table and tags are one array here, in the
+// digest's layout; the same 11 520 bytes of LDS
+__global__ __launch_bounds__(64) void k_bc_find_solo_cdict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
+                                                           const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
+                                                           ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool,
+                                                           const uint8_t* __restrict__ dict_end, uint32_t dict_len, const uint4* __restrict__ digest)
+{
+    __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BcChunk e = chunks[w];
+        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
+        const EncPlace pl = bc_place_of(e);
+        solo_find_chunk<true, true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), solo_digest_table(s_dig), solo_digest_tags(s_dig),
+                                    dict_end, dict_len, digest);
     }
 }
 

@@ -32,14 +32,54 @@ constexpr uint32_t SOLO_SEED_STRIDE = 4, SOLO_SEED_DENSE = 1024;
 constexpr uint32_t SOLO_LONG_MATCH = 192;
 __device__ __forceinline__ uint32_t solo_slot(uint32_t hv) { return ((hv >> (32 - SOLO_HASH_LOG)) * 15u) >> 4; }
 
+// A dictionary's digest (the batch encoder's prepared dictionary): the table, then the tags, as the seeding below leaves them for a
+// chunk with the dictionary alone in front of it - SOLO_DIGEST_BYTES in all, 16-byte aligned, laid out in LDS as in memory.
+constexpr uint32_t SOLO_DIGEST_BYTES = SOLO_HASH_SIZE * (uint32_t)(sizeof(uint16_t) + sizeof(uint8_t)), SOLO_DIGEST_VEC = SOLO_DIGEST_BYTES / 16;
+static_assert(SOLO_DIGEST_BYTES == 11520 && SOLO_DIGEST_BYTES % 16 == 0 && (SOLO_HASH_SIZE * sizeof(uint16_t)) % 16 == 0, "digest layout");
+constexpr int SOLO_DIGEST_IN_FLIGHT = 6;                                                    // 16-byte loads in flight per lane: 720 in two rounds
+static_assert(SOLO_DIGEST_VEC % SOLO_DIGEST_IN_FLIGHT == 0 && SOLO_DIGEST_VEC / SOLO_DIGEST_IN_FLIGHT <= 2 * WAVE, "digest rounds");
+__device__ __forceinline__ uint16_t* solo_digest_table(uint4* dig) { return (uint16_t*)dig; }
+__device__ __forceinline__ uint8_t* solo_digest_tags(uint4* dig) { return (uint8_t*)dig + SOLO_HASH_SIZE * sizeof(uint16_t); }
+// the wave's LDS table and tags <- the digest; a round's loads are all issued before its first store.  The fences order the vector
+// stores behind the last chunk's probes and in front of this one's, which read halfwords and bytes that other lanes' vectors hold
+// (one wave owns the table: nothing beyond the wave's own order is needed, as with the seeding's stores)
+__device__ __forceinline__ void solo_digest_load(uint4* lds, const uint4* __restrict__ digest)
+{
+    const uint32_t lane = lane_id();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+#pragma unroll 1                                                         // (unrolled, all twelve loads are in flight and cost the wave its fourth on a SIMD)
+    for (uint32_t q = 0; q < SOLO_DIGEST_VEC; q += SOLO_DIGEST_IN_FLIGHT * WAVE) {
+        uint4 vv[SOLO_DIGEST_IN_FLIGHT];
+#pragma unroll
+        for (int u = 0; u < SOLO_DIGEST_IN_FLIGHT; u++) { const uint32_t i = q + u * WAVE + lane; vv[u] = digest[i < SOLO_DIGEST_VEC ? i : 0u]; }
+#pragma unroll
+        for (int u = 0; u < SOLO_DIGEST_IN_FLIGHT; u++) { const uint32_t i = q + u * WAVE + lane; if (i < SOLO_DIGEST_VEC) lds[i] = vv[u]; }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+}
+// the digest <- the wave's LDS table and tags (k_solo_digest_dict)
+__device__ __forceinline__ void solo_digest_store(uint4* __restrict__ digest, const uint4* lds)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();     // (the seeds are other lanes' halfword and byte stores)
+    for (uint32_t i = lane_id(); i < SOLO_DIGEST_VEC; i += WAVE) digest[i] = lds[i];
+}
+
 // One chunk, one wave: the search itself, for a chunk whose place is resolved (EncPlace, encode.cuh) - by k_find_matches_solo from the
 // call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `table` / `tags`: the wave's own, in LDS; `rec`: the
 // chunk's record list (max_rec records of room; !rec_room: none, the chunk goes out as literals).
-template <bool DICT = false>
+// CDICT (with DICT; lz4f_mi355x_dev_compressFrames_usingCDict): a chunk with the dictionary alone in front of it (cs_abs == low_abs)
+// has seam == back == min(64 KiB, dict_len), so its positions and with them the seeded table and tags are a function of the
+// dictionary alone: `digest` holds them, made once by k_solo_digest_dict, and such a chunk copies it instead of clearing and seeding
+// (`table` and `tags` are then one 16-byte aligned array in the digest's layout).  Every other chunk seeds as without it.
+// SEED_ONLY: clear and seed, nothing else - how k_solo_digest_dict makes the digest, by the very code and in the very insertion
+// order ("later inserts win") of the finders.
+template <bool DICT = false, bool CDICT = false, bool SEED_ONLY = false>
 __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
                                                 uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
-                                                uint16_t* table, uint8_t* tags, const uint8_t* dict_end = nullptr, uint32_t dict_len = 0)
+                                                uint16_t* table, uint8_t* tags, const uint8_t* dict_end = nullptr, uint32_t dict_len = 0,
+                                                const uint4* __restrict__ digest = nullptr)
 {
+    static_assert(DICT || !(CDICT || SEED_ONLY), "a digest is a dictionary's");
     const uint32_t lane = lane_id();
     const uint64_t bstart = pl.bstart, bend_abs = pl.bend_abs, cs_abs = pl.cs_abs, ce_abs = pl.ce_abs, low_abs = pl.low_abs;
     uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
@@ -62,83 +102,90 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
     // clear + pre-seed the table with the history in front of the chunk.  A 4096-entry table cannot hold
     // 64 KiB of positions, and later inserts win: seed the whole window sparsely (every SEED_STRIDE-th position,
     // roughly the density the skip-accelerated search itself leaves behind), then the last SEED_DENSE bytes densely.
-    for (uint32_t i = lane; i < SOLO_HASH_SIZE / 2; i += WAVE) ((uint32_t*)table)[i] = 0;
-    for (uint32_t i = lane; i < SOLO_HASH_SIZE * sizeof(uint8_t) / 4; i += WAVE) ((uint32_t*)tags)[i] = 0;
-    if (DICT && seam) {
-        // the same scheme over [dictionary tail | input]: a lane's 16 bytes lie on one side of the seam, or its seeds go in one by one
-        const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
-        constexpr int SEED_IN_FLIGHT = 8;
-        auto ok4 = [&](uint32_t p) -> bool { return p + 4 <= seam || (p >= seam && p + 4 <= back); };
-        auto put = [&](uint32_t p, uint32_t v) { const uint32_t hv = v * 2654435761u; table[solo_slot(hv)] = (uint16_t)p; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); };
-        for (uint32_t q = 0; q < dense_from; q += SEED_IN_FLIGHT * 1024) {
-            uint4 vv[SEED_IN_FLIGHT];
-#pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) {
-                const uint32_t p = q + u * 1024 + lane * 16;
-                vv[u] = uint4{0u, 0u, 0u, 0u};
-                if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) { const b16_ua t = *(const b16_ua*)at_pos(p); vv[u] = uint4{t.a, t.b, t.c, t.d}; }
-            }
-#pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) {
-                const uint32_t p = q + u * 1024 + lane * 16;
-                if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) {
-                    const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++) put(p + 4 * k, w[k]);
-                } else {
-                    for (uint32_t k = 0; k < 4; k++) { const uint32_t pk = p + 4 * k; if (pk < dense_from && ok4(pk)) put(pk, ld32(at_pos(pk))); }
-                }
-            }
-        }
-        for (uint32_t q = dense_from; q + 4 <= back; q += SEED_IN_FLIGHT * WAVE) {       // (inserted in position order: later ones win)
-            uint32_t vv[SEED_IN_FLIGHT];
-#pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; vv[u] = ok4(p) ? ld32(at_pos(p)) : 0u; }
-#pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; if (ok4(p)) put(p, vv[u]); }
-        }
-    } else if (back >= 4) {
-        const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
-        const uint32_t ss = SOLO_SEED_STRIDE;
-        constexpr int SEED_IN_FLIGHT = 16;                                           // loads in flight per wave (registers are plentiful: LDS bounds the occupancy)
-        uint32_t q = 0;
-        if (ss == 4) {
-            // every 4th position: 16 bytes per lane hold four of them, a wave-load covers 1 KiB (a quarter of the load instructions)
-            const uint32_t span = dense_from & ~1023u;
-            for (; q < span; q += SEED_IN_FLIGHT * 1024) {
+    bool seeded = false;
+    if constexpr (CDICT) {
+        if (seam && cs_abs == low_abs) { solo_digest_load((uint4*)table, digest); seeded = true; }
+    }
+    if (!seeded) {
+        for (uint32_t i = lane; i < SOLO_HASH_SIZE / 2; i += WAVE) ((uint32_t*)table)[i] = 0;
+        for (uint32_t i = lane; i < SOLO_HASH_SIZE * sizeof(uint8_t) / 4; i += WAVE) ((uint32_t*)tags)[i] = 0;
+        if (DICT && seam) {
+            // the same scheme over [dictionary tail | input]: a lane's 16 bytes lie on one side of the seam, or its seeds go in one by one
+            const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
+            constexpr int SEED_IN_FLIGHT = 8;
+            auto ok4 = [&](uint32_t p) -> bool { return p + 4 <= seam || (p >= seam && p + 4 <= back); };
+            auto put = [&](uint32_t p, uint32_t v) { const uint32_t hv = v * 2654435761u; table[solo_slot(hv)] = (uint16_t)p; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); };
+            for (uint32_t q = 0; q < dense_from; q += SEED_IN_FLIGHT * 1024) {
                 uint4 vv[SEED_IN_FLIGHT];
-#pragma unroll
-                for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * 1024 + lane * 16; const b16_ua t = *(const b16_ua*)(base + (p < span ? p : 0u)); vv[u] = uint4{t.a, t.b, t.c, t.d}; }
 #pragma unroll
                 for (int u = 0; u < SEED_IN_FLIGHT; u++) {
                     const uint32_t p = q + u * 1024 + lane * 16;
-                    if (p < span) {
+                    vv[u] = uint4{0u, 0u, 0u, 0u};
+                    if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) { const b16_ua t = *(const b16_ua*)at_pos(p); vv[u] = uint4{t.a, t.b, t.c, t.d}; }
+                }
+#pragma unroll
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) {
+                    const uint32_t p = q + u * 1024 + lane * 16;
+                    if (p + 16 <= dense_from && (p + 16 <= seam || p >= seam)) {
                         const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
 #pragma unroll
-                        for (int k = 0; k < 4; k++) { const uint32_t hv = w[k] * 2654435761u; table[solo_slot(hv)] = (uint16_t)(p + 4 * k); tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
+                        for (int k = 0; k < 4; k++) put(p + 4 * k, w[k]);
+                    } else {
+                        for (uint32_t k = 0; k < 4; k++) { const uint32_t pk = p + 4 * k; if (pk < dense_from && ok4(pk)) put(pk, ld32(at_pos(pk))); }
                     }
                 }
             }
-            q = span;
-        }
-        for (; q < dense_from; q += SEED_IN_FLIGHT * WAVE * ss) {
-            uint32_t pp[SEED_IN_FLIGHT], vv[SEED_IN_FLIGHT];
+            for (uint32_t q = dense_from; q + 4 <= back; q += SEED_IN_FLIGHT * WAVE) {       // (inserted in position order: later ones win)
+                uint32_t vv[SEED_IN_FLIGHT];
 #pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) { pp[u] = q + (u * WAVE + lane) * ss; vv[u] = ld32(base + (pp[u] < dense_from ? pp[u] : 0u)); }
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; vv[u] = ok4(p) ? ld32(at_pos(p)) : 0u; }
 #pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) if (pp[u] < dense_from) { const uint32_t hv = vv[u] * 2654435761u; table[solo_slot(hv)] = (uint16_t)pp[u]; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
-        }
-        for (uint32_t q = dense_from; q + 4 <= back; q += SEED_IN_FLIGHT * WAVE) {       // (inserted in position order: later ones win)
-            uint32_t vv[SEED_IN_FLIGHT];
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; if (ok4(p)) put(p, vv[u]); }
+            }
+        } else if (back >= 4) {
+            const uint32_t dense_from = back > SOLO_SEED_DENSE ? back - SOLO_SEED_DENSE : 0;
+            const uint32_t ss = SOLO_SEED_STRIDE;
+            constexpr int SEED_IN_FLIGHT = 16;                                           // loads in flight per wave (registers are plentiful: LDS bounds the occupancy)
+            uint32_t q = 0;
+            if (ss == 4) {
+                // every 4th position: 16 bytes per lane hold four of them, a wave-load covers 1 KiB (a quarter of the load instructions)
+                const uint32_t span = dense_from & ~1023u;
+                for (; q < span; q += SEED_IN_FLIGHT * 1024) {
+                    uint4 vv[SEED_IN_FLIGHT];
 #pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; vv[u] = ld32(base + (p + 4 <= back ? p : 0u)); }
+                    for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * 1024 + lane * 16; const b16_ua t = *(const b16_ua*)(base + (p < span ? p : 0u)); vv[u] = uint4{t.a, t.b, t.c, t.d}; }
 #pragma unroll
-            for (int u = 0; u < SEED_IN_FLIGHT; u++) {
-                const uint32_t p = q + u * WAVE + lane;
-                if (p + 4 <= back) { const uint32_t hv = vv[u] * 2654435761u; table[solo_slot(hv)] = (uint16_t)p; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
+                    for (int u = 0; u < SEED_IN_FLIGHT; u++) {
+                        const uint32_t p = q + u * 1024 + lane * 16;
+                        if (p < span) {
+                            const uint32_t w[4] = {vv[u].x, vv[u].y, vv[u].z, vv[u].w};
+#pragma unroll
+                            for (int k = 0; k < 4; k++) { const uint32_t hv = w[k] * 2654435761u; table[solo_slot(hv)] = (uint16_t)(p + 4 * k); tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
+                        }
+                    }
+                }
+                q = span;
+            }
+            for (; q < dense_from; q += SEED_IN_FLIGHT * WAVE * ss) {
+                uint32_t pp[SEED_IN_FLIGHT], vv[SEED_IN_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) { pp[u] = q + (u * WAVE + lane) * ss; vv[u] = ld32(base + (pp[u] < dense_from ? pp[u] : 0u)); }
+#pragma unroll
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) if (pp[u] < dense_from) { const uint32_t hv = vv[u] * 2654435761u; table[solo_slot(hv)] = (uint16_t)pp[u]; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
+            }
+            for (uint32_t q = dense_from; q + 4 <= back; q += SEED_IN_FLIGHT * WAVE) {       // (inserted in position order: later ones win)
+                uint32_t vv[SEED_IN_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) { const uint32_t p = q + u * WAVE + lane; vv[u] = ld32(base + (p + 4 <= back ? p : 0u)); }
+#pragma unroll
+                for (int u = 0; u < SEED_IN_FLIGHT; u++) {
+                    const uint32_t p = q + u * WAVE + lane;
+                    if (p + 4 <= back) { const uint32_t hv = vv[u] * 2654435761u; table[solo_slot(hv)] = (uint16_t)p; tags[solo_slot(hv)] = (uint8_t)(hv >> (32 - SOLO_TAG_BITS - SOLO_HASH_LOG)); }
+                }
             }
         }
     }
+    if constexpr (SEED_ONLY) return;
 
     uint32_t nrec = 0, first_lit = 0, body = 0;
     uint32_t anchor = cs;
@@ -335,6 +382,20 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const u
     uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
     if (lane == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
     solo_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, s_table[wave], s_tag[wave]);
+}
+
+// The prepared dictionary's digest: one wave seeds its table from the dictionary's last dict_len (<= 64 KiB) bytes, which end at
+// dict_end, as a chunk with nothing but the dictionary in front of it seeds it (an empty place at dict_end: cs_abs == low_abs, so
+// seam == back == dict_len and no position is the input's), and stores table and tags to `digest` (SOLO_DIGEST_BYTES, 16-byte aligned).
+// A dictionary of fewer than 4 bytes is ignored by the finder: its digest is the cleared table.
+__global__ __launch_bounds__(64) void k_solo_digest_dict(const uint8_t* __restrict__ dict_end, uint32_t dict_len, uint4* __restrict__ digest)
+{
+    __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
+    EncPlace pl;
+    pl.bstart = 0; pl.bend_abs = 0; pl.cs_abs = 0; pl.ce_abs = 0; pl.low_abs = 0; pl.rd_end = 0;
+    solo_find_chunk<true, false, true>(dict_end, pl, nullptr, nullptr, false, 0u, solo_digest_table(s_dig), solo_digest_tags(s_dig), dict_end,
+                                       dict_len < 65536u ? dict_len : 65536u);
+    solo_digest_store(digest, s_dig);
 }
 
 // ------------------------------- pass S --------------------------------------------------------

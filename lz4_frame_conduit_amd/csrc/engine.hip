@@ -996,6 +996,15 @@ struct Carve {
     template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
 };
 
+// A prepared dictionary (lz4f_mi355x_dev_createCDict): its engine's, never written after the stream has run its creation.
+// One device allocation: the digest (SOLO_DIGEST_BYTES: the finder's table and tags, seeded), then `size` (<= 64 KiB) dictionary bytes
+struct lz4f_mi355x_cdict {
+    lz4f_mi355x_engine* engine = nullptr;
+    uint4* digest = nullptr;               // the allocation; NULL: an empty dictionary
+    uint8_t* data = nullptr;
+    size_t size = 0;
+};
+
 extern "C" {
 
 const char* lz4f_mi355x_last_error(void) { return lz4f::last_error(); }
@@ -1267,9 +1276,11 @@ size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, c
     return batch_end("dev_measureFrames");
 }
 
+// `digest` (a prepared dictionary's, made by k_solo_digest_dict from these very dictSize bytes; NULL: none): the finder copies it where
+// it would seed from the dictionary alone
 static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                               void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
+                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize, const uint4* digest = nullptr)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
@@ -1325,6 +1336,9 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     if (hc)
         hipLaunchKernelGGL(k_bc_find_hc, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
+    else if (dict_len && digest)
+        hipLaunchKernelGGL(k_bc_find_solo_cdict, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
+                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, dict_end, dict_len, digest);
     else if (dict_len)
         hipLaunchKernelGGL(k_bc_find_solo_dict, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, dict_end, dict_len);
@@ -1356,6 +1370,77 @@ size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t 
                                                 lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
 {
     return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, d_dict, dictSize);
+}
+
+// ---- the prepared dictionary: the dictionary's last 64 KiB, owned, and the finder's table seeded from them once ----
+size_t lz4f_mi355x_dev_createCDict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize)
+{
+    if (out) *out = nullptr;
+    if (!e || !out || (!d_dict && dictSize)) { set_last_error("dev_createCDict: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    lz4f_mi355x_cdict* c = new (std::nothrow) lz4f_mi355x_cdict();
+    if (!c) { set_last_error("dev_createCDict: out of memory"); return make_err(LZ4F_ERROR_allocation_failed); }
+    c->engine = e;
+    const uint8_t* dict_end; uint32_t dict_len;
+    batch_dict_tail(d_dict, dictSize, dict_end, dict_len);
+    if (dict_len) {
+        // one allocation: the digest (16-byte aligned: it leads), then the copy
+        void* p = nullptr;
+        const hipError_t he = hipMalloc(&p, SOLO_DIGEST_BYTES + (size_t)dict_len);
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            set_last_error("dev_createCDict: hipMalloc(%zu) failed: %s", SOLO_DIGEST_BYTES + (size_t)dict_len, hipGetErrorString(he));
+            delete c;
+            return make_err(LZ4F_ERROR_allocation_failed);
+        }
+        c->digest = (uint4*)p; c->data = (uint8_t*)p + SOLO_DIGEST_BYTES; c->size = dict_len;
+        hipStream_t st = (hipStream_t)e->stream;
+        if (hipMemcpyAsync(c->data, dict_end - dict_len, dict_len, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipFree(p); delete c;
+            set_last_error("dev_createCDict: the dictionary's copy failed");
+            return make_err(LZ4F_ERROR_GENERIC);
+        }
+        hipLaunchKernelGGL(k_solo_digest_dict, dim3(1), dim3(64), 0, st, (const uint8_t*)c->data + dict_len, dict_len, c->digest);
+        if (hipGetLastError() != hipSuccess) {                             // (the copy may be in flight: wait before its target goes)
+            (void)hipStreamSynchronize(st); (void)hipFree(p); delete c;
+            set_last_error("dev_createCDict: launch failed");
+            return make_err(LZ4F_ERROR_GENERIC);
+        }
+    }
+    *out = c;
+    return 0;
+}
+
+size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c)
+{
+    if (!c) return 0;
+    size_t r = 0;
+    if (c->digest) {                                                       // (an empty one owns nothing and has nothing in flight)
+        if (hipSetDevice(c->engine->device) != hipSuccess || hipStreamSynchronize((hipStream_t)c->engine->stream) != hipSuccess) {
+            (void)hipGetLastError(); set_last_error("dev_freeCDict: waiting for the engine's stream failed"); r = make_err(LZ4F_ERROR_GENERIC);
+        }
+        (void)hipFree(c->digest);
+    }
+    delete c;
+    return r;
+}
+
+const void* lz4f_mi355x_cdict_data(const lz4f_mi355x_cdict* c, size_t* size)
+{
+    if (size) *size = c ? c->size : 0;
+    return c && c->size ? c->data : nullptr;
+}
+
+size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                                                 lz4f_mi355x_result* d_results, const lz4f_mi355x_cdict* cdict)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (!cdict || !cdict->size) return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, nullptr, 0);
+    if (cdict->engine != e) { set_last_error("dev_compressFrames_usingCDict: cdict belongs to another engine"); return make_err(LZ4F_ERROR_GENERIC); }
+    // (a dictionary of 1-3 bytes: the finder ignores it, its digest is the cleared table - the _usingDict kernel, as that call launches it)
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, cdict->data, cdict->size,
+                           cdict->size >= 4 ? cdict->digest : nullptr);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

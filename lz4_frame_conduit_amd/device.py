@@ -6,6 +6,7 @@ into the C ABI.  Work is enqueued on torch's current stream, so torch.cuda.Event
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -91,6 +92,38 @@ def frame_windows(lengths, prefs: Preferences, gap: int = 0) -> "list[int]":
     return offs
 
 
+class CDict:
+    """A prepared dictionary (Engine.create_cdict): the engine's own copy of the dictionary's last 64 KiB in device memory and the
+    match finder's table digested from it once.  It serves any number of compress_frames_async(..., cdict=) calls on the engine that
+    made it, and decompress_frames_async(..., dictionary=) takes it too.  close() waits for the engine's stream and frees it; the
+    engine closes the ones that are still open when it is closed itself.  Use it as a context manager to close it on the way out."""
+
+    def __init__(self, engine: "Engine", h):
+        self.engine, self.h = engine, h
+        n = ctypes.c_size_t(0)
+        p = engine.L.lz4f_mi355x_cdict_data(h, ctypes.byref(n))
+        self.data_ptr, self.size = (p or None), int(n.value)
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.data_ptr, self.size = None, 0
+            self.engine._cdicts.discard(self)
+            self.engine.L.lz4f_mi355x_dev_freeCDict(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device: int = 0, stream: "torch.cuda.Stream | None" = None):
         self.L = _ffi.lib()
@@ -100,11 +133,14 @@ class Engine:
         h = ctypes.c_void_p()
         _chk(self.L, self.L.lz4f_mi355x_engine_create(ctypes.byref(h), device, ctypes.c_void_p(self.stream.cuda_stream), 1))
         self.h = h
+        self._cdicts = weakref.WeakSet()                                          # the prepared dictionaries still open: closed with the engine
         self._res = torch.zeros(32, dtype=torch.uint8, device="cuda:%d" % device)
         self._res_host = torch.zeros(32, dtype=torch.uint8).pin_memory()      # the result record comes back by DMA into page-locked memory: one wait, no staging
 
     def close(self):
         if self.h:
+            for c in list(self._cdicts):                                          # (a CDict is freed before its engine)
+                c.close()
             self.L.lz4f_mi355x_engine_free(self.h)
             self.h = None
 
@@ -190,18 +226,38 @@ class Engine:
             raise ValueError("dictionary must be a contiguous one-dimensional uint8 tensor on cuda:%d" % self.device)
         return (dictionary.data_ptr() if dictionary.numel() else None), dictionary.numel()
 
+    def create_cdict(self, dictionary: torch.Tensor) -> CDict:
+        """Prepare a dictionary (a uint8 tensor on the engine's device; it may be empty) for compress_frames_async(..., cdict=): its
+        last 64 KiB are copied and digested on the engine's stream, once.  The tensor may be reused or freed once the stream has run
+        the call; nothing is read back."""
+        d_ptr, d_len = self._check_dictionary(dictionary)
+        h = ctypes.c_void_p()
+        _chk(self.L, self.L.lz4f_mi355x_dev_createCDict(self.h, ctypes.byref(h), d_ptr, d_len))
+        c = CDict(self, h)
+        self._cdicts.add(c)
+        return c
+
+    def _check_cdict(self, cdict) -> CDict:
+        if not isinstance(cdict, CDict) or cdict.h is None:
+            raise ValueError("cdict must be an open CDict (Engine.create_cdict)")
+        return cdict
+
     def decompress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, results: torch.Tensor,
-                                dictionary: "torch.Tensor | None" = None):
+                                dictionary: "torch.Tensor | CDict | None" = None):
         """Enqueue a batch: frame i is the first frame in src[src_off[i]:src_off[i+1]], its output goes to dst[dst_off[i]:dst_off[i+1]].
         src, dst: uint8 device tensors; src_off, dst_off: int64 device tensors of n+1 offsets; results: uint8 device tensor of
         32*n bytes (new_results).  Each frame's verdict lands in its record (frame_results) - a bad frame fails alone, the call
         raises only for what is wrong with the call itself.  Nothing is read back: no synchronisation.
         dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch, as LZ4F_decompress_usingDict
         applies it - the history in front of every frame (linked blocks) or every block (independent blocks); its last 64 KiB count.
-        It must stay alive until the stream has run the call.  The header's dictID is not looked at."""
+        It must stay alive until the stream has run the call.  The header's dictID is not looked at.  A CDict (create_cdict) is
+        taken too: the dictionary is then its own copy."""
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
         if dictionary is not None:
-            d_ptr, d_len = self._check_dictionary(dictionary)
+            if isinstance(dictionary, CDict):
+                d_ptr, d_len = self._check_cdict(dictionary).data_ptr, dictionary.size
+            else:
+                d_ptr, d_len = self._check_dictionary(dictionary)
             _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
                                                                           dst.numel(), dst_off.data_ptr(), results.data_ptr(), d_ptr, d_len))
             return
@@ -224,7 +280,7 @@ class Engine:
                                                          dst_off.data_ptr() if dst_off is not None else None, results.data_ptr()))
 
     def compress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, prefs: Preferences,
-                              results: torch.Tensor, dictionary: "torch.Tensor | None" = None):
+                              results: torch.Tensor, dictionary: "torch.Tensor | None" = None, cdict: "CDict | None" = None):
         """Enqueue a batch: input i is src[src_off[i]:src_off[i+1]], its frame is written at dst[dst_off[i]] and may use
         dst[dst_off[i]:dst_off[i+1]] (this module's frame_windows gives offsets that always suffice).  One prefs for all frames; a non-zero
         prefs.frameInfo.contentSize means every header declares its own input's length.  Tensors as for decompress_frames_async,
@@ -234,10 +290,19 @@ class Engine:
         dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch - the match finder reaches into
         its last 64 KiB as if they lay in front of every input; decompress_frames_async(..., dictionary=) and liblz4's
         LZ4F_decompress_usingDict decode the frames.  Levels 0-2 only (3-12 raise compressionLevel_invalid); prefs.frameInfo.dictID
-        is written as it is and means nothing else."""
+        is written as it is and means nothing else.
+        cdict (create_cdict, of this engine; not together with dictionary=): the same dictionary prepared once - the same frames,
+        byte for byte, without reading and seeding the dictionary again for every 64 KiB chunk of every call."""
         if not isinstance(prefs, Preferences):
             raise ValueError("prefs must be a Preferences")
+        if cdict is not None and dictionary is not None:
+            raise ValueError("give dictionary= or cdict=, not both")
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        if cdict is not None:
+            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingCDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
+                                                                         dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(),
+                                                                         self._check_cdict(cdict).h))
+            return
         if dictionary is not None:
             d_ptr, d_len = self._check_dictionary(dictionary)
             _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),

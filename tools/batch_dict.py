@@ -1,4 +1,4 @@
-"""Many small records with a shared dictionary: the batch calls with and without `dictionary=`.  GPU box.
+"""Many small records with a shared dictionary: the batch calls with and without `dictionary=`, and with a prepared one (`cdict=`).  GPU box.
 
     python tools/batch_dict.py [--cases c1,c2,..] [--runs N] [--timeout S]
 
@@ -8,7 +8,12 @@ Cases
   dict_1k_x16384     records of 1 KiB / 16 KiB stitched from 32-byte slices of a 64 KiB phrase dictionary with a random byte
   dict_16k_x4096     between them: compress and decode with the dictionary beside the plain calls on the same records, and the
                      plain frames decoded through the dictionary call (its independent blocks go through the scalar-parse
-                     decoder, the plain call's through the lanes' decoder: the cost of that routing on text-like records)
+                     decoder, the plain call's through the lanes' decoder: the cost of that routing on text-like records).
+                     Then the prepared dictionary: create_cdict timed alone (the copy and the digest kernel), and the three
+                     compress calls - dictionary=, cdict=, plain - timed by turns in one loop ("alternating"), the cdict's frames
+                     and records checked to be the dictionary call's, byte for byte
+  dict1k_1k_x16384   the same records with the dictionary's last 1 KiB as the dictionary (d1k): there the digest's 11.25 KiB are
+  dict1k_16k_x4096   more than the dictionary they stand for
 Every case runs in a child process with its own time limit.  Timed with torch events on the engine's stream: a warm-up call, then
 `runs` calls, each timed on its own - the minimum, the median and the spread ((max - min) / min) are reported; GiB/s are of
 uncompressed bytes over the minimum.  Every output is checked against the input.  One JSON line per case."""
@@ -21,10 +26,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-CASES = {                       # name: (records, bytes per record, with a dictionary)
-    "plain_64k_x4096": (4096, 64 << 10, False),
-    "dict_1k_x16384": (16384, 1 << 10, True),
-    "dict_16k_x4096": (4096, 16 << 10, True),
+CASES = {                       # name: (records, bytes per record, dictionary bytes: the phrase dictionary's last ones; 0: none)
+    "plain_64k_x4096": (4096, 64 << 10, 0),
+    "dict_1k_x16384": (16384, 1 << 10, 65525),
+    "dict_16k_x4096": (4096, 16 << 10, 65525),
+    "dict1k_1k_x16384": (16384, 1 << 10, 1024),
+    "dict1k_16k_x4096": (4096, 16 << 10, 1024),
 }
 DICT_BYTES = 65525
 PIECE = 32
@@ -55,7 +62,7 @@ def child(case: str, runs: int) -> "list[dict]":
     import torch
     from lz4_frame_conduit_amd import conduit, datagen
     from lz4_frame_conduit_amd.device import Engine, frame_windows, synth50_device
-    n, fb, with_dict = CASES[case]
+    n, fb, dict_bytes = CASES[case]
     dev, total = "cuda:0", n * fb
     eng = Engine(0)
     p = conduit.make_preferences(blockSizeID=4, blockMode=1)
@@ -66,19 +73,27 @@ def child(case: str, runs: int) -> "list[dict]":
     back = torch.empty(total, dtype=torch.uint8, device=dev)
     res = eng.new_results(n)
 
-    def timed(fn):
-        ms = []
+    def timed_by_turns(fns: dict) -> dict:
+        """name -> timing; in every round each call runs once, in the given order, timed on its own"""
+        ms = {name: [] for name in fns}
         for k in range(runs + 1):                                    # (the first: warm-up - the workspace, the code objects)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            with torch.cuda.stream(eng.stream):
-                a.record(eng.stream)
-                fn()
-                b.record(eng.stream)
-            b.synchronize()
-            if k: ms.append(a.elapsed_time(b))
-        ms.sort()
-        return {"ms_min": round(ms[0], 4), "ms_median": round(ms[len(ms) // 2], 4), "spread": round((ms[-1] - ms[0]) / ms[0], 3),
-                "GiB_s": round(total / ms[0] / 1e-3 / (1 << 30), 2)}
+            for name, fn in fns.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(eng.stream):
+                    a.record(eng.stream)
+                    fn()
+                    b.record(eng.stream)
+                b.synchronize()
+                if k: ms[name].append(a.elapsed_time(b))
+        out = {}
+        for name, v in ms.items():
+            v.sort()
+            out[name] = {"ms_min": round(v[0], 4), "ms_median": round(v[len(v) // 2], 4), "spread": round((v[-1] - v[0]) / v[0], 3),
+                         "GiB_s": round(total / v[0] / 1e-3 / (1 << 30), 2)}
+        return out
+
+    def timed(fn):
+        return timed_by_turns({"": fn})[""]
 
     def roundtrip(src, cdict, ddict, frames_from=None):
         """compress with cdict (or take frames_from = (frames, offsets)), decode with ddict -> (compress timing, decode timing, frames, offsets, bytes)"""
@@ -103,7 +118,7 @@ def child(case: str, runs: int) -> "list[dict]":
         return enc, dec, frames, fo_t, int(fo_t[-1])
 
     outs = []
-    if not with_dict:
+    if not dict_bytes:
         for data in ("synth50", "text"):
             if data == "synth50": src = synth50_device(total, 5, dev)
             else:
@@ -113,16 +128,35 @@ def child(case: str, runs: int) -> "list[dict]":
             outs.append({"case": case, "data": data, "records": n, "record_bytes": fb, "compressed_bytes": cbytes, "compress": enc, "decompress": dec})
     else:
         d_np = phrase_dictionary(np)
-        d = torch.from_numpy(d_np.copy()).to(dev)
+        d = torch.from_numpy(d_np[-dict_bytes:].copy()).to(dev)
         src = torch.from_numpy(stitched_records(np, d_np, n, fb)).to(dev).reshape(-1)
         enc0, dec0, frames0, fo0, c0 = roundtrip(src, None, None)
         enc1, dec1, _, _, c1 = roundtrip(src, d, d)
         _, dec2, _, _, _ = roundtrip(src, None, d, frames_from=(frames0, fo0))      # the plain frames through the dictionary call's decoders
-        outs.append({"case": case, "data": "stitched", "records": n, "record_bytes": fb, "dictionary_bytes": DICT_BYTES,
+        # the prepared dictionary: its creation alone (each round makes one; close() waits for the stream, outside the events)
+        made = []
+        create = timed(lambda: made.append(eng.create_cdict(d)))
+        del create["GiB_s"]
+        for c in made[:-1]: c.close()
+        cd = made[-1]
+        slots.zero_(); res.zero_()
+        eng.compress_frames_async(src, so_t, slots, wo_t, p, res, dictionary=d)
+        eng.stream.synchronize()
+        want = (slots.clone(), res.clone())
+        slots.zero_(); res.zero_()
+        eng.compress_frames_async(src, so_t, slots, wo_t, p, res, cdict=cd)
+        eng.stream.synchronize()
+        assert torch.equal(res, want[1]) and torch.equal(slots, want[0]), "cdict: the frames are not the dictionary call's"
+        turns = timed_by_turns({"dictionary": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p, res, dictionary=d),
+                                "cdict": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p, res, cdict=cd),
+                                "plain": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p, res)})
+        cd.close()
+        outs.append({"case": case, "data": "stitched", "records": n, "record_bytes": fb, "dictionary_bytes": dict_bytes,
                      "plain": {"compressed_bytes": c0, "compress": enc0, "decompress": dec0},
                      "dictionary": {"compressed_bytes": c1, "compress": enc1, "decompress": dec1},
                      "plain_frames_scalar_parse_decode": dec2,
-                     "bytes_plain_over_dictionary": round(c0 / c1, 2)})
+                     "bytes_plain_over_dictionary": round(c0 / c1, 2),
+                     "create_cdict": create, "compress_by_turns": turns})
     eng.close()
     return outs
 
