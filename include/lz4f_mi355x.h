@@ -563,6 +563,70 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_eng
                                                                  const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
                                                                  const lz4f_mi355x_cdict* cdict);
 
+/* BATCH PACK: the frames of a batch back to back in one contiguous stream - what is stored or sent - made on the device, on the same
+ * stream, behind lz4f_mi355x_dev_compressFrames (or its _usingDict / _usingCDict forms), from that call's windows and records as they
+ * are: "compress -> pack -> send" with no record read back, no host prefix sum and no copy per frame.  d_src / srcBytes / d_src_off
+ * are the compress call's d_dst / dstBytes / d_dst_off, d_results its records.  Back-to-back LZ4 frames are a valid concatenated .lz4
+ * stream: `lz4 -d` decodes the packed bytes to the inputs in order, with or without the directory.
+ * Conventions as for the other batch calls: offsets (n_frames + 1 uint64) and records in DEVICE memory, 8-byte aligned; the data at
+ * any byte address; srcBytes / dstBytes host values that bound every span; asynchronous on the engine's stream, no host
+ * synchronisation, no device->host copy, two kernel launches whatever n_frames is; the workspace is one control block.
+ *   - Pack never parses frame bytes: it copies what the records say.  Frame i is usable when d_results[i].status == 0,
+ *     src_off[i] <= src_off[i+1] <= srcBytes and d_results[i].size <= src_off[i+1] - src_off[i].  L[i] is that size when the frame is
+ *     usable and 0 otherwise: a frame the encoder failed keeps its slot as an empty span, slot i stays frame i, and the batch decoder
+ *     gives the empty span ERROR_frameHeader_incomplete as it does today.
+ *   - Output: D = lz4f_mi355x_packDirectorySize(n_frames) with LZ4F_MI355X_PACK_DIRECTORY in flags, 0 without; d_dst_off[0] = D,
+ *     d_dst_off[i+1] = d_dst_off[i] + L[i]; frame i's L[i] bytes stand at d_dst + d_dst_off[i].  The first d_dst_off[n_frames] bytes
+ *     of d_dst, with d_dst_off, are what lz4f_mi355x_dev_measureFrames, lz4f_mi355x_dev_decompressFrames and _usingDict take as d_src,
+ *     srcBytes and d_src_off.  Nothing is written outside d_dst[0 .. d_dst_off[n_frames]), the n_frames + 1 offsets and the record;
+ *     nothing is read outside d_src[src_off[i] .. src_off[i] + L[i]), the offsets and the records.  d_dst_off is an array of its
+ *     own: not d_src_off, and not inside d_dst.
+ *   - d_pack (DEVICE memory, may be NULL): size = d_dst_off[n_frames]; consumed = the sum of L; n_blocks = the frames with L[i] > 0;
+ *     first_bad_block = the first i whose record says status 0 but is not usable (offsets or a size that lie; 0xFFFFFFFF: none - the
+ *     pack succeeds all the same); flags = LZ4F_MI355X_PATH_BATCH; status 0, but
+ *       ERROR_dstMaxSize_tooSmall when d_dst_off[n_frames] > dstBytes: no byte of d_dst is written; d_dst_off and size still say
+ *         what was needed;
+ *       ERROR_srcSize_tooLarge when the directory is asked for and some L[i] > 0xFFFFFFFF (a length the directory's u32 cannot say;
+ *         likewise more than 0x3FFFFFFB frames, whose payload size it cannot say): nothing is written to d_dst.
+ *     (Both at once: ERROR_dstMaxSize_tooSmall.)
+ *   - THE DIRECTORY (LZ4F_MI355X_PACK_DIRECTORY): one skippable frame at the front of the stream, which every LZ4 reader steps over as
+ *     the format requires, so that the one buffer is all a receiver needs: u32 magic 0x184D2A5D, u32 payloadBytes = 16 + 4 * n_frames,
+ *     then the payload: u32 tag 0x44505A4C ("LZPD"), u32 n_frames, u64 framesBytes (the sum of L), u32 L[n_frames].  Little-endian, at
+ *     any alignment.  D = 24 + 4 * n_frames.
+ *   - The call itself fails only on a null engine, a null pointer with n_frames > 0 (d_pack excepted), a failed allocation, or a d_dst
+ *     range [d_dst, d_dst + dstBytes) that overlaps [d_src, d_src + srcBytes): ERROR_GENERIC ("d_dst overlaps d_src"), checked on the
+ *     host, nothing enqueued.  n_frames == 0 returns 0 and enqueues nothing.
+ * The copy is dealt by OUTPUT bytes, LZ4F_MI355X_PACK_TILE of them to a workgroup at a time, so that 16 384 frames of 350 bytes and
+ * three frames of 4 MiB load the machine alike.
+ *
+ * THE RECEIVING SIDE.  lz4f_mi355x_packDirectorySize: D for n_frames frames (host arithmetic).
+ * lz4f_mi355x_peekPackDirectory reads the directory's fixed 24 bytes from HOST memory (a receiver has the head of a message on the
+ * host, or copies 24 bytes itself) -> D, and *n_frames and *framesBytes (each may be NULL); ERROR_frameHeader_incomplete for fewer
+ * than 24 bytes (or a NULL head), ERROR_frameType_unknown for another magic or tag, ERROR_frameSize_wrong where payloadBytes !=
+ * 16 + 4 * n_frames.  The stream is then D + framesBytes bytes.
+ * lz4f_mi355x_dev_readPackDirectory turns the directory of the stream in d_pack[0 .. packBytes) into d_src_off (n_frames + 1 uint64,
+ * DEVICE memory) for the measure and decode calls, one launch on the engine's stream, every read bounded by packBytes.  It checks, in
+ * this order: the fixed part as the peek does; the stored n_frames against the argument (ERROR_frameSize_wrong); packBytes >= D
+ * (ERROR_frameHeader_incomplete); framesBytes == the sum of L (ERROR_frameSize_wrong); D + framesBytes <= packBytes
+ * (ERROR_frameHeader_incomplete).  When it accepts: d_src_off[0] = D, then the running sums; d_result (DEVICE memory, may be NULL):
+ * status 0, size = framesBytes, consumed = D + framesBytes, n_blocks = n_frames.  When it refuses: n_frames + 1 zeros - every span
+ * empty, so a forged directory never hands a later call a span outside the buffer (the batch calls' own span checks stand behind it
+ * in any case) - and d_result: that status, size, consumed and n_blocks 0.  flags = LZ4F_MI355X_PATH_BATCH, first_bad_block
+ * 0xFFFFFFFF.  The call itself fails only on a null engine, a null d_pack or d_src_off with n_frames > 0, or a failed allocation;
+ * n_frames == 0 returns 0 and enqueues nothing. */
+#define LZ4F_MI355X_PACK_DIRECTORY 0x1u     /* flags: write the frame directory in front of the frames */
+#define LZ4F_MI355X_PACK_TILE      16384u   /* informational: the copy kernel's output tile, for tests and tools */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_packFrames(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                  const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                  const lz4f_mi355x_result* d_results,
+                                                  void* d_dst, size_t dstBytes, uint64_t* d_dst_off,
+                                                  unsigned flags, lz4f_mi355x_result* d_pack);
+LZ4F_MI355X_API size_t lz4f_mi355x_packDirectorySize(uint32_t n_frames);
+LZ4F_MI355X_API size_t lz4f_mi355x_peekPackDirectory(const void* head, size_t headBytes, uint32_t* n_frames, uint64_t* framesBytes);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                         const void* d_pack, size_t packBytes, uint64_t* d_src_off,
+                                                         lz4f_mi355x_result* d_result);
+
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,
                                              const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out);

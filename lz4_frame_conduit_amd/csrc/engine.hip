@@ -16,6 +16,7 @@
 #include "decode_batch.cuh"
 #include "encode_batch.cuh"
 #include "measure_batch.cuh"
+#include "pack_batch.cuh"
 
 using namespace lz4f;
 
@@ -177,7 +178,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); cframes.release(); cblocks.release(); cchunks.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); pctl.release(); cframes.release(); cblocks.release(); cchunks.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -962,6 +963,7 @@ size_t lz4f_mi355x_engine::launch_decompress(const DecompressJob& j, lz4f_mi355x
 // C ABI: engine + device-pointer entry points
 // ---- the batch calls: many frames, one call, no host read ----
 constexpr uint32_t BATCH_GRID = 8192;       // workgroups at most of a kernel that strides over a table's entries in use
+constexpr uint32_t PK_GRID = 65536;         // the same of the pack's copy kernel: a workgroup per tile up to 1 GiB of output (the dispatcher deals them as CUs come free), striding beyond
 
 // what every batch call begins with, once its own argument checks are through: its pointers, the device, and the work an earlier
 // call left on the aux stream (aux_pending is set here only after launch_decompress's error path failed to join it)
@@ -1274,6 +1276,38 @@ size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, c
     hipLaunchKernelGGL((k_mf_finish<W>), dim3(gw), dim3(64 * W), 0, st, (const MeasFrame*)frames, n_frames, (const MeasBlk*)table, (ResultRec*)d_results, wins);
     if (d_dst_off) hipLaunchKernelGGL(k_mf_scan, dim3(1), dim3(1024), 0, st, (const uint64_t*)wins, n_frames, d_dst_off);
     return batch_end("dev_measureFrames");
+}
+
+// the frames of a batch back to back (pack_batch.cuh): the scan, then the copy dealt by output bytes
+size_t lz4f_mi355x_dev_packFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                  const lz4f_mi355x_result* d_results, void* d_dst, size_t dstBytes, uint64_t* d_dst_off,
+                                  unsigned flags, lz4f_mi355x_result* d_pack)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (const size_t r = batch_begin(e, "dev_packFrames", d_src && d_src_off && d_results && d_dst && d_dst_off)) return r;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (srcBytes && dstBytes && s0 < d0 + dstBytes && d0 < s0 + srcBytes) { set_last_error("dev_packFrames: d_dst overlaps d_src"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (e->pctl.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
+    uint32_t* ctl = (uint32_t*)e->pctl.p;
+    hipStream_t st = (hipStream_t)e->stream;
+    hipLaunchKernelGGL(k_pk_scan, dim3(1), dim3(1024), 0, st, (const ResultRec*)d_results, d_src_off, (uint64_t)srcBytes, n_frames, (uint8_t*)d_dst,
+                       (uint64_t)dstBytes, d_dst_off, (uint32_t)(flags & LZ4F_MI355X_PACK_DIRECTORY), ctl, (ResultRec*)d_pack);
+    // (the tiles of dstBytes output bytes, and one for the destination's shift: the most the copy can have)
+    hipLaunchKernelGGL(k_pk_copy, batch_grid((uint64_t)dstBytes / PK_TILE + 2, 1, PK_GRID), dim3(PK_THREADS), 0, st, (const uint8_t*)d_src, d_src_off, n_frames,
+                       (uint8_t*)d_dst, (const uint64_t*)d_dst_off, (const uint32_t*)ctl);
+    return batch_end("dev_packFrames");
+}
+
+size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_pack, size_t packBytes, uint64_t* d_src_off,
+                                         lz4f_mi355x_result* d_result)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (const size_t r = batch_begin(e, "dev_readPackDirectory", d_pack && d_src_off)) return r;
+    hipLaunchKernelGGL(k_pk_readdir, dim3(1), dim3(1024), 0, (hipStream_t)e->stream, (const uint8_t*)d_pack, (uint64_t)packBytes, n_frames, d_src_off,
+                       (ResultRec*)d_result);
+    return batch_end("dev_readPackDirectory");
 }
 
 // `digest` (a prepared dictionary's, made by k_solo_digest_dict from these very dictSize bytes; NULL: none): the finder copies it where

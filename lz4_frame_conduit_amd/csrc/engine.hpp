@@ -78,6 +78,7 @@ struct lz4f_mi355x_engine {
     lz4f::DevBuf d_in, d_out;                              // staging for the host-pointer paths
     lz4f::DevBuf bframes, btable;                          // dev_decompressFrames: per-frame records + control words, the batch's block table
     lz4f::DevBuf mframes, mtable;                          // dev_measureFrames: per-frame records, windows, counts + control words, the batch's block table
+    lz4f::DevBuf pctl;                                     // dev_packFrames: the control block (the scan's verdict, for the copy)
     lz4f::DevBuf cframes, cblocks, cchunks;                // dev_compressFrames: per-frame records + control words, the batch's block and chunk tables (ChunkInfo: `info`, records: `recs`)
     lz4f::PinBuf h_in, h_out, h_small;
     // A-B and development switches: read from the environment ONCE, when the engine is made (engines of the host-pointer calls

@@ -111,6 +111,31 @@ LZ4F_FN uint32_t skippable_span(const uint8_t* p, uint64_t n, uint64_t& consumed
     return n < consumed ? ST_INCOMPLETE : (uint32_t)ST_OK;
 }
 
+// ---- the frame directory of a packed stream (lz4f_mi355x_dev_packFrames with LZ4F_MI355X_PACK_DIRECTORY) ----
+// One skippable frame in front of the frames: u32 magic, u32 payloadBytes = 16 + 4 * n_frames, then the payload: u32 tag, u32
+// n_frames, u64 framesBytes (the sum of the lengths), u32 L[n_frames].  Little-endian, at any alignment.  (0xE is the trailer's.)
+constexpr uint32_t PACKDIR_MAGIC = SKIP_MAGIC | 0xDu, PACKDIR_TAG = 0x44505A4Cu;       // "LZPD"
+constexpr uint32_t PACKDIR_HEAD = 24, PACKDIR_MOST = (0xFFFFFFFFu - 16u) / 4u;          // the fixed part; the most frames a payload's u32 size can say
+LZ4F_FN uint64_t pack_dir_size(uint32_t n_frames) { return PACKDIR_HEAD + 4ull * n_frames; }
+LZ4F_FN uint64_t pack_dir_len_at(uint32_t i) { return PACKDIR_HEAD + 4ull * i; }       // where L[i] stands
+LZ4F_FN void pack_dir_head_write(uint8_t* p, uint32_t n_frames, uint64_t frames_bytes)
+{
+    st32le(p, PACKDIR_MAGIC); st32le(p + 4, 16u + 4u * n_frames);
+    st32le(p + 8, PACKDIR_TAG); st32le(p + 12, n_frames);
+    st32le(p + 16, (uint32_t)frames_bytes); st32le(p + 20, (uint32_t)(frames_bytes >> 32));
+}
+// the fixed part in p[0..n) -> ST_OK, the frames and the sum of their lengths as the directory states them; or ST_INCOMPLETE for fewer
+// than 24 bytes, ST_FRAMETYPE for another magic or tag, ST_FRAMESIZE where the payload's size is not that of n_frames lengths
+LZ4F_FN uint32_t pack_dir_head_parse(const uint8_t* p, uint64_t n, uint32_t& n_frames, uint64_t& frames_bytes)
+{
+    if (n < PACKDIR_HEAD) return ST_INCOMPLETE;
+    if (rd32le(p) != PACKDIR_MAGIC || rd32le(p + 8) != PACKDIR_TAG) return ST_FRAMETYPE;
+    n_frames = rd32le(p + 12);
+    frames_bytes = rd64le(p + 16);
+    if (n_frames > PACKDIR_MOST || rd32le(p + 4) != 16u + 4u * n_frames) return ST_FRAMESIZE;
+    return ST_OK;
+}
+
 // ---- the blocks ----
 // One hop: the size word `w` of a frame of block size `bs`, `bytes_left` of the frame behind the word -> ST_OK, the payload's size
 // and how far behind the word the next word is (payload and block checksum); or why the walk ends here.  The EndMark is ST_OK

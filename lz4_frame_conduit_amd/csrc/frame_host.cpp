@@ -685,6 +685,17 @@ size_t lz4f_mi355x_compressFrameBound(size_t srcSize, const LZ4F_preferences_t* 
     return LZ4F_HEADER_SIZE_MAX + srcSize + nblocks * (4 + (p.frameInfo.blockChecksumFlag ? 4 : 0)) + 4 + (p.frameInfo.contentChecksumFlag ? 4 : 0);
 }
 
+// ---- the frame directory of a packed stream (lz4f_mi355x_dev_packFrames): host arithmetic, and the fixed part read from host memory ----
+size_t lz4f_mi355x_packDirectorySize(uint32_t n_frames) { return (size_t)pack_dir_size(n_frames); }
+size_t lz4f_mi355x_peekPackDirectory(const void* head, size_t headBytes, uint32_t* n_frames, uint64_t* framesBytes)
+{
+    uint32_t n = 0; uint64_t fb = 0;
+    if (const uint32_t st = pack_dir_head_parse((const uint8_t*)head, head ? headBytes : 0, n, fb)) return make_err((int)st);
+    if (n_frames) *n_frames = n;
+    if (framesBytes) *framesBytes = fb;
+    return (size_t)pack_dir_size(n);
+}
+
 size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src, size_t srcSize, const LZ4F_preferences_t* prefs)
 {
     // header / all blocks through the slab pipeline (pipeline.hip: several slabs in flight, over lz4f_mi355x_use_devices() GPUs) /

@@ -77,6 +77,79 @@ def _check_measure_args(src, src_off, results, dst_off, rec_bytes: int) -> int:
     return n
 
 
+def _check_tensors(named, what: str = "a batch") -> None:
+    """(name, tensor, dtype) triples: contiguous 1-d device tensors of those types on one device; ValueError otherwise."""
+    for name, t, dt in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s must be a tensor" % name)
+        if t.dtype != dt:
+            raise ValueError("%s must be %s, not %s" % (name, dt, t.dtype))
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous 1-d tensor" % name)
+    if not all(t.is_cuda for _, t, _ in named):
+        raise ValueError("the tensors of %s must be in device memory" % what)
+    if len({t.device for _, t, _ in named}) != 1:
+        raise ValueError("the tensors of %s must be on one device" % what)
+
+
+def _check_pack_args(src, src_off, results, dst, dst_off, record, rec_bytes: int) -> int:
+    """The tensors of a pack call (Engine.pack_frames_async) -> the number of frames; ValueError for what is wrong with them."""
+    named = [("src", src, torch.uint8), ("src_off", src_off, torch.int64), ("results", results, torch.uint8), ("dst", dst, torch.uint8),
+             ("dst_off", dst_off, torch.int64)]
+    if record is not None:
+        named.append(("record", record, torch.uint8))
+    _check_tensors(named)
+    if src_off.numel() < 1 or src_off.numel() != dst_off.numel():
+        raise ValueError("src_off and dst_off must both hold n+1 offsets (got %d and %d)" % (src_off.numel(), dst_off.numel()))
+    n = src_off.numel() - 1
+    if n >= 1 << 32:
+        raise ValueError("too many frames for one call")
+    if results.numel() < n * rec_bytes:
+        raise ValueError("results must hold %d bytes for %d frames (got %d)" % (n * rec_bytes, n, results.numel()))
+    if record is not None and record.numel() < rec_bytes:
+        raise ValueError("record must hold %d bytes (got %d)" % (rec_bytes, record.numel()))
+    return n
+
+
+def _check_read_directory_args(pack, n_frames, src_off, record, rec_bytes: int) -> int:
+    """The arguments of Engine.read_pack_directory_async -> the number of frames; ValueError for what is wrong with them."""
+    named = [("pack", pack, torch.uint8), ("src_off", src_off, torch.int64)]
+    if record is not None:
+        named.append(("record", record, torch.uint8))
+    _check_tensors(named, "a directory read")
+    if not isinstance(n_frames, int) or isinstance(n_frames, bool) or not 0 <= n_frames < 1 << 32:
+        raise ValueError("n_frames must be an int in [0, 2^32)")
+    if src_off.numel() != n_frames + 1:
+        raise ValueError("src_off must hold n_frames+1 = %d offsets (got %d)" % (n_frames + 1, src_off.numel()))
+    if record is not None and record.numel() < rec_bytes:
+        raise ValueError("record must hold %d bytes (got %d)" % (rec_bytes, record.numel()))
+    return n_frames
+
+
+PACK_TILE = 16384       # LZ4F_MI355X_PACK_TILE: the output bytes a workgroup of the pack's copy kernel takes at a time (for tests and tools)
+PACK_DIRECTORY = 0x1    # LZ4F_MI355X_PACK_DIRECTORY
+
+
+def pack_directory_size(n: int) -> int:
+    """The bytes of a packed stream's frame directory for n frames (24 + 4 n).  Host arithmetic only: no device is touched."""
+    if not isinstance(n, int) or isinstance(n, bool) or not 0 <= n < 1 << 32:
+        raise ValueError("n must be an int in [0, 2^32)")
+    return int(_ffi.lib().lz4f_mi355x_packDirectorySize(n))
+
+
+def peek_pack_directory(head: bytes) -> "tuple[int, int, int]":
+    """The fixed part of a packed stream's directory, from its first 24 bytes in host memory -> (directory bytes, n_frames, frames
+    bytes): the stream is directory bytes + frames bytes long, and Engine.read_pack_directory_async wants that n_frames.
+    DeviceCodecError (frameHeader_incomplete, frameType_unknown, frameSize_wrong) for what is not such a head."""
+    if not isinstance(head, (bytes, bytearray, memoryview)):
+        raise ValueError("head must be bytes")
+    head = bytes(head)
+    L = _ffi.lib()
+    n, fb = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    d = _chk(L, L.lz4f_mi355x_peekPackDirectory(head, len(head), ctypes.byref(n), ctypes.byref(fb)))
+    return int(d), int(n.value), int(fb.value)
+
+
 def frame_windows(lengths, prefs: Preferences, gap: int = 0) -> "list[int]":
     """Window offsets for Engine.compress_frames_async: n+1 cumulative offsets, window i being
     lz4f_mi355x_compressFrameBound(lengths[i], prefs) bytes - which always suffice for input i's frame - plus `gap` spare bytes
@@ -310,6 +383,49 @@ class Engine:
             return
         _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
                                                           dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr()))
+
+    def pack_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, results: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor,
+                          directory: bool = False, record: "torch.Tensor | None" = None):
+        """Enqueue the compaction of a batch, behind compress_frames_async on the same stream: src, src_off and results are that
+        call's dst, dst_off and results as they are; the frames come to lie back to back in dst, frame i at dst[dst_off[i]:dst_off[i+1]]
+        (dst_off: int64 device tensor of n+1 elements, written here).  No frame byte is parsed: frame i is results[i].size bytes when
+        its record says status 0 and size and offsets hold (src_off[i] <= src_off[i+1] <= src.numel(), size within the window), and an
+        empty span otherwise - slot i stays frame i, and the batch decoder reports frameHeader_incomplete for it.
+        directory=True puts the frame directory in front (a skippable frame of pack_directory_size(n) bytes, which every LZ4 reader
+        steps over): dst_off[0] is then its size, and a receiver needs nothing but the stream (read_pack_directory_async).
+        dst[:dst_off[n]] with dst_off is what measure_frames_async and decompress_frames_async take as src and src_off, and what
+        `lz4 -d` decodes to the inputs in order.  dst must not overlap src (DeviceCodecError; nothing is enqueued).
+        record (uint8 device tensor of 32 bytes, optional) receives one Result: size = dst_off[n], consumed = the frames' bytes,
+        n_blocks = the non-empty frames, first_bad_block = the first record with status 0 whose size or offsets lie (0xFFFFFFFF:
+        none), status dstMaxSize_tooSmall when dst is smaller than dst_off[n] (dst is then untouched; dst_off and size say what was
+        needed) or srcSize_tooLarge when the directory cannot say a frame's length (> 0xFFFFFFFF).  Nothing is read back: no
+        synchronisation.  On one stream:
+
+            eng.compress_frames_async(inp, inp_off, win, win_off, prefs, results, cdict=cd)
+            eng.pack_frames_async(win, win_off, results, out, out_off, directory=True, record=rec)
+            # send out[:size] - size is Result.from_buffer_copy(rec.cpu().numpy().tobytes()).size, the one read-back"""
+        n = _check_pack_args(src, src_off, results, dst, dst_off, record, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_packFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), results.data_ptr(), dst.data_ptr(),
+                                                      dst.numel(), dst_off.data_ptr(), PACK_DIRECTORY if directory else 0,
+                                                      record.data_ptr() if record is not None else None))
+
+    def read_pack_directory_async(self, pack: torch.Tensor, n_frames: int, src_off: torch.Tensor, record: "torch.Tensor | None" = None):
+        """Enqueue the reading of a packed stream's directory (pack_frames_async(directory=True)): pack is the stream, a uint8 device
+        tensor; n_frames what peek_pack_directory said of its head; src_off (int64 device tensor of n_frames+1 elements) receives
+        the frames' offsets into pack, as measure_frames_async and decompress_frames_async take them.  Everything is checked on the
+        device, every read bounded by pack.numel(): magic, tag and sizes, the stored n_frames against the argument, the lengths' sum
+        against the stated frames bytes, and the whole stream against pack.numel().  A directory that fails gives n_frames+1 zeros -
+        every span empty, every frame frameHeader_incomplete to the decoder - and its status in record (uint8 device tensor of 32
+        bytes, optional: status, size = frames bytes, consumed = the stream's bytes, n_blocks = n_frames).  Nothing is read back.
+        On one stream, with the head of the message on the host:
+
+            d, n, fb = peek_pack_directory(head24)
+            eng.read_pack_directory_async(pack, n, src_off)
+            eng.measure_frames_async(pack, src_off, results, dst_off)
+            eng.decompress_frames_async(pack, src_off, dst, dst_off, results)"""
+        n = _check_read_directory_args(pack, n_frames, src_off, record, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_readPackDirectory(self.h, n, pack.data_ptr(), pack.numel(), src_off.data_ptr(),
+                                                             record.data_ptr() if record is not None else None))
 
     def frame_results(self, results: torch.Tensor) -> "list[Result]":
         """Wait for the stream, then the records of a batch (status 0 = ok; otherwise the LZ4F error code of that frame)."""
