@@ -521,8 +521,10 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uin
  *     d_dict == NULL with dictSize > 0 and n_frames > 0 is a call error.
  *   - prefs->frameInfo.dictID is written to the header as before and means nothing else to this library: it is not derived from the
  *     dictionary and not checked on decode.  Matching IDs to dictionaries is the caller's job.
- *   - compressionLevel 3-12 with dictSize > 0: the call returns ERROR_compressionLevel_invalid and enqueues nothing (the hash-chain
- *     finder does not know the dictionary yet).  Levels <= 2 take it.
+ *   - compressionLevel 3-12 with dictSize > 0: the call returns ERROR_compressionLevel_invalid and enqueues nothing.  Levels <= 2
+ *     take it.  (The hash-chain finder inserts 960 positions per barrier round through one wave: seeding a raw 64 KiB dictionary
+ *     would put 69 such rounds in front of every record.  At those levels a dictionary comes prepared:
+ *     lz4f_mi355x_dev_createCDictHC below.)
  *   - Frame i is a function of input i, the dictionary and prefs alone: the same bytes in a batch of one and in a batch of many.  A
  *     match is cut where the dictionary ends and the input begins (liblz4 may let one run across; the decoders take both).
  *   - Everything said above about the plain call holds: spans, windows, isolation, the record's fields, LZ4F_MI355X_PATH_BATCH, the
@@ -552,9 +554,27 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engi
  * lz4f_mi355x_dev_compressFrames_usingCDict is lz4f_mi355x_dev_compressFrames_usingDict with the CDict's copy for d_dict / dictSize:
  * every sentence above holds, and frame i and d_results[i] are byte for byte what that call writes for the same inputs, prefs and
  * dictionary bytes.  A NULL or empty cdict is lz4f_mi355x_dev_compressFrames (the same kernels, the same bytes); compressionLevel 3-12
- * with a non-empty one returns ERROR_compressionLevel_invalid and enqueues nothing. */
+ * with a non-empty one of lz4f_mi355x_dev_createCDict returns ERROR_compressionLevel_invalid and enqueues nothing: that CDict has no
+ * digest for the hash-chain finder, and making one per call is what a prepared dictionary is there to avoid.
+ *
+ * lz4f_mi355x_dev_createCDictHC is lz4f_mi355x_dev_createCDict plus the hash-chain finder's digest: the CDict then serves every
+ * compressionLevel.  Arguments, errors, ownership, engine affinity, lz4f_mi355x_cdict_data and lz4f_mi355x_dev_freeCDict are as above.
+ *   - Still one device allocation - the digest above, the hash-chain digest, the copy - which grows by at most 147 456 bytes: the
+ *     finder's head (16 KiB) and 2 bytes for each of the at most 65 536 chain slots, as they stand once the dictionary's positions
+ *     have been inserted in order.  One more kernel (one workgroup) is enqueued on the engine's stream; nothing synchronises.
+ *   - lz4f_mi355x_dev_compressFrames_usingCDict with compressionLevel >= 3 and such a CDict runs the hash-chain finder with the
+ *     dictionary in front of every frame (linked) or block (independent): a scope's first chunk loads the digest where it would
+ *     clear its tables.  Every other sentence of that call's contract holds: spans, windows, isolation, the record's fields,
+ *     LZ4F_MI355X_PATH_BATCH, the workspace formula, a launch count independent of n_frames, any byte alignment; frame i is a
+ *     function of input i, the dictionary bytes, prefs and the level alone (and of LZ4F_MI355X_HC_ATTEMPTS / LZ4F_MI355X_HC_LAZY
+ *     where set).  A match is cut at the seam, as at levels <= 2.
+ *   - At levels <= 2 it is the plain CDict: the same kernel, the same bytes.  Empty, or of 1-3 bytes, it gives at levels 3-12 the
+ *     frames of lz4f_mi355x_dev_compressFrames at that level, byte for byte (the copy is kept for the decoder).
+ * lz4f_mi355x_cdict_has_hc: 1 when the CDict was made by lz4f_mi355x_dev_createCDictHC, else 0 (NULL: 0). */
 typedef struct lz4f_mi355x_cdict lz4f_mi355x_cdict;
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_createCDict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_createCDictHC(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize);
+LZ4F_MI355X_API int    lz4f_mi355x_cdict_has_hc(const lz4f_mi355x_cdict* c);
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c);
 LZ4F_MI355X_API const void* lz4f_mi355x_cdict_data(const lz4f_mi355x_cdict* c, size_t* size);
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t n_frames,

@@ -90,6 +90,7 @@ _SIGS = {
     "lz4f_mi355x_dev_compressFrames_usingDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p, c_size_t]),
     "lz4f_mi355x_dev_createCDict": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t]), "lz4f_mi355x_dev_freeCDict": (c_size_t, [c_void_p]),
     "lz4f_mi355x_cdict_data": (c_void_p, [c_void_p, ctypes.POINTER(c_size_t)]),
+    "lz4f_mi355x_dev_createCDictHC": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t]), "lz4f_mi355x_cdict_has_hc": (ctypes.c_int, [c_void_p]),
     "lz4f_mi355x_dev_compressFrames_usingCDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p]),
     "lz4f_mi355x_dev_packFrames": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_uint, c_void_p]),
     "lz4f_mi355x_packDirectorySize": (c_size_t, [ctypes.c_uint32]),

@@ -18,7 +18,8 @@
 //                  <= 2) or hc_find_chunk (encode_hc.cuh, a workgroup per chunk, levels 3-12) - the very functions the single call's
 //                  kernels run, so a frame's records are what they would be alone
 //                  (k_bc_find_solo_dict: the same finder with the call's shared dictionary in front of every low_abs;
-//                  k_bc_find_solo_cdict: with a prepared dictionary, whose digested table a scope's first chunk copies)
+//                  k_bc_find_solo_cdict: with a prepared dictionary, whose digested table a scope's first chunk copies;
+//                  k_bc_find_hc_cdict: levels 3-12 with a prepared dictionary that carries the hash-chain digest)
 //   k_bc_layout    a wave per block: layout_block_chunks (pass S's per-block step: carries, raw fallback) -> the size word
 //   k_bc_frames    a wave per frame: the blocks placed behind the header, the window judged, then header (made here: content size and
 //                  HC byte are the frame's own), size words, EndMark, every chunk's place in the destination, the result record
@@ -230,6 +231,27 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc(const uint8_t* __r
         if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
         const EncPlace pl = bc_place_of(e);
         hc_find_chunk(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh);
+        __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
+    }
+}
+
+// the same with a prepared dictionary that carries the hash-chain digest (lz4f_mi355x_dev_createCDictHC): a chunk with the dictionary
+// alone in front of it - cs_abs == low_abs: every frame's first chunk, and every independent block's - loads `digest` (head and
+// chain[0 .. D), k_hc_digest_dict) into the workgroup's LDS where k_bc_find_hc clears head, and walks on from the batch that holds
+// the seam.  All of it is loaded again for every such chunk, so nothing depends on the chunks this workgroup had before; every other
+// chunk has 64 KiB of input in front of it and runs as in k_bc_find_hc.  The same HcShared: the digest needs no LDS of its own
+__global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc_cdict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
+                                                                    const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
+                                                                    ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf,
+                                                                    const uint8_t* __restrict__ dict_end, uint32_t dict_len, const uint4* __restrict__ digest)
+{
+    __shared__ HcShared sh;
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BcChunk e = chunks[w];
+        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
+        const EncPlace pl = bc_place_of(e);
+        hc_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dict_end, dict_len, digest);
         __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
     }
 }

@@ -998,11 +998,14 @@ struct Carve {
     template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
 };
 
-// A prepared dictionary (lz4f_mi355x_dev_createCDict): its engine's, never written after the stream has run its creation.
-// One device allocation: the digest (SOLO_DIGEST_BYTES: the finder's table and tags, seeded), then `size` (<= 64 KiB) dictionary bytes
+// A prepared dictionary (lz4f_mi355x_dev_createCDict / _createCDictHC): its engine's, never written after the stream has run its creation.
+// One device allocation: the digest (SOLO_DIGEST_BYTES: the finder's table and tags, seeded), the hash-chain finder's digest where asked
+// for (lz4f_mi355x_dev_createCDictHC: hc_digest_bytes(size), head and chain), then `size` (<= 64 KiB) dictionary bytes
 struct lz4f_mi355x_cdict {
     lz4f_mi355x_engine* engine = nullptr;
     uint4* digest = nullptr;               // the allocation; NULL: an empty dictionary
+    uint4* hc_digest = nullptr;            // NULL: none (made by createCDict, or an empty dictionary)
+    bool hc = false;                       // made by createCDictHC: serves levels 3-12 too
     uint8_t* data = nullptr;
     size_t size = 0;
 };
@@ -1311,10 +1314,12 @@ size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frame
 }
 
 // `digest` (a prepared dictionary's, made by k_solo_digest_dict from these very dictSize bytes; NULL: none): the finder copies it where
-// it would seed from the dictionary alone
+// it would seed from the dictionary alone.  `hc_dict`: the dictionary is a prepared one made for levels 3-12 too, and `hc_digest` its
+// hash-chain digest (k_hc_digest_dict; NULL: fewer than 4 bytes, which the finder ignores)
 static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                               void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize, const uint4* digest = nullptr)
+                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize, const uint4* digest = nullptr,
+                              bool hc_dict = false, const uint4* hc_digest = nullptr)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
@@ -1322,8 +1327,12 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
     const size_t bs = block_size_of(p.frameInfo.blockSizeID);
     if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
-    // (levels 3-12 have no dictionary yet: hc_find_chunk does not know it.  Nothing is enqueued)
-    if (dictSize && p.compressionLevel >= 3) { set_last_error("dev_compressFrames_usingDict: levels 3-12 take no dictionary"); return make_err(LZ4F_ERROR_compressionLevel_invalid); }
+    // (levels 3-12 take a dictionary only with the hash-chain digest: seeding a raw one costs up to 69 barrier rounds in front of
+    // every chunk.  Nothing is enqueued)
+    if (dictSize && p.compressionLevel >= 3 && !hc_dict) {
+        set_last_error("dev_compressFrames_usingDict: levels 3-12 take a dictionary only as a CDict of dev_createCDictHC");
+        return make_err(LZ4F_ERROR_compressionLevel_invalid);
+    }
     if (n_frames == 0) return 0;
     if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (d_dict || !dictSize))) return r;
     const uint8_t* dict_end; uint32_t dict_len;
@@ -1367,7 +1376,10 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
     hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
     hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
-    if (hc)
+    if (hc && dict_len && hc_digest)
+        hipLaunchKernelGGL(k_bc_find_hc_cdict, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
+                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf, dict_end, dict_len, hc_digest);
+    else if (hc)                                                       // (also a prepared dictionary of 1-3 bytes: the finder ignores it)
         hipLaunchKernelGGL(k_bc_find_hc, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
                            (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
     else if (dict_len && digest)
@@ -1406,44 +1418,59 @@ size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t 
     return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, d_dict, dictSize);
 }
 
-// ---- the prepared dictionary: the dictionary's last 64 KiB, owned, and the finder's table seeded from them once ----
-size_t lz4f_mi355x_dev_createCDict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize)
+// ---- the prepared dictionary: the dictionary's last 64 KiB, owned, and the finder's table seeded from them once (createCDictHC: the
+// hash-chain finder's head and chain too) ----
+// `hc`: with the hash-chain finder's digest between the solo digest and the copy (`who`: the call's name in messages)
+static size_t create_cdict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize, bool hc, const char* who)
 {
     if (out) *out = nullptr;
-    if (!e || !out || (!d_dict && dictSize)) { set_last_error("dev_createCDict: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (!e || !out || (!d_dict && dictSize)) { set_last_error("%s: null pointer", who); return make_err(LZ4F_ERROR_GENERIC); }
     if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
     lz4f_mi355x_cdict* c = new (std::nothrow) lz4f_mi355x_cdict();
-    if (!c) { set_last_error("dev_createCDict: out of memory"); return make_err(LZ4F_ERROR_allocation_failed); }
-    c->engine = e;
+    if (!c) { set_last_error("%s: out of memory", who); return make_err(LZ4F_ERROR_allocation_failed); }
+    c->engine = e; c->hc = hc;
     const uint8_t* dict_end; uint32_t dict_len;
     batch_dict_tail(d_dict, dictSize, dict_end, dict_len);
     if (dict_len) {
-        // one allocation: the digest (16-byte aligned: it leads), then the copy
+        // one allocation: the digests (16-byte aligned: they lead, and both are whole vectors), then the copy
         void* p = nullptr;
-        const hipError_t he = hipMalloc(&p, SOLO_DIGEST_BYTES + (size_t)dict_len);
+        const size_t hc_bytes = hc ? hc_digest_bytes(dict_len) : 0, bytes = SOLO_DIGEST_BYTES + hc_bytes + (size_t)dict_len;
+        const hipError_t he = hipMalloc(&p, bytes);
         if (he != hipSuccess) {
             (void)hipGetLastError();
-            set_last_error("dev_createCDict: hipMalloc(%zu) failed: %s", SOLO_DIGEST_BYTES + (size_t)dict_len, hipGetErrorString(he));
+            set_last_error("%s: hipMalloc(%zu) failed: %s", who, bytes, hipGetErrorString(he));
             delete c;
             return make_err(LZ4F_ERROR_allocation_failed);
         }
-        c->digest = (uint4*)p; c->data = (uint8_t*)p + SOLO_DIGEST_BYTES; c->size = dict_len;
+        c->digest = (uint4*)p; c->data = (uint8_t*)p + SOLO_DIGEST_BYTES + hc_bytes; c->size = dict_len;
+        if (hc) c->hc_digest = (uint4*)((uint8_t*)p + SOLO_DIGEST_BYTES);
         hipStream_t st = (hipStream_t)e->stream;
         if (hipMemcpyAsync(c->data, dict_end - dict_len, dict_len, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             (void)hipGetLastError(); (void)hipFree(p); delete c;
-            set_last_error("dev_createCDict: the dictionary's copy failed");
+            set_last_error("%s: the dictionary's copy failed", who);
             return make_err(LZ4F_ERROR_GENERIC);
         }
         hipLaunchKernelGGL(k_solo_digest_dict, dim3(1), dim3(64), 0, st, (const uint8_t*)c->data + dict_len, dict_len, c->digest);
+        if (hc) hipLaunchKernelGGL(k_hc_digest_dict, dim3(1), dim3(64 * HC_WAVES), 0, st, (const uint8_t*)c->data + dict_len, dict_len, c->hc_digest);
         if (hipGetLastError() != hipSuccess) {                             // (the copy may be in flight: wait before its target goes)
             (void)hipStreamSynchronize(st); (void)hipFree(p); delete c;
-            set_last_error("dev_createCDict: launch failed");
+            set_last_error("%s: launch failed", who);
             return make_err(LZ4F_ERROR_GENERIC);
         }
     }
     *out = c;
     return 0;
 }
+
+size_t lz4f_mi355x_dev_createCDict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize)
+{
+    return create_cdict(e, out, d_dict, dictSize, false, "dev_createCDict");
+}
+size_t lz4f_mi355x_dev_createCDictHC(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const void* d_dict, size_t dictSize)
+{
+    return create_cdict(e, out, d_dict, dictSize, true, "dev_createCDictHC");
+}
+int lz4f_mi355x_cdict_has_hc(const lz4f_mi355x_cdict* c) { return c && c->hc ? 1 : 0; }
 
 size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c)
 {
@@ -1474,7 +1501,7 @@ size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t
     if (cdict->engine != e) { set_last_error("dev_compressFrames_usingCDict: cdict belongs to another engine"); return make_err(LZ4F_ERROR_GENERIC); }
     // (a dictionary of 1-3 bytes: the finder ignores it, its digest is the cleared table - the _usingDict kernel, as that call launches it)
     return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, cdict->data, cdict->size,
-                           cdict->size >= 4 ? cdict->digest : nullptr);
+                           cdict->size >= 4 ? cdict->digest : nullptr, cdict->hc, cdict->size >= 4 ? cdict->hc_digest : nullptr);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

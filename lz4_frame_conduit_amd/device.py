@@ -169,13 +169,19 @@ class CDict:
     """A prepared dictionary (Engine.create_cdict): the engine's own copy of the dictionary's last 64 KiB in device memory and the
     match finder's table digested from it once.  It serves any number of compress_frames_async(..., cdict=) calls on the engine that
     made it, and decompress_frames_async(..., dictionary=) takes it too.  close() waits for the engine's stream and frees it; the
-    engine closes the ones that are still open when it is closed itself.  Use it as a context manager to close it on the way out."""
+    engine closes the ones that are still open when it is closed itself.  Use it as a context manager to close it on the way out.
+    One made with create_cdict(..., hc=True) also carries the hash-chain finder's digest and serves compression levels 3-12 (`hc`)."""
 
     def __init__(self, engine: "Engine", h):
         self.engine, self.h = engine, h
         n = ctypes.c_size_t(0)
         p = engine.L.lz4f_mi355x_cdict_data(h, ctypes.byref(n))
         self.data_ptr, self.size = (p or None), int(n.value)
+
+    @property
+    def hc(self) -> bool:
+        """Whether it carries the hash-chain finder's digest (create_cdict(..., hc=True)); False once closed."""
+        return bool(self.h) and bool(self.engine.L.lz4f_mi355x_cdict_has_hc(self.h))
 
     def close(self):
         if self.h:
@@ -299,13 +305,15 @@ class Engine:
             raise ValueError("dictionary must be a contiguous one-dimensional uint8 tensor on cuda:%d" % self.device)
         return (dictionary.data_ptr() if dictionary.numel() else None), dictionary.numel()
 
-    def create_cdict(self, dictionary: torch.Tensor) -> CDict:
+    def create_cdict(self, dictionary: torch.Tensor, hc: bool = False) -> CDict:
         """Prepare a dictionary (a uint8 tensor on the engine's device; it may be empty) for compress_frames_async(..., cdict=): its
         last 64 KiB are copied and digested on the engine's stream, once.  The tensor may be reused or freed once the stream has run
-        the call; nothing is read back."""
+        the call; nothing is read back.  hc=True also digests it for the hash-chain finder (one more kernel, up to 144 KiB more
+        device memory): the CDict then serves compression levels 3-12 too, and is the plain one at levels 0-2."""
         d_ptr, d_len = self._check_dictionary(dictionary)
         h = ctypes.c_void_p()
-        _chk(self.L, self.L.lz4f_mi355x_dev_createCDict(self.h, ctypes.byref(h), d_ptr, d_len))
+        create = self.L.lz4f_mi355x_dev_createCDictHC if hc else self.L.lz4f_mi355x_dev_createCDict
+        _chk(self.L, create(self.h, ctypes.byref(h), d_ptr, d_len))
         c = CDict(self, h)
         self._cdicts.add(c)
         return c
@@ -362,10 +370,12 @@ class Engine:
         (frame_results) - a frame whose window is too small fails alone.  Nothing is read back: no synchronisation.
         dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch - the match finder reaches into
         its last 64 KiB as if they lay in front of every input; decompress_frames_async(..., dictionary=) and liblz4's
-        LZ4F_decompress_usingDict decode the frames.  Levels 0-2 only (3-12 raise compressionLevel_invalid); prefs.frameInfo.dictID
-        is written as it is and means nothing else.
+        LZ4F_decompress_usingDict decode the frames.  Levels 0-2 only (3-12 raise compressionLevel_invalid: there a dictionary comes
+        as a CDict made with hc=True); prefs.frameInfo.dictID is written as it is and means nothing else.
         cdict (create_cdict, of this engine; not together with dictionary=): the same dictionary prepared once - the same frames,
-        byte for byte, without reading and seeding the dictionary again for every 64 KiB chunk of every call."""
+        byte for byte, without reading and seeding the dictionary again for every 64 KiB chunk of every call.  Levels 3-12 take a
+        CDict made with create_cdict(..., hc=True) - the hash-chain search with the dictionary in front of every frame or independent
+        block - and raise compressionLevel_invalid for one made without."""
         if not isinstance(prefs, Preferences):
             raise ValueError("prefs must be a Preferences")
         if cdict is not None and dictionary is not None:

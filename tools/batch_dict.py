@@ -1,6 +1,6 @@
 """Many small records with a shared dictionary: the batch calls with and without `dictionary=`, and with a prepared one (`cdict=`).  GPU box.
 
-    python tools/batch_dict.py [--cases c1,c2,..] [--runs N] [--timeout S]
+    python tools/batch_dict.py [--cases c1,c2,..] [--runs N] [--timeout S] [--level L]
 
 Cases
   plain_64k_x4096    the plain batch calls at the README's shape (synth50 and text, level 0): no dictionary anywhere, so the same
@@ -14,6 +14,10 @@ Cases
                      and records checked to be the dictionary call's, byte for byte
   dict1k_1k_x16384   the same records with the dictionary's last 1 KiB as the dictionary (d1k): there the digest's 11.25 KiB are
   dict1k_16k_x4096   more than the dictionary they stand for
+--level L (3-12; the default 0 is everything above): the plain case runs at that level, and a dictionary case becomes the prepared
+dictionary with the hash-chain digest (create_cdict(d, hc=True)): create_cdict timed with and without hc by turns, then three compress
+calls by turns - the HC CDict at level L, the plain call at level L, the CDict at level 0 - each with its compressed bytes beside
+its time, the HC CDict's frames decoded through the dictionary decoder and checked against the input.
 Every case runs in a child process with its own time limit.  Timed with torch events on the engine's stream: a warm-up call, then
 `runs` calls, each timed on its own - the minimum, the median and the spread ((max - min) / min) are reported; GiB/s are of
 uncompressed bytes over the minimum.  Every output is checked against the input.  One JSON line per case."""
@@ -57,7 +61,7 @@ def stitched_records(np, d, n, fb):
     return np.ascontiguousarray(rec.reshape(n, -1)[:, :fb])
 
 
-def child(case: str, runs: int) -> "list[dict]":
+def child(case: str, runs: int, level: int = 0) -> "list[dict]":
     import numpy as np
     import torch
     from lz4_frame_conduit_amd import conduit, datagen
@@ -65,7 +69,8 @@ def child(case: str, runs: int) -> "list[dict]":
     n, fb, dict_bytes = CASES[case]
     dev, total = "cuda:0", n * fb
     eng = Engine(0)
-    p = conduit.make_preferences(blockSizeID=4, blockMode=1)
+    p = conduit.make_preferences(blockSizeID=4, blockMode=1, compressionLevel=level)
+    p0 = conduit.make_preferences(blockSizeID=4, blockMode=1)
     so_t = torch.arange(0, n + 1, dtype=torch.int64, device=dev) * fb
     bound = frame_windows([fb], p)[1]
     wo_t = torch.arange(0, n + 1, dtype=torch.int64, device=dev) * bound
@@ -125,7 +130,44 @@ def child(case: str, runs: int) -> "list[dict]":
                 base = torch.from_numpy(datagen.synth_text(min(total, 64 << 20), 5)).to(dev)
                 src = base.repeat((total + base.numel() - 1) // base.numel())[:total].contiguous()
             enc, dec, _, _, cbytes = roundtrip(src, None, None)
-            outs.append({"case": case, "data": data, "records": n, "record_bytes": fb, "compressed_bytes": cbytes, "compress": enc, "decompress": dec})
+            outs.append({"case": case, "data": data, "level": level, "records": n, "record_bytes": fb, "compressed_bytes": cbytes, "compress": enc, "decompress": dec})
+    elif level >= 3:
+        d_np = phrase_dictionary(np)
+        d = torch.from_numpy(d_np[-dict_bytes:].copy()).to(dev)
+        src = torch.from_numpy(stitched_records(np, d_np, n, fb)).to(dev).reshape(-1)
+        made = {"plain": [], "hc": []}
+        create = timed_by_turns({"create_cdict": lambda: made["plain"].append(eng.create_cdict(d)),
+                                 "create_cdict_hc": lambda: made["hc"].append(eng.create_cdict(d, hc=True))})
+        for v in create.values(): del v["GiB_s"]
+        for c in made["plain"][:-1] + made["hc"][:-1]: c.close()
+        cd, cd_hc = made["plain"][-1], made["hc"][-1]
+
+        def frames_bytes(pp, **kw):
+            """one call -> the frames' bytes in all; every frame made"""
+            slots.zero_(); res.zero_()
+            eng.compress_frames_async(src, so_t, slots, wo_t, pp, res, **kw)
+            rr = eng.frame_results(res)
+            assert all(r.status == 0 and r.consumed == fb for r in rr), "compress: a frame failed"
+            return sum(r.size for r in rr), rr
+
+        c_plain, _ = frames_bytes(p)
+        c_cd0, _ = frames_bytes(p0, cdict=cd)
+        c_hc, rr = frames_bytes(p, cdict=cd_hc)
+        # the HC CDict's frames through the dictionary decoder
+        sizes = torch.tensor([r.size for r in rr], dtype=torch.int64, device=dev)
+        fo_t = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        fo_t[1:] = torch.cumsum(sizes, 0)
+        frames = slots[(torch.arange(bound, device=dev)[None, :] < sizes[:, None]).reshape(-1)].contiguous()
+        back.zero_()
+        eng.decompress_frames_async(frames, fo_t, back, so_t, res, dictionary=cd_hc)
+        assert all(r.status == 0 and r.size == fb for r in eng.frame_results(res)) and torch.equal(back, src), "decode: output differs"
+        turns = timed_by_turns({"hc_cdict": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p, res, cdict=cd_hc),
+                                "plain": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p, res),
+                                "cdict_level0": lambda: eng.compress_frames_async(src, so_t, slots, wo_t, p0, res, cdict=cd)})
+        turns["hc_cdict"]["compressed_bytes"], turns["plain"]["compressed_bytes"], turns["cdict_level0"]["compressed_bytes"] = c_hc, c_plain, c_cd0
+        cd.close(); cd_hc.close()
+        outs.append({"case": case, "data": "stitched", "level": level, "records": n, "record_bytes": fb, "dictionary_bytes": dict_bytes,
+                     "create_by_turns": create, "compress_by_turns": turns})
     else:
         d_np = phrase_dictionary(np)
         d = torch.from_numpy(d_np[-dict_bytes:].copy()).to(dev)
@@ -166,15 +208,18 @@ def main():
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per case (a child process each)")
+    ap.add_argument("--level", type=int, default=0, help="0 (levels 0-2: the cases as described) or 3-12 (the HC CDict)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.level != 0 and not 3 <= a.level <= 12:
+        ap.error("--level must be 0 or 3-12")
     if a.child:
-        for o in child(a.child, a.runs):
+        for o in child(a.child, a.runs, a.level):
             print(json.dumps(o), flush=True)
         return 0
     for case in a.cases.split(","):
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--runs", str(a.runs), "--child", case], capture_output=True, text=True, timeout=a.timeout)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--runs", str(a.runs), "--level", str(a.level), "--child", case], capture_output=True, text=True, timeout=a.timeout)
         except subprocess.TimeoutExpired:
             print(json.dumps({"case": case, "error": "timeout after %d s" % a.timeout}), flush=True)
             return 1                                              # (nothing more on the GPU after a run that did not end)
