@@ -133,7 +133,7 @@ class Case:
             # mend: a free literal that takes part in a flaw gets a new value, the plants are copied again, until nothing is left
             free = np.frombuffer(bytes(b.free), np.uint8).astype(bool)
             for _ in range(40):
-                flaws = _flaws(d, b.plants, b.ghosts)
+                flaws = self.flaws(d, b.plants, b.ghosts)
                 if not flaws: break
                 at = [max([p for p in where if free[p]], default=-1) for _, where in flaws]
                 if min(at) < 0: break                         # a flaw no free literal touches: another draw
@@ -141,12 +141,16 @@ class Case:
                 for pos, M, D in sorted(b.plants + b.ghosts):
                     if D >= M: d[pos:pos + M] = d[pos - D:pos - D + M]
                     else: d[pos:pos + M] = np.resize(d[pos - D:pos], M)
-            if not _flaws(d, b.plants, b.ghosts): break
+            if not self.flaws(d, b.plants, b.ghosts): break
         else:
             raise AssertionError("%s: no valid draw" % self.name)
         out = (d.tobytes(), b.plants, b.ghosts)
         if len(out[0]) < (1 << 20): self._built = out
         return out
+
+    def flaws(self, d: np.ndarray, plants, ghosts) -> list:
+        """What build() mends and rejects a draw for: _flaws, here; a subclass may judge its cases by more (dict_encoder_cases.py)."""
+        return _flaws(d, plants, ghosts)
 
     @property
     def data(self) -> bytes:

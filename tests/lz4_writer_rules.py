@@ -23,8 +23,9 @@ Each violation is a string "rule: detail"; `rules(violations)` gives the set of 
            short-block-match   no match if blen < 13
            match-start    every match starts at or before blen - 12
            offset-range   every offset is in 1..65535 (only 0 can be written wrong: the field has 16 bits)
-           offset-reach   every offset is at most the match's position in the block plus, in a linked frame, min(bytes in front of
-                          the block, 65536)
+           offset-reach   every offset is at most the match's position in the block plus what lies in front of the block: the
+                          dictionary's dict_len bytes (the batch calls' shared dictionary; 0 without one), in a linked frame
+                          min(bytes in front of the block + dict_len, 65536)
 A match length below 4 cannot be written (the token holds length - 4), so there is no rule for it.
 """
 from __future__ import annotations
@@ -45,9 +46,11 @@ def rules(violations) -> set:
     return {v.split(":", 1)[0] for v in violations}
 
 
-def audit(frame: bytes, data: bytes, want: dict | None = None, parsed: Parsed | None = None) -> list[str]:
+def audit(frame: bytes, data: bytes, want: dict | None = None, parsed: Parsed | None = None, dict_len: int = 0) -> list[str]:
     """The writer rules `frame` breaks as a frame of `data`; [] for a frame a strict decoder accepts.  `want`: the preferences the
-    header must name - dict(bsid, linked, bck, cck), any subset.  `parsed`: Parsed(frame), if the caller has it."""
+    header must name - dict(bsid, linked, bck, cck), any subset.  `parsed`: Parsed(frame), if the caller has it.  `dict_len`: the
+    bytes of the dictionary the frame was written with that count (at most 65536): they lie in front of every block of an
+    independent frame and in front of a linked frame's first byte."""
     bad = []
     if len(frame) < 7 or struct.unpack_from("<I", frame, 0)[0] != 0x184D2204: return ["header: no LZ4 frame magic"]
     flg, bd = frame[4], frame[5]
@@ -88,7 +91,7 @@ def audit(frame: bytes, data: bytes, want: dict | None = None, parsed: Parsed | 
             bad.append("match-start: block %d of %d bytes: sequence %d's match starts at blen - %d" % (b, blen, k, blen - int(start[k])))
         if np.any(M[:, 4] < 1) or np.any(M[:, 4] > 65535):
             bad.append("offset-range: block %d: offset %d" % (b, int(M[np.argmax((M[:, 4] < 1) | (M[:, 4] > 65535)), 4])))
-        reach = start + (min(B["out_off"], 65536) if P.linked else 0)
+        reach = start + (min(B["out_off"] + dict_len, 65536) if P.linked else dict_len)
         if np.any(M[:, 4] > reach):
             k = int(np.argmax(M[:, 4] > reach))
             bad.append("offset-reach: block %d: sequence %d at %d has offset %d, reach %d" % (b, k, int(start[k]), int(M[k, 4]), int(reach[k])))

@@ -78,8 +78,10 @@ def edge_dictionary(n: int) -> bytes:
 
 
 def edge_record(n: int, d: bytes) -> bytes:
-    """The dictionary's last bytes (a match that ends at the seam), its first ones (the farthest position there is), then 200 bytes
-    stitched from the dictionary itself."""
+    """The dictionary's last bytes (a match that ends at the seam), its first ones, then 200 bytes stitched from the dictionary
+    itself.  The first ones stand at position 40, n + 40 bytes behind their source: the farthest position there is while
+    n + 40 <= 65535 - from n = 65496 on (the 65535- and 65536-byte dictionaries) they are out of reach and no match at all.  The
+    reach edge itself (a source exactly 65535 back, and 65536) is test_gpu_dict_encoder_edges.py's."""
     k = min(40, n)
     return d[-k:] + d[:k] + dc.stitched("hcedge/%d" % n, 200, d)
 
