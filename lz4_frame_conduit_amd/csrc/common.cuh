@@ -34,6 +34,13 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v)
 // z = dst, w = match_len (0: last sequence).  Positions and lengths are < 2^23 because a block holds at most 4 MiB.
 struct SeqDesc { uint32_t x, y, z, w; };
 
+// a batch call's shared dictionary as the kernels take it, decoders and encoders alike: the len (<= 64 KiB) bytes that end at `end`
+// (len 0: none).  The encoders' EncDict (encode.cuh) is this and the digests
+struct DictTail {
+    const uint8_t* end = nullptr;
+    uint32_t len = 0;
+};
+
 // (XXH32's constants and rotl32: frame_format.hpp)
 
 // ---- wave-cooperative copies (all arguments wave-uniform) --------------------------------------

@@ -21,10 +21,11 @@
 //
 // THE SHARED DICTIONARY (lz4f_mi355x_dev_decompressFrames_usingDict).  One dictionary for the whole batch: the history in front of a
 // frame's output (linked blocks), or in front of every block (independent blocks), is the dictionary's last <= 64 KiB, as
-// LZ4F_decompress_usingDict has it.  The kernels that decode blocks exist a second time, k_bf_*_dict: the same bodies with DICT set,
-// every block through the scalar-parse decoder (wave_decode_block_lim<true, true>: the offset check and the two-part match copy are
-// there, decode.cuh) - independent blocks too, which the plain call gives to wave_decode_block_win.  The plain call's kernels are
-// the DICT = false instantiations: what they were.
+// LZ4F_decompress_usingDict has it.  The three kernels that decode blocks are templates, k_bf_blocks / k_bf_serial / k_bf_finish
+// <W, DICT>, and take the dictionary by value (DictTail, common.cuh: the type the batch encoder's EncDict begins with).  With DICT set
+// (these instantiations were k_bf_blocks_dict, k_bf_serial_dict, k_bf_finish_dict) every block goes through the scalar-parse decoder
+// (wave_decode_block_lim<true, true>: the offset check and the two-part match copy are there, decode.cuh) - independent blocks too,
+// which the plain call gives to wave_decode_block_win.  The plain call launches the DICT = false instantiations, which ignore `dc`.
 #pragma once
 #include "common.cuh"
 #include "decode.cuh"
@@ -44,14 +45,10 @@ struct BatchBlk {                           // block table entry (40 bytes)
 };
 
 // wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
-// decodes but not into wlim
-struct BfDict {                              // the batch's dictionary: the len (<= 64 KiB) bytes that end at `end`
-    const uint8_t* end;
-    uint32_t len;
-};
-template <bool DICT = false>
+// decodes but not into wlim.  DICT: dc, the batch's dictionary (DictTail, common.cuh), lies in front of the history
+template <bool DICT>
 __device__ __forceinline__ int32_t bf_decode_block(const uint8_t* __restrict__ in, uint32_t csize, uint8_t* out, uint32_t cap, uint32_t wlim,
-                                                   uint64_t hist, const BfDict& dc = BfDict{nullptr, 0u})
+                                                   uint64_t hist, const DictTail& dc)
 {
     if constexpr (DICT) return wave_decode_block_lim<true, true>(in, csize, out, cap, wlim, hist, (const uint8_t*)uni64((uint64_t)dc.end), uni(dc.len));
     else return wave_decode_block_lim<true>(in, csize, out, cap, wlim, hist);
@@ -74,9 +71,9 @@ __device__ __forceinline__ void bf_move_down(uint8_t* dst, const uint8_t* src, u
 }
 
 // the tight last block (k_redo_tight_block): judged against a whole block, written only if it fits.  -> size, -2 or -3
-template <bool DICT = false>
+template <bool DICT>
 __device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz, uint8_t* out, uint32_t bs, uint32_t room, uint64_t hist,
-                                                 const BfDict& dc = BfDict{nullptr, 0u})
+                                                 const DictTail& dc)
 {
     const int32_t g = bf_decode_block<DICT>(in, csz, out, bs, room, hist, dc);
     return g == -1 ? -3 : g;
@@ -128,7 +125,7 @@ __global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ sr
 template <int W, bool DICT>
 __device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
                                                uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl,
-                                               uint32_t (*expand)[64], const BfDict& dc)
+                                               uint32_t (*expand)[64], const DictTail& dc)
 {
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t total = uni(ctl[0]);
@@ -158,24 +155,21 @@ __device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, 
         if (lane_id() == 0) { table[w].got = got; table[w].ck = ck; }
     }
 }
-template <int W>
+template <int W, bool DICT>
 __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
-                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl)
+                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl, DictTail dc)
 {
-    __shared__ uint32_t expand[W][64];
-    bf_blocks_body<W, false>(src, dst, frames, n_frames, table, ctl, expand, BfDict{nullptr, 0u});
-}
-template <int W>
-__global__ __launch_bounds__(64 * W, 8) void k_bf_blocks_dict(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
-                                                             uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl, BfDict dc)
-{
-    bf_blocks_body<W, true>(src, dst, frames, n_frames, table, ctl, nullptr, dc);
+    if constexpr (DICT) bf_blocks_body<W, true>(src, dst, frames, n_frames, table, ctl, nullptr, dc);
+    else {
+        __shared__ uint32_t expand[W][64];                             // (wave_decode_block_win's: with DICT the kernel has no LDS)
+        bf_blocks_body<W, false>(src, dst, frames, n_frames, table, ctl, expand, dc);
+    }
 }
 
 // a wave per frame without a table slice: blocks in order
 template <int W, bool DICT>
 __device__ __forceinline__ void bf_serial_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                               const BfDict& dc)
+                                               const DictTail& dc)
 {
     const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
     if (i >= n_frames) return;
@@ -216,22 +210,17 @@ __device__ __forceinline__ void bf_serial_body(const uint8_t* __restrict__ src, 
         }
     }
 }
-template <int W>
-__global__ __launch_bounds__(64 * W, 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames)
+template <int W, bool DICT>       // (DICT: held to 8 waves a SIMD, as the plain form is, the two-part copy spills to scratch: 6 it is)
+__global__ __launch_bounds__(64 * W, DICT ? 4 : 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames,
+                                                                   uint32_t n_frames, DictTail dc)
 {
-    bf_serial_body<W, false>(src, dst, frames, n_frames, BfDict{nullptr, 0u});
-}
-template <int W>       // (held to 8 waves a SIMD, as k_bf_serial is, the two-part copy spills to scratch: 6 it is)
-__global__ __launch_bounds__(64 * W, 4) void k_bf_serial_dict(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                                             BfDict dc)
-{
-    bf_serial_body<W, true>(src, dst, frames, n_frames, dc);
+    bf_serial_body<W, DICT>(src, dst, frames, n_frames, dc);
 }
 
 template <int W, bool DICT>
 __device__ __forceinline__ void bf_finish_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
                                                const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
-                                               uint32_t (*park)[XXH_PARK / 4], const BfDict& dc)
+                                               uint32_t (*park)[XXH_PARK / 4], const DictTail& dc)
 {
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t i = uni(blockIdx.x * W + wv);
@@ -293,20 +282,13 @@ __device__ __forceinline__ void bf_finish_body(const uint8_t* __restrict__ src, 
         results[i] = x;
     }
 }
-template <int W>
+template <int W, bool DICT>
 __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                                      const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check)
+                                                      const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
+                                                      DictTail dc)
 {
     __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
-    bf_finish_body<W, false>(src, dst, frames, n_frames, table, results, content_check, park, BfDict{nullptr, 0u});
-}
-template <int W>
-__global__ __launch_bounds__(64 * W) void k_bf_finish_dict(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                                           const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
-                                                           BfDict dc)
-{
-    __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
-    bf_finish_body<W, true>(src, dst, frames, n_frames, table, results, content_check, park, dc);
+    bf_finish_body<W, DICT>(src, dst, frames, n_frames, table, results, content_check, park, dc);
 }
 
 }  // namespace lz4f

@@ -67,6 +67,14 @@ struct EncPlace {
     uint64_t low_abs;            // matches may not start before this: the block's start, or the input's when linked
     uint64_t rd_end;             // nothing is read at or beyond this
 };
+// The batch encoder's shared dictionary, as the deterministic match finders take it: its tail (`end`, `len`: what lies in front of
+// every scope's low_abs) and, from a prepared dictionary, the finders' state once the tail is in - solo_digest (k_solo_digest_dict,
+// encode_solo.cuh) and hc_digest (k_hc_digest_dict, encode_hc.cuh).  nullptr: none - the solo finder then seeds from the bytes, and
+// levels 3-12 get a dictionary only with its digest (engine.hip).  EncDict{}: no dictionary
+struct EncDict : DictTail {
+    const uint4* solo_digest = nullptr;
+    const uint4* hc_digest = nullptr;
+};
 // false: the chunk lies beyond a short last block
 __device__ __forceinline__ bool enc_place(const EncGeom& g, uint32_t chunk, EncPlace& pl)
 {

@@ -17,9 +17,10 @@
 //   k_bc_find_*    the deterministic match finders over the chunk table: solo_find_chunk (encode_solo.cuh, a wave per chunk, levels
 //                  <= 2) or hc_find_chunk (encode_hc.cuh, a workgroup per chunk, levels 3-12) - the very functions the single call's
 //                  kernels run, so a frame's records are what they would be alone
-//                  (k_bc_find_solo_dict: the same finder with the call's shared dictionary in front of every low_abs;
-//                  k_bc_find_solo_cdict: with a prepared dictionary, whose digested table a scope's first chunk copies;
-//                  k_bc_find_hc_cdict: levels 3-12 with a prepared dictionary that carries the hash-chain digest)
+//                  Two kernels of one signature, k_bc_find_solo<DICT, CDICT> and k_bc_find_hc<DICT>; the call's dictionary reaches
+//                  them as one EncDict (encode.cuh).  k_bc_find_solo<true, false>: the call's shared dictionary in front of every
+//                  low_abs; <true, true>: a prepared dictionary, whose digested table a scope's first chunk copies;
+//                  k_bc_find_hc<true>: levels 3-12 with a prepared dictionary that carries the hash-chain digest
 //   k_bc_layout    a wave per block: layout_block_chunks (pass S's per-block step: carries, raw fallback) -> the size word
 //   k_bc_frames    a wave per frame: the blocks placed behind the header, the window judged, then header (made here: content size and
 //                  HC byte are the frame's own), size words, EndMark, every chunk's place in the destination, the result record
@@ -163,66 +164,55 @@ __device__ __forceinline__ EncPlace bc_place_of(const BcChunk& e)
     return pl;
 }
 
-// the deterministic finder of levels <= 2 over the chunk table: a wave per chunk (a one-wave workgroup, as the single call launches it:
-// 11.25 KiB of LDS per wave bound the occupancy)
+// The deterministic finder of levels <= 2 over the chunk table: a wave per chunk (a one-wave workgroup, as the single call launches it:
+// 11.25 KiB of LDS per wave bound the occupancy).  Its three instantiations (the two finder kernels share one signature, so that the
+// host picks one and launches it: `pf` is k_bc_find_hc's, `dc` is for DICT):
+//   <false, false>  no dictionary (lz4f_mi355x_dev_compressFrames)
+//   <true, false>   the batch's shared dictionary (lz4f_mi355x_dev_compressFrames_usingDict; it was k_bc_find_solo_dict): the dc.len
+//                   (<= 64 KiB) bytes that end at dc.end lie in front of every chunk's low_abs (solo_find_chunk<true>).  The dictionary
+//                   is the call's, not a chunk's: the chunk table and the workspace are what they are without it
+//   <true, true>    a prepared dictionary (lz4f_mi355x_dev_compressFrames_usingCDict; it was k_bc_find_solo_cdict): dc.solo_digest is
+//                   the seeded table of a chunk that has the dictionary alone in front of it (k_solo_digest_dict), and such a chunk -
+//                   cs_abs == low_abs: every frame's first chunk, and every independent block's - copies it into LDS, 11.25 KiB, where
+//                   <true, false> reads up to 64 KiB of dictionary and inserts some 17 000 seeds.  (Chunks are 64 KiB, so a chunk
+//                   behind the first of its scope has 64 KiB of input in front and no dictionary: it seeds as ever.  The finder asks
+//                   cs_abs == low_abs itself and does not lean on that.)  Table and tags are one array here, in the digest's layout;
+//                   the same 11 520 bytes of LDS.  (The other two keep their two arrays: the one-array form costs the plain kernel
+//                   two VGPRs and an SGPR)
+template <bool DICT, bool CDICT>
 __global__ __launch_bounds__(64) void k_bc_find_solo(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
                                                      const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                     ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool)
+                                                     ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, EncDict dc)
 {
-    __shared__ uint16_t s_table[SOLO_HASH_SIZE];
-    __shared__ uint8_t s_tag[SOLO_HASH_SIZE];
-    const uint32_t total = uni(ctl[0]);
-    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const BcChunk e = chunks[w];
-        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
-        const EncPlace pl = bc_place_of(e);
-        solo_find_chunk(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), s_table, s_tag);
+    static_assert(DICT || !CDICT, "a digest is a dictionary's");
+    uint16_t* table; uint8_t* tags;
+    if constexpr (CDICT) {
+        __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
+        table = solo_digest_table(s_dig); tags = solo_digest_tags(s_dig);
+    } else {
+        __shared__ uint16_t s_table[SOLO_HASH_SIZE];
+        __shared__ uint8_t s_tag[SOLO_HASH_SIZE];
+        table = s_table; tags = s_tag;
     }
-}
-// the same with the batch's shared dictionary (lz4f_mi355x_dev_compressFrames_usingDict): the dict_len (<= 64 KiB) bytes that end at
-// dict_end lie in front of every chunk's low_abs (solo_find_chunk<true>).  The dictionary is the call's, not a chunk's: the chunk table
-// and the workspace are what they are without it
-__global__ __launch_bounds__(64) void k_bc_find_solo_dict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
-                                                          const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                          ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool,
-                                                          const uint8_t* __restrict__ dict_end, uint32_t dict_len)
-{
-    __shared__ uint16_t s_table[SOLO_HASH_SIZE];
-    __shared__ uint8_t s_tag[SOLO_HASH_SIZE];
     const uint32_t total = uni(ctl[0]);
     for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
         const BcChunk e = chunks[w];
         if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
         const EncPlace pl = bc_place_of(e);
-        solo_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), s_table, s_tag, dict_end, dict_len);
-    }
-}
-// the same with a prepared dictionary (lz4f_mi355x_dev_compressFrames_usingCDict): `digest` is the seeded table of a chunk that has
-// the dictionary alone in front of it (k_solo_digest_dict), and such a chunk - cs_abs == low_abs: every frame's first chunk, and every
-// independent block's - copies it into LDS, 11.25 KiB, where k_bc_find_solo_dict reads up to 64 KiB of dictionary and inserts some
-// 17 000 seeds.  (Chunks are 64 KiB, so a chunk behind the first of its scope has 64 KiB of input in front and no dictionary: it
-// seeds as ever.  The finder asks cs_abs == low_abs itself and does not lean on that.)  Table and tags are one array here, in the
-// digest's layout; the same 11 520 bytes of LDS
-__global__ __launch_bounds__(64) void k_bc_find_solo_cdict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
-                                                           const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                           ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool,
-                                                           const uint8_t* __restrict__ dict_end, uint32_t dict_len, const uint4* __restrict__ digest)
-{
-    __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
-    const uint32_t total = uni(ctl[0]);
-    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const BcChunk e = chunks[w];
-        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
-        const EncPlace pl = bc_place_of(e);
-        solo_find_chunk<true, true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), solo_digest_table(s_dig), solo_digest_tags(s_dig),
-                                    dict_end, dict_len, digest);
+        solo_find_chunk<DICT, CDICT>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), table, tags, dc);
     }
 }
 
-// levels 3-12: a workgroup per chunk
+// Levels 3-12: a workgroup per chunk.  DICT (it was k_bc_find_hc_cdict): a prepared dictionary that carries the hash-chain digest
+// (lz4f_mi355x_dev_createCDictHC).  A chunk with the dictionary alone in front of it - cs_abs == low_abs: every frame's first chunk, and
+// every independent block's - loads dc.hc_digest (head and chain[0 .. D), k_hc_digest_dict) into the workgroup's LDS where the plain
+// kernel clears head, and walks on from the batch that holds the seam.  All of it is loaded again for every such chunk, so nothing
+// depends on the chunks this workgroup had before; every other chunk has 64 KiB of input in front of it and runs as without DICT.  The
+// same HcShared: the digest needs no LDS of its own
+template <bool DICT>
 __global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
                                                               const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                              ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf)
+                                                              ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, EncDict dc)
 {
     __shared__ HcShared sh;
     const uint32_t total = uni(ctl[0]);
@@ -230,31 +220,12 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc(const uint8_t* __r
         const BcChunk e = chunks[w];
         if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
         const EncPlace pl = bc_place_of(e);
-        hc_find_chunk(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh);
+        hc_find_chunk<DICT>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dc);
         __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
     }
 }
-
-// the same with a prepared dictionary that carries the hash-chain digest (lz4f_mi355x_dev_createCDictHC): a chunk with the dictionary
-// alone in front of it - cs_abs == low_abs: every frame's first chunk, and every independent block's - loads `digest` (head and
-// chain[0 .. D), k_hc_digest_dict) into the workgroup's LDS where k_bc_find_hc clears head, and walks on from the batch that holds
-// the seam.  All of it is loaded again for every such chunk, so nothing depends on the chunks this workgroup had before; every other
-// chunk has 64 KiB of input in front of it and runs as in k_bc_find_hc.  The same HcShared: the digest needs no LDS of its own
-__global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc_cdict(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
-                                                                    const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                                    ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf,
-                                                                    const uint8_t* __restrict__ dict_end, uint32_t dict_len, const uint4* __restrict__ digest)
-{
-    __shared__ HcShared sh;
-    const uint32_t total = uni(ctl[0]);
-    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const BcChunk e = chunks[w];
-        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
-        const EncPlace pl = bc_place_of(e);
-        hc_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dict_end, dict_len, digest);
-        __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
-    }
-}
+// what the two have in common, for the host
+using BcFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, EncDict);
 
 // a wave per block: pass S's per-block step
 template <int W>

@@ -21,8 +21,8 @@
 // another writes in the same iteration, so the records are a function of the input, its history and the level alone: nothing depends
 // on timing or on the pool.
 //
-// DICT (the batch encoder's prepared dictionary at these levels, encode_batch.cuh): the virtual history, the seam and the seam policy of
-// encode_solo.cuh.  In front of a scope's first chunk (cs_abs == low_abs) lies the dictionary's tail: seam == back == min(64 KiB,
+// DICT (the batch encoder's prepared dictionary at these levels, encode_batch.cuh; it comes as one EncDict, encode.cuh, whose hc_digest
+// is this finder's): the virtual history, the seam and the seam policy of encode_solo.cuh.  In front of a scope's first chunk (cs_abs == low_abs) lies the dictionary's tail: seam == back == min(64 KiB,
 // dict_len), positions below `seam` address the dictionary.  Such a chunk loads head and chain[0 .. seam) from the dictionary's
 // digest - their state once the dictionary's positions are in, made by this very build loop (DIGEST, k_hc_digest_dict) - and walks on
 // from the batch that holds the seam.  A match is CUT at the seam: a candidate in the dictionary extends forwards to the dictionary's
@@ -97,14 +97,13 @@ __device__ __forceinline__ void hc_digest_load(HcShared& sh, const uint4* __rest
 // k_find_matches_hc from the call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `rec`: the chunk's record
 // list (max_rec records of room; !rec_room: none, the chunk goes out as literals).  Every path ends behind a barrier or before the
 // first use of `sh`, so a workgroup may call this for one chunk after another.
-// DICT: the dict_len (<= 64 KiB) bytes that end at dict_end lie in front of a scope's first chunk, and `digest` holds head and chain as
+// DICT: the dc.len (<= 64 KiB) bytes that end at dc.end lie in front of a scope's first chunk, and dc.hc_digest holds head and chain as
 // the dictionary leaves them (see above).  DIGEST (with DICT): clear, build the dictionary's positions, nothing else - how
 // k_hc_digest_dict makes the digest, by the very code and in the very insertion order of the finders.
 template <bool DICT = false, bool DIGEST = false>
 __device__ __forceinline__ void hc_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
                                               uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
-                                              const uint32_t hc_attempts, const uint32_t lazy, HcShared& sh,
-                                              const uint8_t* dict_end = nullptr, uint32_t dict_len = 0, const uint4* __restrict__ digest = nullptr)
+                                              const uint32_t hc_attempts, const uint32_t lazy, HcShared& sh, const EncDict& dc)
 {
     static_assert(DICT || !DIGEST, "a digest is a dictionary's");
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
@@ -112,15 +111,15 @@ __device__ __forceinline__ void hc_find_chunk(const uint8_t* __restrict__ src, c
     uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
     uint32_t seam = 0;                                               // DICT: positions below it are the dictionary's
     if constexpr (DICT) {
-        if (dict_len >= 4 && cs_abs == low_abs) { seam = dict_len < 65536u ? dict_len : 65536u; back = seam; }
+        if (dc.len >= 4 && cs_abs == low_abs) { seam = dc.len < 65536u ? dc.len : 65536u; back = seam; }
     }
     const uint8_t* base = src + (cs_abs - back);                     // position 0 of the window (DICT: positions from seam on)
-    const uint8_t* dbase = DICT ? dict_end - seam : nullptr;         // DICT: position 0, for positions below seam
+    const uint8_t* dbase = DICT ? dc.end - seam : nullptr;           // DICT: position 0, for positions below seam
     const uint8_t* rd_end = src + pl.rd_end;                         // nothing is read at or beyond this
     auto at_pos = [&](uint32_t x) -> const uint8_t* { return DICT && x < seam ? dbase + x : base + x; };
     // 8 bytes of a match's source at position sp; in the dictionary: nothing at or beyond the seam (zeros instead)
     auto src8 = [&](uint32_t sp, bool in_dict) -> uint64_t {
-        if (DICT && in_dict) return sp < seam ? ld64_guard(dbase + sp, dict_end) : 0ull;
+        if (DICT && in_dict) return sp < seam ? ld64_guard(dbase + sp, dc.end) : 0ull;
         return ld64_guard(base + sp, rd_end);
     };
     const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
@@ -151,7 +150,7 @@ __device__ __forceinline__ void hc_find_chunk(const uint8_t* __restrict__ src, c
     if constexpr (DIGEST) {
         for (uint32_t k = tid; k < HC_RING / 2; k += 64 * HC_WAVES) ((uint32_t*)sh.chain)[k] = 0;
     } else if constexpr (DICT) {
-        if (seam) { hc_digest_load(sh, digest, seam); it0 = seam / HC_T; ins_from = seam; cleared = true; }
+        if (seam) { hc_digest_load(sh, dc.hc_digest, seam); it0 = seam / HC_T; ins_from = seam; cleared = true; }
     }
     if (!cleared)
         for (uint32_t k = tid; k < (1u << HC_HASH_LOG) / 2; k += 64 * HC_WAVES) ((uint32_t*)sh.head)[k] = 0;
@@ -279,14 +278,14 @@ __device__ __forceinline__ void hc_find_chunk(const uint8_t* __restrict__ src, c
                     if (d == 0 || d > q - qmin) break;
                     q -= d;
                     // DICT, a candidate in the dictionary: its match ends at the seam at the latest, so every load below lies in
-                    // [dbase + q, dict_end) - and one that cannot beat `best` (or has no 4 bytes in front of the seam) is passed over
+                    // [dbase + q, dc.end) - and one that cannot beat `best` (or has no 4 bytes in front of the seam) is passed over
                     uint32_t cmax = maxlen;
                     const bool cd = DICT && q < seam;
                     if constexpr (DICT) {
                         if (cd) { if (seam - q < cmax) cmax = seam - q; if (cmax < MINMATCH || cmax <= best) continue; }
                     }
                     const uint8_t* qp = cd ? dbase + q : base + q;
-                    const uint8_t* q_end = cd ? dict_end : rd_end;
+                    const uint8_t* q_end = cd ? dc.end : rd_end;
                     if (ld32(qp) != cur) continue;
                     if (best >= MINMATCH && ld32(qp + best - 3) != tail) continue;
                     uint32_t len = MINMATCH;
@@ -331,7 +330,8 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_hc_digest_dict(const uint8_t*
     EncPlace pl;
     pl.bstart = 0; pl.bend_abs = 0; pl.cs_abs = 0; pl.ce_abs = 0; pl.low_abs = 0; pl.rd_end = 0;
     const uint32_t D = dict_len < 65536u ? dict_len : 65536u;
-    hc_find_chunk<true, true>(dict_end, pl, nullptr, nullptr, false, 0u, 0u, 0u, sh, dict_end, D);    // (ends behind a barrier)
+    const EncDict dc{DictTail{dict_end, D}};
+    hc_find_chunk<true, true>(dict_end, pl, nullptr, nullptr, false, 0u, 0u, 0u, sh, dc);    // (ends behind a barrier)
     digest[threadIdx.x] = ((const uint4*)sh.head)[threadIdx.x];
     for (uint32_t i = threadIdx.x; i < hc_digest_chain_vec(D); i += 64 * HC_WAVES) digest[HC_DIGEST_HEAD_VEC + i] = ((const uint4*)sh.chain)[i];
 }
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_find_matches_hc(const uint8_t
     const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
     uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
     if (tid == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
-    hc_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, g.hc_attempts, g.hc_lazy, sh);
+    hc_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, g.hc_attempts, g.hc_lazy, sh, EncDict{});
 }
 
 }  // namespace lz4f

@@ -11,7 +11,8 @@
 // block's start) is seeded into the table sparsely, its last KiB densely, so matches reach back across chunk boundaries.
 // Same record and ChunkInfo format as pass E1 of encode.cuh: passes S and E2 do not know the difference.
 //
-// DICT (the batch encoder's shared dictionary, encode_batch.cuh): what lies in front of low_abs is the dictionary's tail, so the window in
+// DICT (the batch encoder's shared dictionary, encode_batch.cuh; it comes as one EncDict, encode.cuh: the tail, and a prepared
+// dictionary's digests): what lies in front of low_abs is the dictionary's tail, so the window in
 // front of a chunk is [dictionary tail | input from low_abs] and `back` the smaller of 64 KiB and (bytes from low_abs + the dictionary's).
 // Positions below `seam` address the dictionary.  It is seeded by the same scheme (a seed whose four bytes would straddle the seam is
 // left out).  The seam policy: a match is CUT at the seam - a candidate in the dictionary extends backwards within the dictionary and
@@ -68,16 +69,15 @@ __device__ __forceinline__ void solo_digest_store(uint4* __restrict__ digest, co
 // call's EncGeom, by the batch encoder from its chunk table (encode_batch.cuh).  `table` / `tags`: the wave's own, in LDS; `rec`: the
 // chunk's record list (max_rec records of room; !rec_room: none, the chunk goes out as literals).
 // CDICT (with DICT; lz4f_mi355x_dev_compressFrames_usingCDict): a chunk with the dictionary alone in front of it (cs_abs == low_abs)
-// has seam == back == min(64 KiB, dict_len), so its positions and with them the seeded table and tags are a function of the
-// dictionary alone: `digest` holds them, made once by k_solo_digest_dict, and such a chunk copies it instead of clearing and seeding
+// has seam == back == min(64 KiB, dc.len), so its positions and with them the seeded table and tags are a function of the
+// dictionary alone: dc.solo_digest holds them, made once by k_solo_digest_dict, and such a chunk copies it instead of clearing and seeding
 // (`table` and `tags` are then one 16-byte aligned array in the digest's layout).  Every other chunk seeds as without it.
 // SEED_ONLY: clear and seed, nothing else - how k_solo_digest_dict makes the digest, by the very code and in the very insertion
 // order ("later inserts win") of the finders.
 template <bool DICT = false, bool CDICT = false, bool SEED_ONLY = false>
 __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src, const EncPlace& pl, ChunkInfo* __restrict__ ci,
                                                 uint64_t* __restrict__ rec, const bool rec_room, const uint32_t max_rec,
-                                                uint16_t* table, uint8_t* tags, const uint8_t* dict_end = nullptr, uint32_t dict_len = 0,
-                                                const uint4* __restrict__ digest = nullptr)
+                                                uint16_t* table, uint8_t* tags, const EncDict& dc)
 {
     static_assert(DICT || !(CDICT || SEED_ONLY), "a digest is a dictionary's");
     const uint32_t lane = lane_id();
@@ -85,15 +85,15 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
     uint32_t back = (uint32_t)((cs_abs - low_abs < 65536u) ? (cs_abs - low_abs) : 65536u);
     uint32_t seam = 0;                                               // DICT: positions below it are the dictionary's
     if constexpr (DICT) {
-        if (dict_len >= 4 && back < 65536u) { seam = 65536u - back < dict_len ? 65536u - back : dict_len; back += seam; }
+        if (dc.len >= 4 && back < 65536u) { seam = 65536u - back < dc.len ? 65536u - back : dc.len; back += seam; }
     }
     const uint8_t* base = src + (cs_abs - back);                     // position 0 (DICT: positions from seam on)
-    const uint8_t* dbase = dict_end - seam;                          // DICT: position 0, for positions below seam
+    const uint8_t* dbase = dc.end - seam;                            // DICT: position 0, for positions below seam
     const uint8_t* rd_end = src + pl.rd_end;                         // nothing is read at or beyond this
     auto at_pos = [&](uint32_t p) -> const uint8_t* { return DICT && p < seam ? dbase + p : base + p; };
     // 8 bytes of a match's source at position sp; in the dictionary: nothing at or beyond the seam (zeros instead)
     auto src8 = [&](uint32_t sp, bool in_dict) -> uint64_t {
-        if (DICT && in_dict) return sp < seam ? ld64_guard(dbase + sp, dict_end) : 0ull;
+        if (DICT && in_dict) return sp < seam ? ld64_guard(dbase + sp, dc.end) : 0ull;
         return ld64_guard(base + sp, rd_end);
     };
     const uint32_t cs = back, ce = back + (uint32_t)(ce_abs - cs_abs);
@@ -104,7 +104,7 @@ __device__ __forceinline__ void solo_find_chunk(const uint8_t* __restrict__ src,
     // roughly the density the skip-accelerated search itself leaves behind), then the last SEED_DENSE bytes densely.
     bool seeded = false;
     if constexpr (CDICT) {
-        if (seam && cs_abs == low_abs) { solo_digest_load((uint4*)table, digest); seeded = true; }
+        if (seam && cs_abs == low_abs) { solo_digest_load((uint4*)table, dc.solo_digest); seeded = true; }
     }
     if (!seeded) {
         for (uint32_t i = lane; i < SOLO_HASH_SIZE / 2; i += WAVE) ((uint32_t*)table)[i] = 0;
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_find_matches_solo(const u
     const bool rec_room = rec_at + g.max_rec_per_chunk <= g.rec_pool;
     uint64_t* rec = rec_pool_of(recs, g) + (rec_room ? rec_at : 0);
     if (lane == 0) rec_offs(recs)[chunk] = (uint32_t)(rec_room ? rec_at : 0);
-    solo_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, s_table[wave], s_tag[wave]);
+    solo_find_chunk(src, pl, ci, rec, rec_room, g.max_rec_per_chunk, s_table[wave], s_tag[wave], EncDict{});
 }
 
 // The prepared dictionary's digest: one wave seeds its table from the dictionary's last dict_len (<= 64 KiB) bytes, which end at
@@ -393,8 +393,8 @@ __global__ __launch_bounds__(64) void k_solo_digest_dict(const uint8_t* __restri
     __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
     EncPlace pl;
     pl.bstart = 0; pl.bend_abs = 0; pl.cs_abs = 0; pl.ce_abs = 0; pl.low_abs = 0; pl.rd_end = 0;
-    solo_find_chunk<true, false, true>(dict_end, pl, nullptr, nullptr, false, 0u, solo_digest_table(s_dig), solo_digest_tags(s_dig), dict_end,
-                                       dict_len < 65536u ? dict_len : 65536u);
+    const EncDict dc{DictTail{dict_end, dict_len < 65536u ? dict_len : 65536u}};
+    solo_find_chunk<true, false, true>(dict_end, pl, nullptr, nullptr, false, 0u, solo_digest_table(s_dig), solo_digest_tags(s_dig), dc);
     solo_digest_store(digest, s_dig);
 }
 

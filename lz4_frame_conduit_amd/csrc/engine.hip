@@ -274,6 +274,14 @@ static uint64_t rec_pool_records(uint32_t n_chunks, uint32_t max_rec_per_chunk, 
     return want;
 }
 
+// levels 3-12: the chain candidates a search looks at and the lazy parse's depth - the level's (hc_level), unless a development switch
+// sets one
+static HcLevel hc_level_of(int level, const lz4f_mi355x_engine::Switches& sw)
+{
+    const HcLevel hl = hc_level(level);
+    return HcLevel{sw.hc_attempts ? sw.hc_attempts : hl.attempts, sw.hc_lazy ? sw.hc_lazy : hl.lazy};
+}
+
 struct lz4f_mi355x_engine::EncodePlan {
     bool too_large;                  // more chunks than a 32-bit count holds: the call is refused, nothing else here is filled in
     EncGeom g;                       // what every kernel of the call takes
@@ -305,11 +313,7 @@ lz4f_mi355x_engine::EncodePlan lz4f_mi355x_engine::encode_plan(const CompressJob
     // levels 3-12: the hash-chain finder, a workgroup per chunk (encode_hc.cuh) - deterministic too.
     const bool hc = j.level >= 3;
     p.finder = hc ? EncodePlan::HASH_CHAIN : ((sw.e1_solo & 1u) && !(sw.e1_solo & 4u)) ? EncodePlan::E1_SOLO : EncodePlan::E1_SHARED;
-    if (hc) {
-        const HcLevel hl = hc_level(j.level);
-        g.hc_attempts = sw.hc_attempts ? sw.hc_attempts : hl.attempts;
-        g.hc_lazy = sw.hc_lazy ? sw.hc_lazy : hl.lazy;
-    }
+    if (hc) { const HcLevel hl = hc_level_of(j.level, sw); g.hc_attempts = hl.attempts; g.hc_lazy = hl.lazy; }
     // (deterministic mode: the worst case for every tile - which tiles a short pool turns away is a matter of which workgroup's merge
     // gets to the bump pointer first, and "equal input, equal bytes" must not hang on that: 2 bytes of workspace per input byte)
     // (levels 3-12 likewise: their output is a function of the input alone, so a chunk's list has a place of its own, encode_hc.cuh)
@@ -1000,14 +1004,12 @@ struct Carve {
 
 // A prepared dictionary (lz4f_mi355x_dev_createCDict / _createCDictHC): its engine's, never written after the stream has run its creation.
 // One device allocation: the digest (SOLO_DIGEST_BYTES: the finder's table and tags, seeded), the hash-chain finder's digest where asked
-// for (lz4f_mi355x_dev_createCDictHC: hc_digest_bytes(size), head and chain), then `size` (<= 64 KiB) dictionary bytes
+// for (lz4f_mi355x_dev_createCDictHC: hc_digest_bytes(len), head and chain), then the dictionary's last `len` (<= 64 KiB) bytes
 struct lz4f_mi355x_cdict {
     lz4f_mi355x_engine* engine = nullptr;
-    uint4* digest = nullptr;               // the allocation; NULL: an empty dictionary
-    uint4* hc_digest = nullptr;            // NULL: none (made by createCDict, or an empty dictionary)
+    EncDict dict;                          // the owned copy's tail and its digests (hc_digest NULL: made by createCDict); len 0: an empty dictionary
     bool hc = false;                       // made by createCDictHC: serves levels 3-12 too
-    uint8_t* data = nullptr;
-    size_t size = 0;
+    void* mem = nullptr;                   // the allocation; NULL: an empty dictionary
 };
 
 extern "C" {
@@ -1098,16 +1100,24 @@ size_t lz4f_mi355x_trailer_bound(size_t srcSize, const LZ4F_preferences_t* prefs
     return lz4f_mi355x_dev_index_size(srcSize, prefs) + (sizing_shape(srcSize, prefs).n_blocks + 2) * 8 + 128;
 }
 
+// A compress call's preferences resolved: p, the caller's copy (NULL: all defaults) with 64 KiB blocks where it names no size, and bs,
+// its block size -> 0, or ERROR_maxBlockSize_invalid
+static size_t resolve_prefs(const LZ4F_preferences_t* prefs, LZ4F_preferences_t& p, size_t& bs)
+{
+    memset(&p, 0, sizeof(p));
+    if (prefs) p = *prefs;
+    if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
+    bs = block_size_of(p.frameInfo.blockSizeID);
+    return bs ? 0 : make_err(LZ4F_ERROR_maxBlockSize_invalid);
+}
+
 // the preferences resolved and checked, then the whole-frame job (index_cap: LZ4F_MI355X_INBAND, a given index's capacity, or 0 for none)
 static size_t compress_frame(lz4f_mi355x_engine* e, void* d_dst, size_t dstCapacity, const void* d_src, size_t srcSize, const LZ4F_preferences_t* prefs,
                              lz4f_mi355x_result* d_result, lz4f_mi355x_block* d_table, void* d_index, size_t index_cap)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
-    if (prefs) p = *prefs;
-    if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
-    const size_t bs = block_size_of(p.frameInfo.blockSizeID);
-    if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
+    LZ4F_preferences_t p; size_t bs;
+    if (const size_t r = resolve_prefs(prefs, p, bs)) return r;
     if (p.frameInfo.contentSize && p.frameInfo.contentSize != srcSize) return make_err(LZ4F_ERROR_frameSize_wrong);
     const auto j = lz4f_mi355x_engine::make_compress_job((const uint8_t*)d_src, srcSize, 0, (uint32_t)bs, p.frameInfo.blockMode == LZ4F_blockLinked,
                                                          p.frameInfo.blockChecksumFlag != 0, p.compressionLevel, &p);
@@ -1192,11 +1202,14 @@ size_t lz4f_mi355x_dev_decompressBlocks(lz4f_mi355x_engine* e, void* d_dst, size
     return lz4f_mi355x_dev_decompressBlocksIndexed(e, d_dst, dstCapacity, d_frame, frameCapacity, d_table, n_blocks, info, nullptr, 0, d_result);
 }
 
-// the batch's dictionary as the kernels take it: the last 64 KiB at most (dictSize 0: none)
-static void batch_dict_tail(const void* d_dict, size_t dictSize, const uint8_t*& end, uint32_t& len)
+// the batch's dictionary as the kernels take it: the last 64 KiB at most (dictSize 0: none; bytes without a pointer: a length without
+// an end, which batch_begin's callers refuse as a null pointer)
+static DictTail batch_dict_tail(const void* d_dict, size_t dictSize)
 {
-    len = (uint32_t)std::min<size_t>(dictSize, 65536);
-    end = len ? (const uint8_t*)d_dict + dictSize : nullptr;
+    DictTail t;
+    t.len = (uint32_t)std::min<size_t>(dictSize, 65536);
+    t.end = t.len && d_dict ? (const uint8_t*)d_dict + dictSize : nullptr;
+    return t;
 }
 
 static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
@@ -1205,9 +1218,8 @@ static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const 
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (d_dict || !dictSize))) return r;
-    BfDict dc;
-    batch_dict_tail(d_dict, dictSize, dc.end, dc.len);
+    const DictTail dc = batch_dict_tail(d_dict, dictSize);
+    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len))) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // the block table: a frame of full blocks never needs more than window / 64 KiB + 1 entries, so this bound needs nothing read back
     const uint64_t table_cap = batch_table_cap(n_frames, dstBytes / BF_SHARE);
@@ -1224,17 +1236,13 @@ static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const 
     hipLaunchKernelGGL(k_bf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts);
     hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
     hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
-    if (dc.len) {                                                      // (the dictionary's instantiations: every block through the scalar-parse decoder)
-        hipLaunchKernelGGL((k_bf_blocks_dict<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table, (const uint32_t*)ctl, dc);
-        hipLaunchKernelGGL((k_bf_serial_dict<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, dc);
-        hipLaunchKernelGGL((k_bf_finish_dict<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
-                           e->sw.no_content_check ? 0u : 1u, dc);
-        return batch_end("dev_decompressFrames");
-    }
-    hipLaunchKernelGGL((k_bf_blocks<W>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table, (const uint32_t*)ctl);
-    hipLaunchKernelGGL((k_bf_serial<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames);
-    hipLaunchKernelGGL((k_bf_finish<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
-                       e->sw.no_content_check ? 0u : 1u);
+    // (a dictionary: the DICT instantiations, every block through the scalar-parse decoder)
+    const bool dict = dc.len != 0;
+    hipLaunchKernelGGL((dict ? k_bf_blocks<W, true> : k_bf_blocks<W, false>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames,
+                       n_frames, table, (const uint32_t*)ctl, dc);
+    hipLaunchKernelGGL((dict ? k_bf_serial<W, true> : k_bf_serial<W, false>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, dc);
+    hipLaunchKernelGGL((dict ? k_bf_finish<W, true> : k_bf_finish<W, false>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table,
+                       (ResultRec*)d_results, e->sw.no_content_check ? 0u : 1u, dc);
     return batch_end("dev_decompressFrames");
 }
 
@@ -1313,30 +1321,32 @@ size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frame
     return batch_end("dev_readPackDirectory");
 }
 
-// `digest` (a prepared dictionary's, made by k_solo_digest_dict from these very dictSize bytes; NULL: none): the finder copies it where
-// it would seed from the dictionary alone.  `hc_dict`: the dictionary is a prepared one made for levels 3-12 too, and `hc_digest` its
-// hash-chain digest (k_hc_digest_dict; NULL: fewer than 4 bytes, which the finder ignores)
+// The finder kernel of a batch (encode_batch.cuh) and the most workgroups it gets: by the level, and by what the dictionary brings
+struct BcFind { BcFinder kernel; uint32_t most_wgs, threads; };
+static BcFind bc_finder(bool hc, const EncDict& dc)
+{
+    // (levels 3-12 without the digest: no dictionary, or a prepared one of 1-3 bytes, which the finder ignores)
+    if (hc) return BcFind{dc.len && dc.hc_digest ? k_bc_find_hc<true> : k_bc_find_hc<false>, BATCH_GRID / 4, 64 * HC_WAVES};
+    return BcFind{!dc.len ? k_bc_find_solo<false, false> : dc.solo_digest ? k_bc_find_solo<true, true> : k_bc_find_solo<true, false>, BATCH_GRID * 2, 64};
+}
+
+// `dc`: the call's dictionary (EncDict{}: none) - a raw one's tail, or a prepared one's with its digests.  `dict_hc`: it is a prepared
+// one made for levels 3-12 (which may still come without dc.hc_digest: fewer than 4 bytes, which the finder ignores)
 static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                               void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                              lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize, const uint4* digest = nullptr,
-                              bool hc_dict = false, const uint4* hc_digest = nullptr)
+                              lz4f_mi355x_result* d_results, const EncDict& dc, bool dict_hc)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    LZ4F_preferences_t p; memset(&p, 0, sizeof(p));
-    if (prefs) p = *prefs;
-    if (p.frameInfo.blockSizeID == 0) p.frameInfo.blockSizeID = LZ4F_max64KB;
-    const size_t bs = block_size_of(p.frameInfo.blockSizeID);
-    if (!bs) return make_err(LZ4F_ERROR_maxBlockSize_invalid);
+    LZ4F_preferences_t p; size_t bs;
+    if (const size_t r = resolve_prefs(prefs, p, bs)) return r;
     // (levels 3-12 take a dictionary only with the hash-chain digest: seeding a raw one costs up to 69 barrier rounds in front of
     // every chunk.  Nothing is enqueued)
-    if (dictSize && p.compressionLevel >= 3 && !hc_dict) {
+    if (dc.len && p.compressionLevel >= 3 && !dict_hc) {
         set_last_error("dev_compressFrames_usingDict: levels 3-12 take a dictionary only as a CDict of dev_createCDictHC");
         return make_err(LZ4F_ERROR_compressionLevel_invalid);
     }
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (d_dict || !dictSize))) return r;
-    const uint8_t* dict_end; uint32_t dict_len;
-    batch_dict_tail(d_dict, dictSize, dict_end, dict_len);
+    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len))) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
@@ -1344,11 +1354,7 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     pf.block_size = (uint32_t)bs; pf.bsid = (uint32_t)f.blockSizeID; pf.linked = f.blockMode == LZ4F_blockLinked; pf.block_checksum = f.blockChecksumFlag != 0;
     pf.content_checksum = f.contentChecksumFlag != 0; pf.content_size = f.contentSize != 0; pf.dict_id = f.dictID;
     const bool hc = p.compressionLevel >= 3;                           // (the deterministic finders whatever the engine's switch says)
-    if (hc) {
-        const HcLevel hl = hc_level(p.compressionLevel);
-        pf.hc_attempts = e->sw.hc_attempts ? e->sw.hc_attempts : hl.attempts;
-        pf.hc_lazy = e->sw.hc_lazy ? e->sw.hc_lazy : hl.lazy;
-    }
+    if (hc) { const HcLevel hl = hc_level_of(p.compressionLevel, e->sw); pf.hc_attempts = hl.attempts; pf.hc_lazy = hl.lazy; }
     // the tables and the pool, from the call's arguments alone: chunks are 64 KiB whatever the block size (pick_chunk_size), so spans
     // that do not overlap have at most n_frames + srcBytes / 64 KiB chunks, no more blocks, and a record per 4 bytes + one per chunk
     const uint64_t cap = batch_table_cap(n_frames, srcBytes / BC_CHUNK);
@@ -1376,21 +1382,9 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
     hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
     hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
-    if (hc && dict_len && hc_digest)
-        hipLaunchKernelGGL(k_bc_find_hc_cdict, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
-                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf, dict_end, dict_len, hc_digest);
-    else if (hc)                                                       // (also a prepared dictionary of 1-3 bytes: the finder ignores it)
-        hipLaunchKernelGGL(k_bc_find_hc, batch_grid(cap, 1, BATCH_GRID / 4), dim3(64 * HC_WAVES), 0, st, src, (const BcFrame*)frames, n_frames,
-                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, pf);
-    else if (dict_len && digest)
-        hipLaunchKernelGGL(k_bc_find_solo_cdict, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
-                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, dict_end, dict_len, digest);
-    else if (dict_len)
-        hipLaunchKernelGGL(k_bc_find_solo_dict, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
-                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool, dict_end, dict_len);
-    else
-        hipLaunchKernelGGL(k_bc_find_solo, batch_grid(cap, 1, BATCH_GRID * 2), dim3(64), 0, st, src, (const BcFrame*)frames, n_frames,
-                           (const BcChunk*)chunks, (const uint32_t*)ctl, info, pool);
+    const BcFind find = bc_finder(hc, dc);
+    hipLaunchKernelGGL(find.kernel, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
+                       (const uint32_t*)ctl, info, pool, pf, dc);
     hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
     hipLaunchKernelGGL((k_bc_frames<W>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results);
     hipLaunchKernelGGL((k_bc_emit<W>), g_ent, dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
@@ -1409,13 +1403,13 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
                                       void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
                                       lz4f_mi355x_result* d_results)
 {
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, nullptr, 0);
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false);
 }
 size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
                                                 lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
 {
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, d_dict, dictSize);
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{batch_dict_tail(d_dict, dictSize)}, false);
 }
 
 // ---- the prepared dictionary: the dictionary's last 64 KiB, owned, and the finder's table seeded from them once (createCDictHC: the
@@ -1429,12 +1423,11 @@ static size_t create_cdict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const
     lz4f_mi355x_cdict* c = new (std::nothrow) lz4f_mi355x_cdict();
     if (!c) { set_last_error("%s: out of memory", who); return make_err(LZ4F_ERROR_allocation_failed); }
     c->engine = e; c->hc = hc;
-    const uint8_t* dict_end; uint32_t dict_len;
-    batch_dict_tail(d_dict, dictSize, dict_end, dict_len);
-    if (dict_len) {
+    const DictTail src = batch_dict_tail(d_dict, dictSize);
+    if (src.len) {
         // one allocation: the digests (16-byte aligned: they lead, and both are whole vectors), then the copy
         void* p = nullptr;
-        const size_t hc_bytes = hc ? hc_digest_bytes(dict_len) : 0, bytes = SOLO_DIGEST_BYTES + hc_bytes + (size_t)dict_len;
+        const size_t hc_bytes = hc ? hc_digest_bytes(src.len) : 0, bytes = SOLO_DIGEST_BYTES + hc_bytes + (size_t)src.len;
         const hipError_t he = hipMalloc(&p, bytes);
         if (he != hipSuccess) {
             (void)hipGetLastError();
@@ -1442,16 +1435,17 @@ static size_t create_cdict(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** out, const
             delete c;
             return make_err(LZ4F_ERROR_allocation_failed);
         }
-        c->digest = (uint4*)p; c->data = (uint8_t*)p + SOLO_DIGEST_BYTES + hc_bytes; c->size = dict_len;
-        if (hc) c->hc_digest = (uint4*)((uint8_t*)p + SOLO_DIGEST_BYTES);
+        uint8_t* data = (uint8_t*)p + SOLO_DIGEST_BYTES + hc_bytes;
+        uint4* solo_digest = (uint4*)p, * hc_digest = hc ? (uint4*)((uint8_t*)p + SOLO_DIGEST_BYTES) : nullptr;
+        c->mem = p; c->dict.end = data + src.len; c->dict.len = src.len; c->dict.solo_digest = solo_digest; c->dict.hc_digest = hc_digest;
         hipStream_t st = (hipStream_t)e->stream;
-        if (hipMemcpyAsync(c->data, dict_end - dict_len, dict_len, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        if (hipMemcpyAsync(data, src.end - src.len, src.len, hipMemcpyDeviceToDevice, st) != hipSuccess) {
             (void)hipGetLastError(); (void)hipFree(p); delete c;
             set_last_error("%s: the dictionary's copy failed", who);
             return make_err(LZ4F_ERROR_GENERIC);
         }
-        hipLaunchKernelGGL(k_solo_digest_dict, dim3(1), dim3(64), 0, st, (const uint8_t*)c->data + dict_len, dict_len, c->digest);
-        if (hc) hipLaunchKernelGGL(k_hc_digest_dict, dim3(1), dim3(64 * HC_WAVES), 0, st, (const uint8_t*)c->data + dict_len, dict_len, c->hc_digest);
+        hipLaunchKernelGGL(k_solo_digest_dict, dim3(1), dim3(64), 0, st, c->dict.end, c->dict.len, solo_digest);
+        if (hc) hipLaunchKernelGGL(k_hc_digest_dict, dim3(1), dim3(64 * HC_WAVES), 0, st, c->dict.end, c->dict.len, hc_digest);
         if (hipGetLastError() != hipSuccess) {                             // (the copy may be in flight: wait before its target goes)
             (void)hipStreamSynchronize(st); (void)hipFree(p); delete c;
             set_last_error("%s: launch failed", who);
@@ -1476,11 +1470,11 @@ size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c)
 {
     if (!c) return 0;
     size_t r = 0;
-    if (c->digest) {                                                       // (an empty one owns nothing and has nothing in flight)
+    if (c->mem) {                                                          // (an empty one owns nothing and has nothing in flight)
         if (hipSetDevice(c->engine->device) != hipSuccess || hipStreamSynchronize((hipStream_t)c->engine->stream) != hipSuccess) {
             (void)hipGetLastError(); set_last_error("dev_freeCDict: waiting for the engine's stream failed"); r = make_err(LZ4F_ERROR_GENERIC);
         }
-        (void)hipFree(c->digest);
+        (void)hipFree(c->mem);
     }
     delete c;
     return r;
@@ -1488,8 +1482,8 @@ size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c)
 
 const void* lz4f_mi355x_cdict_data(const lz4f_mi355x_cdict* c, size_t* size)
 {
-    if (size) *size = c ? c->size : 0;
-    return c && c->size ? c->data : nullptr;
+    if (size) *size = c ? c->dict.len : 0;
+    return c && c->dict.len ? c->dict.end - c->dict.len : nullptr;
 }
 
 size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
@@ -1497,11 +1491,12 @@ size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t
                                                  lz4f_mi355x_result* d_results, const lz4f_mi355x_cdict* cdict)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (!cdict || !cdict->size) return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, nullptr, 0);
+    if (!cdict || !cdict->dict.len) return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false);
     if (cdict->engine != e) { set_last_error("dev_compressFrames_usingCDict: cdict belongs to another engine"); return make_err(LZ4F_ERROR_GENERIC); }
     // (a dictionary of 1-3 bytes: the finder ignores it, its digest is the cleared table - the _usingDict kernel, as that call launches it)
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, cdict->data, cdict->size,
-                           cdict->size >= 4 ? cdict->digest : nullptr, cdict->hc, cdict->size >= 4 ? cdict->hc_digest : nullptr);
+    EncDict dc = cdict->dict;
+    if (dc.len < 4) dc.solo_digest = dc.hc_digest = nullptr;
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, dc, cdict->hc);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

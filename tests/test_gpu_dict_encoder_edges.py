@@ -2,9 +2,9 @@
 back, and 65536), the seam (a match's source lies on one side of it), dictionaries of 4 and 7 bytes, the dictionary in front of
 every block of an independent frame and of a linked frame's first 64 KiB only, and a match at a frame's first byte.
 
-Encoders:  U0   lz4f_mi355x_dev_compressFrames_usingDict, level 0 (k_bc_find_solo_dict)
-           P0, P2   ..._usingCDict with the plain CDict, levels 0 and 2 (k_bc_find_solo_cdict)
-           H3, H9, H12   ..._usingCDict with create_cdict(d, hc=True) (k_bc_find_hc_cdict)
+Encoders:  U0   lz4f_mi355x_dev_compressFrames_usingDict, level 0 (k_bc_find_solo<true, false>)
+           P0, P2   ..._usingCDict with the plain CDict, levels 0 and 2 (k_bc_find_solo<true, true>)
+           H3, H9, H12   ..._usingCDict with create_cdict(d, hc=True) (k_bc_find_hc<true>)
 Framings:  i64, l64, l256 of encoder_cases.FRAMINGS.  One batch call per (encoder, framing, dictionary) carries all of that
 dictionary's cases; it is made once and shared by the tests below (`runs`).
 
