@@ -647,6 +647,61 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, 
                                                          const void* d_pack, size_t packBytes, uint64_t* d_src_off,
                                                          lz4f_mi355x_result* d_result);
 
+/* BATCH SPLIT: the frame boundaries of a concatenated LZ4 stream, found on the device - the d_src_off that the measure and decode
+ * calls take, for a stream that came WITHOUT a directory: a packed stream whose sender wrote none, `cat a.lz4 b.lz4`, the output of
+ * writers that emit a frame per chunk, a log that frames are appended to.  Conventions as for the other batch calls: d_src in DEVICE
+ * memory at any byte address; d_src_off (max_frames + 1 uint64) in DEVICE memory, 8-byte aligned, not inside d_src; d_split (one
+ * record, DEVICE memory) may be NULL; srcBytes and max_frames are host values; asynchronous on the engine's stream, no host
+ * synchronisation, no device->host copy.  Nothing is written but the max_frames + 1 offsets, the record and the engine's workspace;
+ * nothing is read outside d_src[0 .. srcBytes).
+ *   - THE DEFINITION is the serial walk, whatever the stream's bytes are:
+ *         pos = 0; n = 0; bytes = 0; skipped = false
+ *         loop: if pos == srcBytes: status = 0, stop
+ *               S[pos .. srcBytes) begins with a skippable frame (any of the 16 magics) that fits: pos += 8 + its size; skipped = true
+ *               ... with an LZ4 frame whose header parses and whose size words walk to the EndMark (and the content checksum's
+ *                   word): start[n] = pos; n += 1; bytes += its length; pos += its length
+ *               anything else: status = what the batch decoder says of such a span, stop - ERROR_frameHeader_incomplete (a cut
+ *                   anywhere in a frame), ERROR_frameType_unknown (no magic; the legacy format's magic too), ERROR_reservedFlag_set,
+ *                   ERROR_headerVersion_wrong, ERROR_maxBlockSize_invalid (a header's block size ID, or a size word above the
+ *                   frame's block size), ERROR_headerChecksum_invalid
+ *     No payload is parsed and no checksum verified: those verdicts stay with the measure and decode calls.
+ *   - Output, with m = min(n, max_frames): d_src_off[i] = start[i] for i < m; every later entry, d_src_off[max_frames] included, is
+ *     start[max_frames] when n > max_frames and pos otherwise.  Span i < m so runs from frame i's first byte to the next frame's
+ *     first byte: the skippable frames behind frame i (this library's in-band trailer among them) are inside it, and the batch decoder
+ *     leaves them alone.  Skippable frames in front of the first frame (a pack directory) are in no span; surplus slots are empty
+ *     spans, which the batch decoder gives ERROR_frameHeader_incomplete; the frame the walk stops at is not listed.  So
+ *     (d_src, consumed, d_src_off, max_frames) are the d_src, srcBytes, d_src_off and n_frames of the measure and decode calls.
+ *   - d_split: status = the walk's, or ERROR_dstMaxSize_tooSmall when the walk ended with 0 but n > max_frames (a grammar error
+ *     wins); consumed = pos; n_blocks = n, ALL the frames found, so that the caller knows what to ask for; size = bytes, the frames'
+ *     own; first_bad_block = n when the walk stopped on an error, else 0xFFFFFFFF; flags: bit 8 when a skippable frame was stepped
+ *     over, and the path bits (flags >> 12): LZ4F_MI355X_PATH_BATCH | LZ4F_MI355X_PATH_PARALLEL_WALK when the parallel kernels
+ *     delivered, LZ4F_MI355X_PATH_BATCH alone when the serial kernel did.
+ *   - HOW: every byte position is looked at once (a streaming read); a position with an LZ4 magic and a header that parses, or a
+ *     skippable magic whose frame fits, is a node, and position 0 is one.  A thread per node walks its size words to where its frame
+ *     ends; the end is looked up in the node list; the true frames are the nodes REACHABLE from position 0, marked by pointer
+ *     doubling - a .lz4 file inside a stored block or a skippable frame is a node that nothing points at.  The node list holds
+ *         max_frames + srcBytes / LZ4F_MI355X_SPLIT_SHARE + 64   nodes (at most 0xFFFFFFF0),
+ *     and the workspace is srcBytes / 8 bytes of position bits, 4 bytes per 16 KiB, and 33 bytes per node: from the two arguments
+ *     alone, grown as needed.  A stream with more nodes (magics with valid headers packed into payloads) is walked by one thread
+ *     instead, behind the parallel kernels, with the same answer.  Launches: 6 and ceil(log2(node list)) doubling rounds, never a
+ *     function of the stream's bytes.
+ *   - A frame of B blocks costs ONE thread B dependent reads, about 0.35 us each (MI355X, 176 MiB of stream: 0.15 ms as 4096 frames
+ *     of 2 blocks, 0.32 ms as 8 frames of 512 blocks): this call is for streams of many frames, and does not replace the single
+ *     call's parallel walks of one big frame.
+ *   - The call itself fails only on a null engine, a null d_src or d_src_off with max_frames > 0, a failed allocation (or a stream
+ *     beyond 2^45 bytes: ERROR_srcSize_tooLarge).  max_frames == 0 returns 0 and enqueues nothing.
+ * LZ4F_MI355X_SPLIT_SERIAL set in the environment when the engine is made skips the parallel kernels (a test switch). */
+#define LZ4F_MI355X_SPLIT_SHARE 256u        /* informational: stream bytes per spare node of the split's node list */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e,
+                                                   const void* d_src, size_t srcBytes,
+                                                   uint32_t max_frames, uint64_t* d_src_off,
+                                                   lz4f_mi355x_result* d_split);
+/* The same walk over a stream in HOST memory, by one host thread (no device is touched, no engine needed): src_off and split are host
+ * memory, the answer is the device call's, the path bits are 0.  What a caller without the device call does after copying the stream
+ * down - tools/batch_split.py times the device call against exactly that. */
+LZ4F_MI355X_API size_t lz4f_mi355x_splitFrames(const void* src, size_t srcBytes, uint32_t max_frames, uint64_t* src_off,
+                                               lz4f_mi355x_result* split);
+
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,
                                              const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out);

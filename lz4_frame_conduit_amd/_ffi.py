@@ -96,6 +96,8 @@ _SIGS = {
     "lz4f_mi355x_packDirectorySize": (c_size_t, [ctypes.c_uint32]),
     "lz4f_mi355x_peekPackDirectory": (c_size_t, [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
     "lz4f_mi355x_dev_readPackDirectory": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lz4f_mi355x_dev_splitFrames": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.c_uint32, c_void_p, c_void_p]),
+    "lz4f_mi355x_splitFrames": (c_size_t, [c_void_p, c_size_t, ctypes.c_uint32, c_void_p, c_void_p]),
     "lz4f_mi355x_conduit_compress": (ctypes.c_int, [c_size_t, PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_compress_yield_immediately": (ctypes.c_int, [PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_decompress": (ctypes.c_int, [AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),

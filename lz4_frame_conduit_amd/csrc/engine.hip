@@ -17,6 +17,7 @@
 #include "encode_batch.cuh"
 #include "measure_batch.cuh"
 #include "pack_batch.cuh"
+#include "split_batch.cuh"
 
 using namespace lz4f;
 
@@ -87,6 +88,7 @@ void lz4f_mi355x_engine::Switches::read()
     no_spx = on("LZ4F_MI355X_NO_SPX");
     no_overlap = on("LZ4F_MI355X_NO_OVERLAP");
     no_content_check = on("LZ4F_MI355X_NO_CONTENT_CHECK");
+    split_serial = on("LZ4F_MI355X_SPLIT_SERIAL");
     prof = on("LZ4F_MI355X_PROF");
     e1_sync = on("LZ4F_MI355X_E1_SYNC");
     no_selffeed = on("LZ4F_MI355X_NO_SELFFEED");
@@ -178,7 +180,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); pctl.release(); cframes.release(); cblocks.release(); cchunks.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); pctl.release(); split.release(); cframes.release(); cblocks.release(); cchunks.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -1319,6 +1321,62 @@ size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frame
     hipLaunchKernelGGL(k_pk_readdir, dim3(1), dim3(1024), 0, (hipStream_t)e->stream, (const uint8_t*)d_pack, (uint64_t)packBytes, n_frames, d_src_off,
                        (ResultRec*)d_result);
     return batch_end("dev_readPackDirectory");
+}
+
+// the node list of a split call (split_batch.cuh), from the call's arguments alone: a node for every frame asked for, one more for every
+// LZ4F_MI355X_SPLIT_SHARE bytes of the stream (skippable frames, magics inside payloads), and 64
+static uint64_t sp_node_cap(uint32_t max_frames, uint64_t src_bytes)
+{
+    return std::min<uint64_t>((uint64_t)max_frames + src_bytes / LZ4F_MI355X_SPLIT_SHARE + 64, 0xFFFFFFF0ull);
+}
+// the doubling rounds that reach every node of a list of `cap`: 2^rounds >= cap
+static uint32_t sp_rounds(uint64_t cap)
+{
+    uint32_t r = 0;
+    while ((1ull << r) < cap) r++;
+    return r;
+}
+
+// the frames of a concatenated stream (split_batch.cuh): candidates, order, list, extents and links, reachability, place; the serial walk behind
+size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e, const void* d_src, size_t srcBytes, uint32_t max_frames, uint64_t* d_src_off,
+                                   lz4f_mi355x_result* d_split)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (max_frames == 0) return 0;
+    if (const size_t r = batch_begin(e, "dev_splitFrames", d_src && d_src_off)) return r;
+    hipStream_t st = (hipStream_t)e->stream;
+    const uint8_t* src = (const uint8_t*)d_src;
+    if (e->sw.split_serial) {
+        hipLaunchKernelGGL(k_split_serial, dim3(1), dim3(256), 0, st, src, (uint64_t)srcBytes, (const SpCtl*)nullptr, 1u, max_frames, d_src_off, (ResultRec*)d_split);
+        return batch_end("dev_splitFrames");
+    }
+    const uint64_t chunks64 = std::max<uint64_t>(((uint64_t)srcBytes + SP_CHUNK - 1) / SP_CHUNK, 1);      // (an empty stream has its root too)
+    if (chunks64 > 0x7FFFFFFFull) { set_last_error("dev_splitFrames: srcBytes too large"); return make_err(LZ4F_ERROR_srcSize_tooLarge); }
+    const uint32_t n_chunks = (uint32_t)chunks64;
+    const uint64_t cap = sp_node_cap(max_frames, srcBytes);
+    Carve ws{e->split};
+    const size_t bits_at = ws.take((size_t)n_chunks * (SP_CHUNK / 8), 16), counts_at = ws.take((size_t)n_chunks * 4, 16), ctl_at = ws.take(256, 256),
+                 list_at = ws.take((size_t)cap * 8, 16), nodes_at = ws.take((size_t)cap * sizeof(SpNode), 16), ja_at = ws.take((size_t)cap * 4, 16),
+                 jb_at = ws.take((size_t)cap * 4, 16), reach_at = ws.take((size_t)cap, 16);
+    if (ws.ensure()) return make_err(LZ4F_ERROR_allocation_failed);
+    uint32_t* counts = ws.at<uint32_t>(counts_at);
+    SpCtl* ctl = ws.at<SpCtl>(ctl_at);
+    uint64_t* list = ws.at<uint64_t>(list_at);
+    SpNode* nodes = ws.at<SpNode>(nodes_at);
+    uint32_t* jump[2] = {ws.at<uint32_t>(ja_at), ws.at<uint32_t>(jb_at)};
+    uint8_t* reach = ws.at<uint8_t>(reach_at);
+    const dim3 g_chunks = batch_grid(n_chunks, 1, PK_GRID), g_nodes = batch_grid(cap, 256);
+    hipLaunchKernelGGL(k_sp_cand, g_chunks, dim3(SP_THREADS), 0, st, src, (uint64_t)srcBytes, n_chunks, ws.at<uint16_t>(bits_at), counts);
+    hipLaunchKernelGGL(k_sp_order, dim3(1), dim3(1024), 0, st, counts, n_chunks, (uint32_t)cap, ctl);
+    hipLaunchKernelGGL(k_sp_list, g_chunks, dim3(SP_THREADS), 0, st, (const uint64_t*)ws.at<uint64_t>(bits_at), (const uint32_t*)counts, n_chunks, (const SpCtl*)ctl, list);
+    hipLaunchKernelGGL(k_sp_extent, g_nodes, dim3(256), 0, st, src, (uint64_t)srcBytes, (const SpCtl*)ctl, (const uint64_t*)list, nodes, jump[0], reach);
+    const uint32_t rounds = sp_rounds(cap);
+    for (uint32_t r = 0; r < rounds; r++)
+        hipLaunchKernelGGL(k_sp_double, g_nodes, dim3(256), 0, st, (const SpCtl*)ctl, (const uint32_t*)jump[r & 1], jump[(r & 1) ^ 1], reach);
+    hipLaunchKernelGGL(k_sp_place, dim3(1), dim3(1024), 0, st, src, (uint64_t)srcBytes, ctl, (const uint64_t*)list, (const SpNode*)nodes, (const uint8_t*)reach,
+                       max_frames, d_src_off, (ResultRec*)d_split);
+    hipLaunchKernelGGL(k_split_serial, dim3(1), dim3(256), 0, st, src, (uint64_t)srcBytes, (const SpCtl*)ctl, 0u, max_frames, d_src_off, (ResultRec*)d_split);
+    return batch_end("dev_splitFrames");
 }
 
 // The finder kernel of a batch (encode_batch.cuh) and the most workgroups it gets: by the level, and by what the dictionary brings

@@ -79,12 +79,13 @@ struct lz4f_mi355x_engine {
     lz4f::DevBuf bframes, btable;                          // dev_decompressFrames: per-frame records + control words, the batch's block table
     lz4f::DevBuf mframes, mtable;                          // dev_measureFrames: per-frame records, windows, counts + control words, the batch's block table
     lz4f::DevBuf pctl;                                     // dev_packFrames: the control block (the scan's verdict, for the copy)
+    lz4f::DevBuf split;                                    // dev_splitFrames: the position bits and chunk counts, the control block, the node list and its links (split_batch.cuh)
     lz4f::DevBuf cframes, cblocks, cchunks;                // dev_compressFrames: per-frame records + control words, the batch's block and chunk tables (ChunkInfo: `info`, records: `recs`)
     lz4f::PinBuf h_in, h_out, h_small;
     // A-B and development switches: read from the environment ONCE, when the engine is made (engines of the host-pointer calls
     // live in a pool: lz4f_mi355x_release_engines() makes the next ones read it again)
     struct Switches {
-        bool no_index, no_selfindex, no_resolve, no_trace, no_doubling, trace_always, no_groups, no_window, serial_walk, no_trailer, no_content_check, no_density_probe, no_spx, no_overlap, prof, e1_sync, no_selffeed;
+        bool no_index, no_selfindex, no_resolve, no_trace, no_doubling, trace_always, no_groups, no_window, serial_walk, no_trailer, no_content_check, split_serial, no_density_probe, no_spx, no_overlap, prof, e1_sync, no_selffeed;
         unsigned dense_mode;           // dense payloads in big independent blocks (LZ4F_MI355X_DENSE_MODE): 0 by block count, 1 workgroup per block (decode_relay.cuh), 2 wave per block
         unsigned group_kib;            // (development) bytes of consecutive small blocks of a linked frame a workgroup of the indexed copy kernel takes
         unsigned feed_round;           // (test switch) sequences per parse round of the self-feeding copy kernel's first wave

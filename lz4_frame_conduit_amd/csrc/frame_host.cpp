@@ -730,6 +730,59 @@ size_t lz4f_mi355x_compressFrame(void* dst, size_t dstCapacity, const void* src,
     return used;
 }
 
+// ---- the frames of a concatenated stream in host memory: the walk that defines lz4f_mi355x_dev_splitFrames, on the host ----
+// what stands at s[0 .. n): 0, its bytes and whether it is a skippable frame; or the status the walk stops with
+static uint32_t frame_extent(const uint8_t* s, size_t n, uint64_t& bytes, bool& skip)
+{
+    skip = false;
+    if (n < 7) return ST_INCOMPLETE;
+    if (is_skippable(rd32le(s))) { skip = true; return skippable_span(s, n, bytes); }
+    FrameHead h;
+    if (const uint32_t st = frame_head_parse(s, n, h)) return st;
+    uint64_t pos = h.hsize;
+    for (;;) {
+        if (!frame_word_fits(n - pos)) return ST_INCOMPLETE;
+        const uint32_t w = rd32le(s + pos);
+        pos += 4;
+        if (is_endmark(w)) break;
+        uint32_t csz; uint64_t step;
+        if (const uint32_t st = frame_block_word(w, h.bs, h.bck, n - pos, csz, step)) return st;
+        pos += step;
+    }
+    uint32_t tail;
+    if (const uint32_t st = frame_end(h.flg, n - pos, tail)) return st;
+    bytes = pos + tail;
+    return ST_OK;
+}
+size_t lz4f_mi355x_splitFrames(const void* src, size_t srcBytes, uint32_t max_frames, uint64_t* src_off, lz4f_mi355x_result* split)
+{
+    if (max_frames == 0) return 0;
+    if (!src || !src_off) { set_last_error("splitFrames: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    const uint8_t* s = (const uint8_t*)src;
+    uint64_t pos = 0, bytes = 0, cut = 0;
+    uint32_t n = 0, status = ST_OK;
+    bool skipped = false;
+    while (pos < srcBytes) {
+        uint64_t took = 0; bool skip = false;
+        if ((status = frame_extent(s + pos, srcBytes - pos, took, skip)) != ST_OK) break;
+        if (skip) skipped = true;
+        else {
+            if (n < max_frames) src_off[n] = pos;
+            if (n == max_frames) cut = pos;
+            n++; bytes += took;
+        }
+        pos += took;
+    }
+    for (uint64_t i = n < max_frames ? n : max_frames; i <= max_frames; i++) src_off[i] = n > max_frames ? cut : pos;
+    if (split) {
+        split->size = bytes; split->consumed = pos; split->n_blocks = n;
+        split->status = status ? status : (n > max_frames ? (uint32_t)ST_DSTSMALL : (uint32_t)ST_OK);
+        split->first_bad_block = status ? n : 0xFFFFFFFFu;
+        split->flags = skipped ? FLAG_SKIPPABLE : 0u;
+    }
+    return 0;
+}
+
 // ---- the block list of a finished frame in host memory (ours or any other encoder's), as the trailer the device decoder looks for ----
 // (host work only: one 4-byte read per block)
 static size_t walk_for_block_list(const uint8_t* s, size_t n, BlockList* bl)

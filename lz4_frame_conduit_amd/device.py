@@ -126,6 +126,21 @@ def _check_read_directory_args(pack, n_frames, src_off, record, rec_bytes: int) 
     return n_frames
 
 
+def _check_split_args(src, max_frames, src_off, record, rec_bytes: int) -> int:
+    """The arguments of Engine.split_frames_async -> max_frames; ValueError for what is wrong with them."""
+    named = [("src", src, torch.uint8), ("src_off", src_off, torch.int64)]
+    if record is not None:
+        named.append(("record", record, torch.uint8))
+    _check_tensors(named, "a split")
+    if not isinstance(max_frames, int) or isinstance(max_frames, bool) or not 0 <= max_frames < 1 << 32:
+        raise ValueError("max_frames must be an int in [0, 2^32)")
+    if src_off.numel() != max_frames + 1:
+        raise ValueError("src_off must hold max_frames+1 = %d offsets (got %d)" % (max_frames + 1, src_off.numel()))
+    if record is not None and record.numel() < rec_bytes:
+        raise ValueError("record must hold %d bytes (got %d)" % (rec_bytes, record.numel()))
+    return max_frames
+
+
 PACK_TILE = 16384       # LZ4F_MI355X_PACK_TILE: the output bytes a workgroup of the pack's copy kernel takes at a time (for tests and tools)
 PACK_DIRECTORY = 0x1    # LZ4F_MI355X_PACK_DIRECTORY
 
@@ -436,6 +451,27 @@ class Engine:
         n = _check_read_directory_args(pack, n_frames, src_off, record, self.RESULT_BYTES)
         _chk(self.L, self.L.lz4f_mi355x_dev_readPackDirectory(self.h, n, pack.data_ptr(), pack.numel(), src_off.data_ptr(),
                                                              record.data_ptr() if record is not None else None))
+
+    def split_frames_async(self, src: torch.Tensor, max_frames: int, src_off: torch.Tensor, record: "torch.Tensor | None" = None):
+        """Enqueue the search for the frame boundaries of a concatenated LZ4 stream that came without a directory: src is the stream,
+        a uint8 device tensor; src_off (int64 device tensor of max_frames+1 elements) receives the frames' offsets into src, as
+        measure_frames_async and decompress_frames_async take them.  The answer is the serial walk's - skippable frames stepped over,
+        LZ4 frames listed until something that is neither, or src's end - found without its chain of dependent reads: every position
+        is looked at once, and the frames are the candidates reachable from position 0, so a .lz4 file inside a stored block or a
+        skippable frame is never listed.  Span i runs to the next frame's first byte (the skippable frames behind frame i are in it);
+        skippable frames in front of the first frame are in no span; surplus slots are empty spans (frameHeader_incomplete to the
+        decoder).  No payload is parsed, no checksum verified.
+        record (uint8 device tensor of 32 bytes, optional) receives one Result: status (the walk's: 0, or why it stopped;
+        dstMaxSize_tooSmall when it ended well with more than max_frames frames), consumed = where the walk ended, n_blocks = all
+        the frames found, size = their bytes, first_bad_block = the frames before an error's stop (0xFFFFFFFF: none), flags bit 8 =
+        a skippable frame was stepped over.  Nothing is read back: no synchronisation.  On one stream:
+
+            eng.split_frames_async(stream, max_frames, src_off, record=rec)
+            eng.measure_frames_async(stream, src_off, results, dst_off)
+            eng.decompress_frames_async(stream, src_off, dst, dst_off, results)"""
+        n = _check_split_args(src, max_frames, src_off, record, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_splitFrames(self.h, src.data_ptr(), src.numel(), n, src_off.data_ptr(),
+                                                       record.data_ptr() if record is not None else None))
 
     def frame_results(self, results: torch.Tensor) -> "list[Result]":
         """Wait for the stream, then the records of a batch (status 0 = ok; otherwise the LZ4F error code of that frame)."""
