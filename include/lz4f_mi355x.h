@@ -583,6 +583,80 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_eng
                                                                  const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
                                                                  const lz4f_mi355x_cdict* cdict);
 
+/* A SET OF DICTIONARIES for the batch calls: one chosen per frame, by a slot the caller gives or by the dictID in the frame's own
+ * header.  A store has a dictionary per table, schema, tenant or message type, and a new version whenever one is retrained; with a set
+ * a mixed batch is one call, and a receiver decodes packed frames (lz4f_mi355x_dev_packFrames / _splitFrames / _readPackDirectory) each
+ * with the dictionary its header names, on one stream, with no header read back and no side channel:
+ *   compressFrames_usingDictSet -> packFrames ... readPackDirectory -> measureFrames -> decompressFrames_usingDictSet(d_slot = NULL)
+ *
+ * THE SET (lz4f_mi355x_dev_createDictSet): n_dicts (<= 65 536) members, cdicts[k] with the ID dictIDs[k] (both HOST arrays, read
+ * during the call only).  The members are CDicts of the same engine, BORROWED, not copied: they must outlive the set, and the set is
+ * freed before the engine.  A member that is NULL or an empty CDict is a dictionary of no bytes.  A receiver that only decodes makes
+ * its members with lz4f_mi355x_dev_createCDict: the decoder needs only the bytes.  The set owns one small device table (per member 32
+ * bytes, and 8 for the lookup: the IDs sorted, searched by bisection), uploaded on the engine's stream during the call; it is never
+ * written again, so one set serves any number of calls and is not consumed by them.
+ *   - dictIDs must be pairwise distinct.  A duplicate, a NULL e / out / array with n_dicts > 0, more than 65 536 members, or a member
+ *     of another engine returns ERROR_GENERIC; lz4f_mi355x_last_error says which, *out is NULL.  A failed allocation returns
+ *     ERROR_allocation_failed.  n_dicts == 0 makes a valid empty set (the arrays may be NULL).
+ *   - lz4f_mi355x_dev_freeDictSet waits for the engine's stream, then frees, like lz4f_mi355x_dev_freeCDict; NULL is accepted.
+ *   - lz4f_mi355x_dictset_count: the number of members (NULL: 0).
+ *
+ * SLOTS.  d_slot: n_frames uint32 in DEVICE memory, 4-byte aligned, read on the device.  d_slot[i] is a member's index < count, or
+ * LZ4F_MI355X_DICT_NONE: frame i has no dictionary.  Any other value, LZ4F_MI355X_DICT_UNKNOWN included, makes that frame - and only
+ * that frame - fail: status ERROR_GENERIC, size, consumed and n_blocks 0, first_bad_block 0xFFFFFFFF, flags =
+ * (LZ4F_MI355X_PATH_BATCH | LZ4F_MI355X_PATH_DICT_UNKNOWN) << 12 with the low 12 bits 0.  Nothing is written in its window and no
+ * dictionary byte is read on its behalf; a slot is held to the set before it indexes the table, so a forged one never reads outside
+ * it.  The verdicts in order - compress: the offset checks as in the plain call, then the slot; decode: the offset checks, then the
+ * header's own errors (frameHeader_incomplete, frameType_unknown, a bad descriptor or header checksum, a skippable frame cut short),
+ * then the slot.
+ *
+ * lz4f_mi355x_dev_compressFrames_usingDictSet: every sentence of the lz4f_mi355x_dev_compressFrames_usingCDict contract holds per
+ * frame.  Frame i and d_results[i] are byte for byte what that call writes for input i alone, in a batch of one, with the member
+ * d_slot[i] and prefs whose frameInfo.dictID is that member's ID (an ID of 0 writes no dictID field).  A LZ4F_MI355X_DICT_NONE frame
+ * is lz4f_mi355x_dev_compressFrames' frame with prefs as given (prefs->frameInfo.dictID included); a NULL or empty member gives the
+ * plain frame with that member's ID.
+ *   - compressionLevel 3-12: a non-empty member that was not made by lz4f_mi355x_dev_createCDictHC fails the whole call,
+ *     ERROR_compressionLevel_invalid, nothing enqueued.  (Membership is known on the host, slots are not: the rule is over all members.)
+ *   - set == NULL, a set of another engine, or d_slot == NULL, with n_frames > 0, is a call error (ERROR_GENERIC).  n_frames == 0
+ *     returns 0 and enqueues nothing.
+ *   - Unchanged: the workspace formula (the slot lives in the frame's record), a launch count that depends neither on n_frames nor on
+ *     n_dicts, any byte alignment of the data, isolation, no host synchronisation.
+ *
+ * lz4f_mi355x_dev_decompressFrames_usingDictSet: every sentence of the lz4f_mi355x_dev_decompressFrames_usingDict contract holds per
+ * frame.  Frame i's record and window bytes are what that call gives for that span and window alone with the member's bytes
+ * (lz4f_mi355x_cdict_data); with LZ4F_MI355X_DICT_NONE or an empty member they are what lz4f_mi355x_dev_decompressFrames gives.
+ * With d_slot == NULL the slot comes from the frame's header: no dictID field, a skippable frame, or a header that does not parse (the
+ * frame fails with its own error) -> LZ4F_MI355X_DICT_NONE; a field whose value is a member's ID (0 too, when a member has it) -> that
+ * member; any other value -> the unknown-slot failure above.  A dictID is still never VERIFIED against the dictionary's bytes: a frame
+ * decoded with the wrong member is caught only by a content checksum.  The workspace is the plain call's and 4 bytes per frame (the
+ * resolved slots); the launch count is the plain call's.
+ *
+ * lz4f_mi355x_dev_resolveDictIDs: one launch, a thread per frame; writes to d_slot[i] exactly what the d_slot == NULL decode uses for
+ * frame i, or LZ4F_MI355X_DICT_UNKNOWN for an ID the set does not have - to see, count or override the choice before decoding.  A span
+ * that does not lie in d_src (the decode call gives that verdict) gives LZ4F_MI355X_DICT_NONE; nothing is read outside the spans.
+ * Not covered: raw (unprepared) dictionaries as members; the single-frame, host-pointer and streaming calls. */
+typedef struct lz4f_mi355x_dictset lz4f_mi355x_dictset;
+#define LZ4F_MI355X_DICT_NONE    0xFFFFFFFFu   /* slot value: this frame has no dictionary */
+#define LZ4F_MI355X_DICT_UNKNOWN 0xFFFFFFFEu   /* written by lz4f_mi355x_dev_resolveDictIDs: the header names an ID the set does not have */
+#define LZ4F_MI355X_PATH_DICT_UNKNOWN 0x4000u  /* result.flags path bit (flags >> 12): the frame failed because its slot is no member of the set */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_createDictSet(lz4f_mi355x_engine* e, lz4f_mi355x_dictset** out, uint32_t n_dicts,
+                                                     const lz4f_mi355x_cdict* const* cdicts, const uint32_t* dictIDs);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_freeDictSet(lz4f_mi355x_dictset* s);
+LZ4F_MI355X_API uint32_t lz4f_mi355x_dictset_count(const lz4f_mi355x_dictset* s);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_resolveDictIDs(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                      const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                      const lz4f_mi355x_dictset* set, uint32_t* d_slot);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_compressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                                   const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                                   void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                                   const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
+                                                                   const lz4f_mi355x_dictset* set, const uint32_t* d_slot);
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_decompressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32_t n_frames,
+                                                                     const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                                     void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                                     lz4f_mi355x_result* d_results,
+                                                                     const lz4f_mi355x_dictset* set, const uint32_t* d_slot /* NULL: by each header's dictID */);
+
 /* BATCH PACK: the frames of a batch back to back in one contiguous stream - what is stored or sent - made on the device, on the same
  * stream, behind lz4f_mi355x_dev_compressFrames (or its _usingDict / _usingCDict forms), from that call's windows and records as they
  * are: "compress -> pack -> send" with no record read back, no host prefix sum and no copy per frame.  d_src / srcBytes / d_src_off

@@ -92,6 +92,11 @@ _SIGS = {
     "lz4f_mi355x_cdict_data": (c_void_p, [c_void_p, ctypes.POINTER(c_size_t)]),
     "lz4f_mi355x_dev_createCDictHC": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_size_t]), "lz4f_mi355x_cdict_has_hc": (ctypes.c_int, [c_void_p]),
     "lz4f_mi355x_dev_compressFrames_usingCDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p]),
+    "lz4f_mi355x_dev_createDictSet": (c_size_t, [c_void_p, ctypes.POINTER(c_void_p), ctypes.c_uint32, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_uint32)]),
+    "lz4f_mi355x_dev_freeDictSet": (c_size_t, [c_void_p]), "lz4f_mi355x_dictset_count": (ctypes.c_uint32, [c_void_p]),
+    "lz4f_mi355x_dev_resolveDictIDs": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "lz4f_mi355x_dev_compressFrames_usingDictSet": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, PP, c_void_p, c_void_p, c_void_p]),
+    "lz4f_mi355x_dev_decompressFrames_usingDictSet": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lz4f_mi355x_dev_packFrames": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, ctypes.c_uint, c_void_p]),
     "lz4f_mi355x_packDirectorySize": (c_size_t, [ctypes.c_uint32]),
     "lz4f_mi355x_peekPackDirectory": (c_size_t, [c_void_p, c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),

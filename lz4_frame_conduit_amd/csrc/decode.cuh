@@ -51,7 +51,9 @@ __device__ __forceinline__ uint64_t fetch8(const uint8_t* __restrict__ in_al, ui
 // anything is read; a match whose source begins k > 0 bytes in front of the hist bytes is copied in two parts: min(mlen, k) bytes from
 // the dictionary's end (disjoint), the rest as an ordinary match copy with the same offset - its source is then the first of the hist
 // bytes, so a match that crosses the seam, or runs through it into what it writes itself, falls out right.
-template <bool LIM, bool DICT = false>
+// UNI: the cursors go through readfirstlane at the loop's head (see there).  DICT needs it; the batch decoder's set form, which has
+// this decoder without a dictionary beside the one with, asks for it there too
+template <bool LIM, bool DICT = false, bool UNI = DICT>
 __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restrict__ in, uint32_t csize,
                                                          uint8_t* out, uint32_t cap, uint32_t wlim, uint64_t hist,
                                                          const uint8_t* dict_end = nullptr, uint32_t dict_len = 0)
@@ -75,7 +77,7 @@ __device__ __forceinline__ int32_t wave_decode_block_lim(const uint8_t* __restri
     for (;;) {
         // (DICT: the two-part copy ends in a lane-predicated branch that the compiler joins at this loop's head, where it then takes the
         // cursors for lane-dependent - and fetch8's scalar loads want them in scalar registers)
-        if constexpr (DICT) { ip = uni(ip); op = uni(op); }
+        if constexpr (UNI) { ip = uni(ip); op = uni(op); }
         // ---- token + literal length -------------------------------------------------------
         uint64_t w = fetch8(in_al, ip, lim4);
         const uint32_t token = (uint32_t)w & 0xFF;

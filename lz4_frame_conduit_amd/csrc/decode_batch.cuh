@@ -26,10 +26,19 @@
 // (these instantiations were k_bf_blocks_dict, k_bf_serial_dict, k_bf_finish_dict) every block goes through the scalar-parse decoder
 // (wave_decode_block_lim<true, true>: the offset check and the two-part match copy are there, decode.cuh) - independent blocks too,
 // which the plain call gives to wave_decode_block_win.  The plain call launches the DICT = false instantiations, which ignore `dc`.
+//
+// A SET OF DICTIONARIES (lz4f_mi355x_dev_decompressFrames_usingDictSet, dictset.cuh).  The dictionary is the frame's, not the call's:
+// k_bf_head<true> resolves every frame's slot - the caller's, or what the header's dictID names - into an array beside the frame
+// records (4 bytes a frame, this call's own workspace), and the third form of the three kernels, <W, BF_SET>, takes the set's table
+// and that array (BfSet) where the others take `dc`: the wave loads its frame's DictTail from the table, wave-uniform.  A frame
+// with a member of at least one byte decodes as DICT = true decodes it, every other frame as DICT = false does (k_bf_blocks<W, BF_SET>
+// has both decoders, and the plain one's LDS), so a frame's bytes and record are what the one-dictionary calls give it alone.
 #pragma once
 #include "common.cuh"
 #include "decode.cuh"
 #include "batch_common.cuh"
+#include "dictset.cuh"
+#include <type_traits>
 
 namespace lz4f {
 
@@ -44,13 +53,30 @@ struct BatchBlk {                           // block table entry (40 bytes)
     int32_t got, pad;                       // decoded bytes; -1 malformed, -2 does not fit
 };
 
+// The three forms of the kernels that decode blocks (their template argument DICT; false and true are the first two): no dictionary,
+// the call's one dictionary, and BF_SET - a set of dictionaries, each frame with the member its slot names
+constexpr int BF_SET = 2;
+// what a BF_SET kernel takes where the others take the call's DictTail: the set's table and the frames' resolved slots (k_bf_head<true>)
+struct BfSet : DsView {
+    const uint32_t* slot = nullptr;
+};
+template <int DICT> using BfDict = typename std::conditional<DICT == BF_SET, BfSet, DictTail>::type;
+// frame fi's dictionary (wave-uniform): the call's, or with BF_SET its member's bytes - none for DS_NONE and for a frame that failed
+__device__ __forceinline__ const DictTail& bf_frame_dict(const DictTail& dc, uint32_t) { return dc; }
+__device__ __forceinline__ DictTail bf_frame_dict(const BfSet& set, uint32_t fi) { return ds_tail(set, uni(set.slot[fi])); }
+
 // wave_decode_block judged by `cap`, writing only the first `wlim` bytes (decode.cuh: wave_decode_block_lim): -1 malformed, -2
-// decodes but not into wlim.  DICT: dc, the batch's dictionary (DictTail, common.cuh), lies in front of the history
-template <bool DICT>
+// decodes but not into wlim.  DICT: dc, the batch's dictionary (DictTail, common.cuh), lies in front of the history.  BF_SET: dc is
+// the frame's own, and a frame that has none (dc.len 0) decodes as the plain form decodes it
+template <int DICT>
 __device__ __forceinline__ int32_t bf_decode_block(const uint8_t* __restrict__ in, uint32_t csize, uint8_t* out, uint32_t cap, uint32_t wlim,
                                                    uint64_t hist, const DictTail& dc)
 {
-    if constexpr (DICT) return wave_decode_block_lim<true, true>(in, csize, out, cap, wlim, hist, (const uint8_t*)uni64((uint64_t)dc.end), uni(dc.len));
+    if constexpr (DICT == BF_SET) {                // (both decoders in one kernel: the plain one's cursors need the readfirstlane too)
+        if (dc.len) return bf_decode_block<1>(in, csize, out, cap, wlim, hist, dc);
+        return wave_decode_block_lim<true, false, true>(in, csize, out, cap, wlim, hist);
+    }
+    else if constexpr (DICT) return wave_decode_block_lim<true, true>(in, csize, out, cap, wlim, hist, (const uint8_t*)uni64((uint64_t)dc.end), uni(dc.len));
     else return wave_decode_block_lim<true>(in, csize, out, cap, wlim, hist);
 }
 
@@ -71,7 +97,7 @@ __device__ __forceinline__ void bf_move_down(uint8_t* dst, const uint8_t* src, u
 }
 
 // the tight last block (k_redo_tight_block): judged against a whole block, written only if it fits.  -> size, -2 or -3
-template <bool DICT>
+template <int DICT>
 __device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz, uint8_t* out, uint32_t bs, uint32_t room, uint64_t hist,
                                                  const DictTail& dc)
 {
@@ -79,9 +105,18 @@ __device__ __forceinline__ int32_t bf_redo_tight(const uint8_t* in, uint32_t csz
     return g == -1 ? -3 : g;
 }
 
+// SET (k_bf_head<true>): the frame's slot is resolved here and kept in slot[i] for the kernels behind - `given`[i] held to the set, or
+// with given == NULL what the header's dictID names.  The verdicts in order: the offsets, the header's own errors, then the slot - a
+// slot that is no member fails the frame (ST_GENERIC, an empty record, DS_UNKNOWN in slot[i]: k_bf_finish marks the record) before
+// anything of it is walked
+// (One kernel template, the set's arguments an empty struct in the plain form: as a shared body behind two kernels the plain form's
+// code came out with an add's operands swapped.)
+template <bool SET> struct BfHeadSet {};
+template <> struct BfHeadSet<true> { DsView set; const uint32_t* given; uint32_t* slot; };
+template <bool SET>
 __global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src, uint64_t src_bytes, const uint64_t* __restrict__ soff,
                                                  uint64_t dst_bytes, const uint64_t* __restrict__ doff, uint32_t n_frames,
-                                                 BatchFrame* __restrict__ frames, uint32_t* __restrict__ counts)
+                                                 BatchFrame* __restrict__ frames, uint32_t* __restrict__ counts, BfHeadSet<SET> hs)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_frames) return;
@@ -89,12 +124,21 @@ __global__ __launch_bounds__(256) void k_bf_head(const uint8_t* __restrict__ src
     batch_core_init(r, soff[i]);
     r.dst = doff[i]; r.win = 0;
     const uint64_t s1 = soff[i + 1], d1 = doff[i + 1];
-    uint32_t count = 0;
-    auto put = [&](uint32_t st) { r.status = st; frames[i] = r; counts[i] = count; };
+    uint32_t count = 0, my_slot = DS_NONE;
+    auto put = [&](uint32_t st) {
+        r.status = st; frames[i] = r; counts[i] = count;
+        if constexpr (SET) hs.slot[i] = my_slot;
+    };
     if (r.src > s1 || s1 > src_bytes) { r.src = 0; r.dst = 0; return put(ST_SRCPTR); }      // nothing is read or written
     if (r.dst > d1 || d1 > dst_bytes) { r.src = 0; r.dst = 0; return put(ST_DSTSMALL); }
     r.span = s1 - r.src; r.win = d1 - r.dst;
     const uint64_t cap = r.span, win = r.win;
+    if constexpr (SET) {
+        bool head_ok;
+        my_slot = ds_header_slot(src + r.src, cap, hs.set, head_ok);
+        if (hs.given) my_slot = head_ok ? ds_given_slot(hs.given[i], hs.set.count) : DS_NONE;
+        if (my_slot == DS_UNKNOWN) return put(ST_GENERIC);
+    }
     uint64_t out = 0;
     const uint32_t st = batch_frame_head(src, r,
         [&](uint32_t bs) { const uint64_t by_dst = win / bs + 2, by_src = cap / 5 + 2; return by_src < by_dst ? by_src : by_dst; },    // the single call's table bound
@@ -122,10 +166,10 @@ __global__ __launch_bounds__(256) void k_bf_table(const uint8_t* __restrict__ sr
 
 // the grid is sized by the host's bound on the table, capped (engine.hip: BATCH_GRID): the waves stride over the entries in
 // use (ctl[0]), so a small batch into a big destination buffer does not launch a workgroup per 64 KiB of it
-template <int W, bool DICT>
+template <int W, int DICT>
 __device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
                                                uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl,
-                                               uint32_t (*expand)[64], const DictTail& dc)
+                                               uint32_t (*expand)[64], const BfDict<DICT>& dc)
 {
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t total = uni(ctl[0]);
@@ -147,6 +191,10 @@ __device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, 
         if (word_stored(word)) {
             if (csz > room) got = -2;
             else { wave_copy_disjoint(dst + dof, src + so, csz); got = (int32_t)csz; }
+        } else if constexpr (DICT == BF_SET) {                     // the frame's own member; a frame without one: as the plain form
+            const DictTail fd = bf_frame_dict(dc, fi);
+            if (fd.len) got = bf_decode_block<1>(src + so, csz, dst + dof, room, room, 0, fd);
+            else got = wave_decode_block_win<true>(src + so, csz, span_end - so, dst + dof, room, expand[wv]);
         } else if constexpr (DICT) {
             got = bf_decode_block<true>(src + so, csz, dst + dof, room, room, 0, dc);
         } else {
@@ -155,11 +203,14 @@ __device__ __forceinline__ void bf_blocks_body(const uint8_t* __restrict__ src, 
         if (lane_id() == 0) { table[w].got = got; table[w].ck = ck; }
     }
 }
-template <int W, bool DICT>
+template <int W, int DICT>
 __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restrict__ src, uint8_t* dst, const BatchFrame* __restrict__ frames,
-                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl, DictTail dc)
+                                                        uint32_t n_frames, BatchBlk* __restrict__ table, const uint32_t* __restrict__ ctl, BfDict<DICT> dc)
 {
-    if constexpr (DICT) bf_blocks_body<W, true>(src, dst, frames, n_frames, table, ctl, nullptr, dc);
+    if constexpr (DICT == BF_SET) {
+        __shared__ uint32_t expand[W][64];                             // (for the frames that have no dictionary)
+        bf_blocks_body<W, BF_SET>(src, dst, frames, n_frames, table, ctl, expand, dc);
+    } else if constexpr (DICT) bf_blocks_body<W, true>(src, dst, frames, n_frames, table, ctl, nullptr, dc);
     else {
         __shared__ uint32_t expand[W][64];                             // (wave_decode_block_win's: with DICT the kernel has no LDS)
         bf_blocks_body<W, false>(src, dst, frames, n_frames, table, ctl, expand, dc);
@@ -167,14 +218,15 @@ __global__ __launch_bounds__(64 * W, 8) void k_bf_blocks(const uint8_t* __restri
 }
 
 // a wave per frame without a table slice: blocks in order
-template <int W, bool DICT>
+template <int W, int DICT>
 __device__ __forceinline__ void bf_serial_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
-                                               const DictTail& dc)
+                                               const BfDict<DICT>& dcs)
 {
     const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
     if (i >= n_frames) return;
     const uint32_t status = uni(frames[i].status), n = uni(frames[i].n_blocks), tbl_at = uni(frames[i].tbl_at);
     if (status != 0 || n == 0 || tbl_at != BF_NONE) return;
+    const auto& dc = bf_frame_dict(dcs, i);
     const uint64_t s0 = uni64(frames[i].src), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
     const uint32_t flg = uni(frames[i].flags), bs = uni(frames[i].bs), bck = flg_bck(flg);
     const bool linked = !flg_indep(flg);
@@ -210,21 +262,22 @@ __device__ __forceinline__ void bf_serial_body(const uint8_t* __restrict__ src, 
         }
     }
 }
-template <int W, bool DICT>       // (DICT: held to 8 waves a SIMD, as the plain form is, the two-part copy spills to scratch: 6 it is)
+template <int W, int DICT>        // (DICT: held to 8 waves a SIMD, as the plain form is, the two-part copy spills to scratch: 6 it is)
 __global__ __launch_bounds__(64 * W, DICT ? 4 : 8) void k_bf_serial(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames,
-                                                                   uint32_t n_frames, DictTail dc)
+                                                                   uint32_t n_frames, BfDict<DICT> dc)
 {
     bf_serial_body<W, DICT>(src, dst, frames, n_frames, dc);
 }
 
-template <int W, bool DICT>
+template <int W, int DICT>
 __device__ __forceinline__ void bf_finish_body(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
                                                const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
-                                               uint32_t (*park)[XXH_PARK / 4], const DictTail& dc)
+                                               uint32_t (*park)[XXH_PARK / 4], const BfDict<DICT>& dcs)
 {
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t i = uni(blockIdx.x * W + wv);
     if (i >= n_frames) return;
+    const auto& dc = bf_frame_dict(dcs, i);
     const uint32_t lane = lane_id();
     const BatchFrame r = frames[i];
     uint32_t status = uni(r.status), first_bad = uni(r.first_bad);
@@ -279,13 +332,14 @@ __device__ __forceinline__ void bf_finish_body(const uint8_t* __restrict__ src, 
         ResultRec x;
         x.size = size; x.consumed = consumed; x.status = status; x.n_blocks = n; x.first_bad_block = first_bad;
         x.flags = (flg & 0xFFFu) | (LZ4F_MI355X_PATH_BATCH << 12);
+        if constexpr (DICT == BF_SET) { if (dcs.slot[i] == DS_UNKNOWN) x.flags |= LZ4F_MI355X_PATH_DICT_UNKNOWN << 12; }
         results[i] = x;
     }
 }
-template <int W, bool DICT>
+template <int W, int DICT>
 __global__ __launch_bounds__(64 * W) void k_bf_finish(const uint8_t* __restrict__ src, uint8_t* dst, BatchFrame* __restrict__ frames, uint32_t n_frames,
                                                       const BatchBlk* __restrict__ table, ResultRec* __restrict__ results, uint32_t content_check,
-                                                      DictTail dc)
+                                                      BfDict<DICT> dc)
 {
     __shared__ __attribute__((aligned(16))) uint32_t park[W][XXH_PARK / 4];
     bf_finish_body<W, DICT>(src, dst, frames, n_frames, table, results, content_check, park, dc);

@@ -27,6 +27,9 @@
 //   k_bc_emit      a wave per chunk: emit_chunk (pass E2)
 //   k_bc_blockck   a wave per block: the block checksums (only when asked for)
 //   k_bc_content   a wave per frame: the content checksums, side by side (only when asked for)
+// A set of dictionaries (lz4f_mi355x_dev_compressFrames_usingDictSet, dictset.cuh): frame i has the member its slot names.  Three
+// launches come in a set form - k_bc_head_set (the slot held to the set, kept in BcFrame::pad), k_bc_find_solo_set / k_bc_find_hc_set
+// (the chunk's frame's EncDict from the set's table) and k_bc_frames<W, true> (the member's ID in the header) - the others are shared.
 // Nothing is written outside a frame's window on its behalf, and nothing at all unless the whole frame fits it.
 // Limits: no sequence index, no in-band trailer, no block table comes out, and the finders are the deterministic ones only.  A big
 // input of many blocks gets a wave for its layout and one for its content checksum: send it through lz4f_mi355x_dev_compressFrame,
@@ -37,6 +40,7 @@
 #include "encode_solo.cuh"
 #include "encode_hc.cuh"
 #include "batch_common.cuh"
+#include "dictset.cuh"
 
 namespace lz4f {
 
@@ -50,7 +54,7 @@ struct BcFrame {                            // per frame (device workspace, 72 b
     uint64_t rec_at;                        // its first record in the pool (until k_bc_place: how many it needs)
     uint64_t fsize;                         // the frame's bytes (k_bc_frames)
     uint32_t status, n_blocks, n_chunks;
-    uint32_t blk_at, chk_at, pad;           // first block / chunk entry, BC_NONE: none
+    uint32_t blk_at, chk_at, pad;           // first block / chunk entry, BC_NONE: none; pad: the set calls' slot (bc_head_body), else 0
 };
 struct BcBlk {                              // block table entry (32 bytes)
     uint64_t src, out;                      // the block in d_src; its payload's place in d_dst (k_bc_frames)
@@ -77,17 +81,22 @@ __device__ __forceinline__ bool bc_blk_live(const BcFrame* __restrict__ frames, 
     return fi < n_frames && uni(frames[fi].status) == 0 && slice_holds(uni(frames[fi].blk_at), uni(frames[fi].n_blocks), w);
 }
 
-__global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
-                                                 const uint64_t* __restrict__ doff, uint32_t n_frames, BcPrefs pf, BcFrame* __restrict__ frames)
+// SET (k_bc_head_set, the set calls): behind the offset checks the frame's slot, slot[i], is held to the set and kept in r.pad - a
+// member, DS_NONE, or DS_UNKNOWN for anything else, which fails the frame (ST_GENERIC: k_bc_frames marks its record)
+template <bool SET>
+__device__ __forceinline__ void bc_head_body(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
+                                             const uint64_t* __restrict__ doff, uint32_t n_frames, const BcPrefs& pf, BcFrame* __restrict__ frames,
+                                             const uint32_t* __restrict__ slot, uint32_t n_members)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n_frames) return;
     BcFrame r;
     r.src = 0; r.len = 0; r.dst = 0; r.win = 0; r.rec_at = 0; r.fsize = 0;
-    r.status = 0; r.n_blocks = 0; r.n_chunks = 0; r.blk_at = BC_NONE; r.chk_at = BC_NONE; r.pad = 0;
+    r.status = 0; r.n_blocks = 0; r.n_chunks = 0; r.blk_at = BC_NONE; r.chk_at = BC_NONE; r.pad = SET ? DS_NONE : 0;
     const uint64_t s0 = soff[i], s1 = soff[i + 1], d0 = doff[i], d1 = doff[i + 1];
     if (s0 > s1 || s1 > src_bytes) r.status = ST_SRCPTR;                 // nothing is read or written
     else if (d0 > d1 || d1 > dst_bytes) r.status = ST_DSTSMALL;
+    else if (SET && (r.pad = ds_given_slot(slot[i], n_members)) == DS_UNKNOWN) r.status = ST_GENERIC;
     else {
         r.src = s0; r.len = s1 - s0; r.dst = d0; r.win = d1 - d0;
         const uint64_t nb = (r.len + pf.block_size - 1) / pf.block_size, full = r.len / BC_CHUNK, rem = r.len % BC_CHUNK;
@@ -98,6 +107,17 @@ __global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint6
         }
     }
     frames[i] = r;
+}
+__global__ __launch_bounds__(256) void k_bc_head(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
+                                                 const uint64_t* __restrict__ doff, uint32_t n_frames, BcPrefs pf, BcFrame* __restrict__ frames)
+{
+    bc_head_body<false>(src_bytes, soff, dst_bytes, doff, n_frames, pf, frames, nullptr, 0u);
+}
+__global__ __launch_bounds__(256) void k_bc_head_set(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
+                                                     const uint64_t* __restrict__ doff, uint32_t n_frames, BcPrefs pf, BcFrame* __restrict__ frames,
+                                                     const uint32_t* __restrict__ slot, uint32_t n_members)
+{
+    bc_head_body<true>(src_bytes, soff, dst_bytes, doff, n_frames, pf, frames, slot, n_members);
 }
 
 // one workgroup: exclusive scans of the frames' blocks, chunks and records; a frame whose slices would end beyond a table or the pool
@@ -227,6 +247,57 @@ __global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc(const uint8_t* __r
 // what the two have in common, for the host
 using BcFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, EncDict);
 
+// THE SET FORMS (lz4f_mi355x_dev_compressFrames_usingDictSet): the dictionary is the chunk's frame's, not the call's.  The wave (the
+// workgroup) loads it for every chunk from the set's table by the frame's slot (BcFrame::pad, held to the set by k_bc_head_set),
+// wave-uniform, and runs the prepared-dictionary finder with it: solo_find_chunk<true, true> / hc_find_chunk<true>.  Those ask the
+// dictionary for a scope's first chunk only (cs_abs == low_abs) and then load ITS digest over the whole table, or clear the table when
+// the frame has no member or one of fewer than 4 bytes (dc.len < 4: seam 0, the finder runs as without a dictionary) - so a workgroup
+// that strides from a chunk of one member to a chunk of another carries nothing over, as the one-dictionary forms carry nothing from
+// chunk to chunk.  (At levels 3-12 the host lets only hash-chain CDicts in as non-empty members: dc.hc_digest is there when seam is.)
+__device__ __forceinline__ EncDict bc_frame_dict(const DsView& set, const BcFrame* __restrict__ frames, uint32_t fi)
+{
+    EncDict dc;
+    const uint32_t s = uni(frames[fi].pad);
+    if (s < set.count) {
+        const DsMember* m = set.members + s;
+        dc.end = (const uint8_t*)uni64((uint64_t)m->end); dc.len = uni(m->len);
+        dc.solo_digest = (const uint4*)uni64((uint64_t)m->solo_digest); dc.hc_digest = (const uint4*)uni64((uint64_t)m->hc_digest);
+    }
+    return dc;
+}
+__global__ __launch_bounds__(64) void k_bc_find_solo_set(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
+                                                         const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
+                                                         ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, DsView set)
+{
+    __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BcChunk e = chunks[w];
+        const uint32_t fi = uni(e.frame);
+        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
+        const EncPlace pl = bc_place_of(e);
+        const EncDict dc = bc_frame_dict(set, frames, fi);
+        solo_find_chunk<true, true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), solo_digest_table(s_dig), solo_digest_tags(s_dig), dc);
+    }
+}
+__global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc_set(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
+                                                                  const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
+                                                                  ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, DsView set)
+{
+    __shared__ HcShared sh;
+    const uint32_t total = uni(ctl[0]);
+    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const BcChunk e = chunks[w];
+        const uint32_t fi = uni(e.frame);
+        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
+        const EncPlace pl = bc_place_of(e);
+        const EncDict dc = bc_frame_dict(set, frames, fi);
+        hc_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dc);
+        __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
+    }
+}
+using BcSetFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, DsView);
+
 // a wave per block: pass S's per-block step
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_bc_layout(const BcFrame* __restrict__ frames, uint32_t n_frames, BcBlk* __restrict__ blocks,
@@ -242,10 +313,15 @@ __global__ __launch_bounds__(64 * W) void k_bc_layout(const BcFrame* __restrict_
     }
 }
 
-// a wave per frame: where its blocks go, whether the window holds the frame, and everything of the frame that is not a block's payload
-template <int W>
+// a wave per frame: where its blocks go, whether the window holds the frame, and everything of the frame that is not a block's payload.
+// SET (k_bc_frames<W, true>): the header's dictID is the frame's member's ID (DS_NONE: the call's, pf.dict_id), and a frame whose slot was
+// no member gets the unknown-slot record
+// (One kernel template, the set an empty struct in the plain form: a shared body behind two kernels changed the plain form's code.)
+template <bool SET> struct BcFramesSet {};
+template <> struct BcFramesSet<true> : DsView {};
+template <int W, bool SET>
 __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __restrict__ frames, uint32_t n_frames, BcPrefs pf, BcBlk* __restrict__ blocks,
-                                                      ChunkInfo* __restrict__ info, ResultRec* __restrict__ results)
+                                                      ChunkInfo* __restrict__ info, ResultRec* __restrict__ results, BcFramesSet<SET> set)
 {
     const uint32_t i = uni(blockIdx.x * W + (threadIdx.x >> 6));
     if (i >= n_frames) return;
@@ -253,7 +329,18 @@ __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __r
     const uint32_t status = uni(frames[i].status), nb = uni(frames[i].n_blocks), nc = uni(frames[i].n_chunks);
     const uint32_t blk_at = uni(frames[i].blk_at), chk_at = uni(frames[i].chk_at);
     const uint64_t len = uni64(frames[i].len), d0 = uni64(frames[i].dst), win = uni64(frames[i].win);
-    auto flg_with = [&](bool csize) { return make_flg(!pf.linked, pf.block_checksum, csize, pf.content_checksum, pf.dict_id != 0); };
+    uint32_t set_id = 0;                                                  // SET: the header's dictID
+    if constexpr (SET) {
+        set_id = pf.dict_id;
+        const uint32_t s = uni(frames[i].pad);
+        if (s < set.count) set_id = uni(set.members[s].id);
+        else if (s != DS_NONE) {
+            if (lane == 0) results[i] = ResultRec{0ull, 0ull, (uint32_t)ST_GENERIC, 0u, 0xFFFFFFFFu, (LZ4F_MI355X_PATH_BATCH | LZ4F_MI355X_PATH_DICT_UNKNOWN) << 12};
+            return;
+        }
+    }
+    const uint32_t dict_id = SET ? set_id : pf.dict_id;
+    auto flg_with = [&](bool csize) { return make_flg(!pf.linked, pf.block_checksum, csize, pf.content_checksum, (SET ? set_id : pf.dict_id) != 0); };
     if (status != 0) {                                                    // (no frame: the call's FLG)
         if (lane == 0) results[i] = ResultRec{0ull, 0ull, status, 0u, 0xFFFFFFFFu, flg_with(pf.content_size) | (LZ4F_MI355X_PATH_BATCH << 12)};
         return;
@@ -277,7 +364,7 @@ __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __r
     if (fits) {
         if (lane == 0) {                                                  // the header: made in registers, then stored
             uint8_t h[20];
-            const uint32_t n = frame_head_write(h, flg, pf.bsid, len, pf.dict_id);
+            const uint32_t n = frame_head_write(h, flg, pf.bsid, len, dict_id);
             for (uint32_t q = 0; q < n; q++) dst[d0 + q] = h[q];
         }
         for (uint32_t b = lane; b < nb; b += WAVE) st32le(dst + blocks[blk_at + b].out - 4, blocks[blk_at + b].word);

@@ -1014,6 +1014,17 @@ struct lz4f_mi355x_cdict {
     void* mem = nullptr;                   // the allocation; NULL: an empty dictionary
 };
 
+// A set of prepared dictionaries (lz4f_mi355x_dev_createDictSet, dictset.cuh): its engine's; the members are borrowed.  One device
+// allocation, uploaded on the engine's stream at creation and never written again: DsMember[count], the IDs sorted, the members in
+// that order
+struct lz4f_mi355x_dictset {
+    lz4f_mi355x_engine* engine = nullptr;
+    DsView view;                           // the device table (count 0: nothing allocated)
+    bool all_hc = true;                    // every non-empty member was made by createCDictHC: the set serves levels 3-12
+    void* mem = nullptr;
+    std::vector<uint8_t> staged;           // the table as it was uploaded (kept: the copy may read it after createDictSet returned)
+};
+
 extern "C" {
 
 const char* lz4f_mi355x_last_error(void) { return lz4f::last_error(); }
@@ -1214,9 +1225,11 @@ static DictTail batch_dict_tail(const void* d_dict, size_t dictSize)
     return t;
 }
 
+// `set` (with d_slot, which may be NULL): a set of dictionaries where d_dict / dictSize give one, each frame with the member its slot
+// or its header names (lz4f_mi355x_dev_decompressFrames_usingDictSet)
 static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results,
-                                const void* d_dict, size_t dictSize)
+                                const void* d_dict, size_t dictSize, const lz4f_mi355x_dictset* set = nullptr, const uint32_t* d_slot = nullptr)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     if (n_frames == 0) return 0;
@@ -1227,6 +1240,7 @@ static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const 
     const uint64_t table_cap = batch_table_cap(n_frames, dstBytes / BF_SHARE);
     Carve ws{e->bframes};
     const size_t frames_at = ws.take((size_t)n_frames * sizeof(BatchFrame)), counts_at = ws.take((size_t)n_frames * 4), ctl_at = ws.take(256, 256);
+    const size_t slots_at = set ? ws.take((size_t)n_frames * 4, 4) : 0;          // (the set call's own: the frames' resolved slots)
     if (ws.ensure() || e->btable.ensure((size_t)table_cap * sizeof(BatchBlk))) return make_err(LZ4F_ERROR_allocation_failed);
     BatchFrame* frames = ws.at<BatchFrame>(frames_at);
     uint32_t* counts = ws.at<uint32_t>(counts_at);
@@ -1235,7 +1249,21 @@ static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const 
     const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
-    hipLaunchKernelGGL(k_bf_head, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts);
+    if (set) {                                                         // the same six launches in their BF_SET form
+        BfSet bs; (DsView&)bs = set->view; bs.slot = ws.at<uint32_t>(slots_at);
+        hipLaunchKernelGGL(k_bf_head<true>, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts,
+                           BfHeadSet<true>{set->view, d_slot, ws.at<uint32_t>(slots_at)});
+        hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
+        hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
+        hipLaunchKernelGGL((k_bf_blocks<W, BF_SET>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table,
+                           (const uint32_t*)ctl, bs);
+        hipLaunchKernelGGL((k_bf_serial<W, BF_SET>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, bs);
+        hipLaunchKernelGGL((k_bf_finish<W, BF_SET>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
+                           e->sw.no_content_check ? 0u : 1u, bs);
+        return batch_end("dev_decompressFrames_usingDictSet");
+    }
+    hipLaunchKernelGGL(k_bf_head<false>, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts,
+                       BfHeadSet<false>{});
     hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
     hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
     // (a dictionary: the DICT instantiations, every block through the scalar-parse decoder)
@@ -1390,9 +1418,12 @@ static BcFind bc_finder(bool hc, const EncDict& dc)
 
 // `dc`: the call's dictionary (EncDict{}: none) - a raw one's tail, or a prepared one's with its digests.  `dict_hc`: it is a prepared
 // one made for levels 3-12 (which may still come without dc.hc_digest: fewer than 4 bytes, which the finder ignores)
+// `set` (with d_slot): a set of dictionaries where `dc` gives one, frame i with the member d_slot[i] names
+// (lz4f_mi355x_dev_compressFrames_usingDictSet, which has checked the set against the level)
 static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                               void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                              lz4f_mi355x_result* d_results, const EncDict& dc, bool dict_hc)
+                              lz4f_mi355x_result* d_results, const EncDict& dc, bool dict_hc,
+                              const lz4f_mi355x_dictset* set = nullptr, const uint32_t* d_slot = nullptr)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
     LZ4F_preferences_t p; size_t bs;
@@ -1404,7 +1435,7 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
         return make_err(LZ4F_ERROR_compressionLevel_invalid);
     }
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len))) return r;
+    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len) && (d_slot || !set))) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
@@ -1437,14 +1468,27 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
     const dim3 g_ent = batch_grid(cap, W);                             // (a wave per entry, striding over the entries in use)
+    const BcFind find = bc_finder(hc, dc);                             // (the set forms: the same grids)
+    if (set) {                                                         // head, finder and header writer in their set forms
+        hipLaunchKernelGGL(k_bc_head_set, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames,
+                           d_slot, set->view.count);
+        hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
+        hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
+        const BcSetFinder sfind = hc ? k_bc_find_hc_set : k_bc_find_solo_set;
+        hipLaunchKernelGGL(sfind, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
+                           (const uint32_t*)ctl, info, pool, pf, set->view);
+        hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
+        BcFramesSet<true> fs; (DsView&)fs = set->view;
+        hipLaunchKernelGGL((k_bc_frames<W, true>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results, fs);
+    } else {
     hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
     hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
     hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
-    const BcFind find = bc_finder(hc, dc);
     hipLaunchKernelGGL(find.kernel, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
                        (const uint32_t*)ctl, info, pool, pf, dc);
     hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
-    hipLaunchKernelGGL((k_bc_frames<W>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results);
+    hipLaunchKernelGGL((k_bc_frames<W, false>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results, BcFramesSet<false>{});
+    }
     hipLaunchKernelGGL((k_bc_emit<W>), g_ent, dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
                        (const ChunkInfo*)info, (const uint64_t*)pool);
     if (pf.block_checksum) {
@@ -1555,6 +1599,130 @@ size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t
     EncDict dc = cdict->dict;
     if (dc.len < 4) dc.solo_digest = dc.hc_digest = nullptr;
     return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, dc, cdict->hc);
+}
+
+// ---- a set of prepared dictionaries: one chosen per frame, by slot or by the header's dictID (dictset.cuh) ----
+size_t lz4f_mi355x_dev_createDictSet(lz4f_mi355x_engine* e, lz4f_mi355x_dictset** out, uint32_t n_dicts, const lz4f_mi355x_cdict* const* cdicts,
+                                     const uint32_t* dictIDs)
+{
+    if (out) *out = nullptr;
+    if (!e || !out || (n_dicts && (!cdicts || !dictIDs))) { set_last_error("dev_createDictSet: null pointer"); return make_err(LZ4F_ERROR_GENERIC); }
+    if (n_dicts > DS_MOST) { set_last_error("dev_createDictSet: %u members (at most %u)", n_dicts, DS_MOST); return make_err(LZ4F_ERROR_GENERIC); }
+    // the IDs in order, each with its member: pairwise distinct, or the lookup has no answer
+    std::vector<std::pair<uint32_t, uint32_t>> by_id;
+    std::vector<DsMember> members;
+    try { by_id.resize(n_dicts); members.resize(n_dicts); }
+    catch (const std::bad_alloc&) { set_last_error("dev_createDictSet: out of memory"); return make_err(LZ4F_ERROR_allocation_failed); }
+    bool all_hc = true;
+    for (uint32_t k = 0; k < n_dicts; k++) {
+        const lz4f_mi355x_cdict* c = cdicts[k];
+        if (c && c->engine != e) { set_last_error("dev_createDictSet: member %u belongs to another engine", k); return make_err(LZ4F_ERROR_GENERIC); }
+        DsMember m{nullptr, nullptr, nullptr, 0u, dictIDs[k]};
+        if (c && c->dict.len) {
+            m.end = c->dict.end; m.len = c->dict.len;
+            if (m.len >= 4) { m.solo_digest = c->dict.solo_digest; m.hc_digest = c->dict.hc_digest; }      // (1-3 bytes: the finders ignore it)
+            if (!c->hc) all_hc = false;
+        }
+        members[k] = m;
+        by_id[k] = {dictIDs[k], k};
+    }
+    std::sort(by_id.begin(), by_id.end());
+    for (uint32_t k = 1; k < n_dicts; k++)
+        if (by_id[k].first == by_id[k - 1].first) {
+            set_last_error("dev_createDictSet: duplicate dictID %u (members %u and %u)", by_id[k].first, by_id[k - 1].second, by_id[k].second);
+            return make_err(LZ4F_ERROR_GENERIC);
+        }
+    if (hipSetDevice(e->device) != hipSuccess) { set_last_error("hipSetDevice failed"); return make_err(LZ4F_ERROR_GENERIC); }
+    lz4f_mi355x_dictset* s = new (std::nothrow) lz4f_mi355x_dictset();
+    if (!s) { set_last_error("dev_createDictSet: out of memory"); return make_err(LZ4F_ERROR_allocation_failed); }
+    s->engine = e; s->all_hc = all_hc;
+    if (n_dicts) {
+        const size_t members_bytes = (size_t)n_dicts * sizeof(DsMember), bytes = members_bytes + (size_t)n_dicts * 8;
+        std::vector<uint8_t>& host = s->staged;
+        try { host.resize(bytes); } catch (const std::bad_alloc&) { delete s; set_last_error("dev_createDictSet: out of memory"); return make_err(LZ4F_ERROR_allocation_failed); }
+        memcpy(host.data(), members.data(), members_bytes);
+        uint32_t* ids = (uint32_t*)(host.data() + members_bytes), * order = ids + n_dicts;
+        for (uint32_t k = 0; k < n_dicts; k++) { ids[k] = by_id[k].first; order[k] = by_id[k].second; }
+        void* p = nullptr;
+        const hipError_t he = hipMalloc(&p, bytes);
+        if (he != hipSuccess) {
+            (void)hipGetLastError(); delete s;
+            set_last_error("dev_createDictSet: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(he));
+            return make_err(LZ4F_ERROR_allocation_failed);
+        }
+        // (ordered on the stream in front of the set's first use; `host` lives as long as the set)
+        if (hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)e->stream) != hipSuccess) {
+            (void)hipGetLastError(); (void)hipStreamSynchronize((hipStream_t)e->stream); (void)hipFree(p); delete s;
+            set_last_error("dev_createDictSet: the table's upload failed");
+            return make_err(LZ4F_ERROR_GENERIC);
+        }
+        s->mem = p;
+        s->view.members = (const DsMember*)p; s->view.ids = (const uint32_t*)((uint8_t*)p + members_bytes); s->view.order = s->view.ids + n_dicts;
+        s->view.count = n_dicts;
+    }
+    *out = s;
+    return 0;
+}
+
+size_t lz4f_mi355x_dev_freeDictSet(lz4f_mi355x_dictset* s)
+{
+    if (!s) return 0;
+    size_t r = 0;
+    if (s->mem) {                                                          // (an empty one owns nothing and has nothing in flight)
+        if (hipSetDevice(s->engine->device) != hipSuccess || hipStreamSynchronize((hipStream_t)s->engine->stream) != hipSuccess) {
+            (void)hipGetLastError(); set_last_error("dev_freeDictSet: waiting for the engine's stream failed"); r = make_err(LZ4F_ERROR_GENERIC);
+        }
+        (void)hipFree(s->mem);
+    }
+    delete s;
+    return r;
+}
+
+uint32_t lz4f_mi355x_dictset_count(const lz4f_mi355x_dictset* s) { return s ? s->view.count : 0u; }
+
+// the set of a set call: there, and this engine's
+static size_t check_dictset(const lz4f_mi355x_engine* e, const lz4f_mi355x_dictset* set, const char* who)
+{
+    if (!set) { set_last_error("%s: null dictset", who); return make_err(LZ4F_ERROR_GENERIC); }
+    if (set->engine != e) { set_last_error("%s: dictset belongs to another engine", who); return make_err(LZ4F_ERROR_GENERIC); }
+    return 0;
+}
+
+size_t lz4f_mi355x_dev_resolveDictIDs(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                      const lz4f_mi355x_dictset* set, uint32_t* d_slot)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (const size_t r = check_dictset(e, set, "dev_resolveDictIDs")) return r;
+    if (const size_t r = batch_begin(e, "dev_resolveDictIDs", d_src && d_src_off && d_slot)) return r;
+    hipLaunchKernelGGL(k_ds_resolve, dim3((n_frames + 255) / 256), dim3(256), 0, (hipStream_t)e->stream, (const uint8_t*)d_src, (uint64_t)srcBytes, d_src_off,
+                       n_frames, set->view, d_slot);
+    return batch_end("dev_resolveDictIDs");
+}
+
+size_t lz4f_mi355x_dev_compressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                   void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
+                                                   lz4f_mi355x_result* d_results, const lz4f_mi355x_dictset* set, const uint32_t* d_slot)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (const size_t r = check_dictset(e, set, "dev_compressFrames_usingDictSet")) return r;
+    // (which members the frames name is known on the device only: the rule of levels 3-12 holds for every member.  Nothing is enqueued)
+    if (prefs && prefs->compressionLevel >= 3 && !set->all_hc) {
+        set_last_error("dev_compressFrames_usingDictSet: levels 3-12 take only members made by dev_createCDictHC");
+        return make_err(LZ4F_ERROR_compressionLevel_invalid);
+    }
+    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false, set, d_slot);
+}
+
+size_t lz4f_mi355x_dev_decompressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes,
+                                                     const uint64_t* d_src_off, void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
+                                                     lz4f_mi355x_result* d_results, const lz4f_mi355x_dictset* set, const uint32_t* d_slot)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    if (n_frames == 0) return 0;
+    if (const size_t r = check_dictset(e, set, "dev_decompressFrames_usingDictSet")) return r;
+    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, nullptr, 0, set, d_slot);
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

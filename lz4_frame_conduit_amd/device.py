@@ -200,10 +200,51 @@ class CDict:
 
     def close(self):
         if self.h:
+            for s in [s for s in list(self.engine._dictsets) if any(m is self for m in s.members)]:      # (the sets that borrow it go first)
+                s.close()
             h, self.h = self.h, None
             self.data_ptr, self.size = None, 0
             self.engine._cdicts.discard(self)
             self.engine.L.lz4f_mi355x_dev_freeCDict(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+DICT_NONE = 0xFFFFFFFF        # LZ4F_MI355X_DICT_NONE: a slot's "this frame has no dictionary"
+DICT_UNKNOWN = 0xFFFFFFFE     # LZ4F_MI355X_DICT_UNKNOWN: resolve_dict_ids_async's "the header names an ID the set does not have"
+PATH_DICT_UNKNOWN = 0x4000    # LZ4F_MI355X_PATH_DICT_UNKNOWN: the path bit (flags >> 12) of a frame that failed because its slot is no member
+
+
+class DictSet:
+    """A set of prepared dictionaries (Engine.create_dictset): member k is a CDict of the same engine (None: a dictionary of no bytes)
+    with the ID dict_ids[k].  compress_frames_async / decompress_frames_async(..., dictset=, slots=) then give every frame of a batch
+    its own member - by slots, an int32 device tensor of member indexes (DICT_NONE, as -1: no dictionary), or, decoding with
+    slots=None, by the dictID in each frame's header.  The members are borrowed: the set keeps references to them, and must be
+    closed before they are (the engine closes its sets first).  close() waits for the engine's stream and frees the set's table."""
+
+    def __init__(self, engine: "Engine", h, members, dict_ids):
+        self.engine, self.h = engine, h
+        self.members, self.dict_ids = tuple(members), tuple(dict_ids)
+
+    def __len__(self) -> int:
+        return int(self.engine.L.lz4f_mi355x_dictset_count(self.h)) if self.h else 0
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.engine._dictsets.discard(self)
+            self.engine.L.lz4f_mi355x_dev_freeDictSet(h)
+            self.members = ()
 
     def __enter__(self):
         return self
@@ -228,11 +269,14 @@ class Engine:
         _chk(self.L, self.L.lz4f_mi355x_engine_create(ctypes.byref(h), device, ctypes.c_void_p(self.stream.cuda_stream), 1))
         self.h = h
         self._cdicts = weakref.WeakSet()                                          # the prepared dictionaries still open: closed with the engine
+        self._dictsets = weakref.WeakSet()                                        # the dictionary sets still open: closed before the CDicts
         self._res = torch.zeros(32, dtype=torch.uint8, device="cuda:%d" % device)
         self._res_host = torch.zeros(32, dtype=torch.uint8).pin_memory()      # the result record comes back by DMA into page-locked memory: one wait, no staging
 
     def close(self):
         if self.h:
+            for s in list(self._dictsets):                                        # (a set is freed before its members)
+                s.close()
             for c in list(self._cdicts):                                          # (a CDict is freed before its engine)
                 c.close()
             self.L.lz4f_mi355x_engine_free(self.h)
@@ -338,8 +382,59 @@ class Engine:
             raise ValueError("cdict must be an open CDict (Engine.create_cdict)")
         return cdict
 
+    def create_dictset(self, cdicts, dict_ids) -> DictSet:
+        """A set of this engine's CDicts (None: a member of no bytes), member k under the ID dict_ids[k] (ints in [0, 2^32), pairwise
+        distinct; at most 65 536 members, an empty set is valid).  One small table goes to the device on the engine's stream;
+        nothing is read back."""
+        cdicts, dict_ids = list(cdicts), list(dict_ids)
+        if len(cdicts) != len(dict_ids):
+            raise ValueError("cdicts and dict_ids must be equally long (got %d and %d)" % (len(cdicts), len(dict_ids)))
+        for c in cdicts:
+            if c is not None: self._check_cdict(c)
+        for i in dict_ids:
+            if not isinstance(i, int) or isinstance(i, bool) or not 0 <= i < 1 << 32:
+                raise ValueError("a dictID must be an int in [0, 2^32)")
+        n = len(cdicts)
+        hs = (ctypes.c_void_p * max(n, 1))(*[c.h if c is not None else None for c in cdicts])
+        ids = (ctypes.c_uint32 * max(n, 1))(*dict_ids)
+        h = ctypes.c_void_p()
+        _chk(self.L, self.L.lz4f_mi355x_dev_createDictSet(self.h, ctypes.byref(h), n, hs, ids))
+        s = DictSet(self, h, cdicts, dict_ids)
+        self._dictsets.add(s)
+        return s
+
+    def _check_dictset(self, dictset, slots, n: int, others, need_slots: bool) -> "int | None":
+        """A set call's dictset= and slots= -> slots' address (None: by the headers).  slots: an int32 device tensor of n elements."""
+        if not isinstance(dictset, DictSet) or dictset.h is None:
+            raise ValueError("dictset must be an open DictSet (Engine.create_dictset)")
+        if slots is None:
+            if need_slots:
+                raise ValueError("slots must be given with dictset=")
+            return None
+        _check_tensors(list(others) + [("slots", slots, torch.int32)])
+        if slots.numel() != n:
+            raise ValueError("slots must hold one element per frame: %d (got %d)" % (n, slots.numel()))
+        return slots.data_ptr()
+
+    def resolve_dict_ids_async(self, src: torch.Tensor, src_off: torch.Tensor, dictset: DictSet, slots: torch.Tensor):
+        """Enqueue the lookup of every frame's dictID in the set: slots (int32 device tensor of n elements) receives, for the first
+        frame in src[src_off[i]:src_off[i+1]], the member whose ID the header names, DICT_NONE (-1 as int32) for a frame without the
+        field, a skippable frame, a header that does not parse or a span outside src, and DICT_UNKNOWN (-2) for an ID that no member
+        has - what decompress_frames_async(..., dictset=, slots=None) uses, to look at or to change before decoding.  Nothing is read
+        back: no synchronisation."""
+        named = [("src", src, torch.uint8), ("src_off", src_off, torch.int64)]
+        _check_tensors(named)
+        if src_off.numel() < 1:
+            raise ValueError("src_off must hold n+1 offsets (got %d)" % src_off.numel())
+        n = src_off.numel() - 1
+        if n >= 1 << 32:
+            raise ValueError("too many frames for one call")
+        p = self._check_dictset(dictset, slots, n, named, True)
+        _chk(self.L, self.L.lz4f_mi355x_dev_resolveDictIDs(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dictset.h, p))
+
     def decompress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, results: torch.Tensor,
-                                dictionary: "torch.Tensor | CDict | None" = None):
+                                dictionary: "torch.Tensor | CDict | None" = None, dictset: "DictSet | None" = None,
+                                slots: "torch.Tensor | None" = None):
         """Enqueue a batch: frame i is the first frame in src[src_off[i]:src_off[i+1]], its output goes to dst[dst_off[i]:dst_off[i+1]].
         src, dst: uint8 device tensors; src_off, dst_off: int64 device tensors of n+1 offsets; results: uint8 device tensor of
         32*n bytes (new_results).  Each frame's verdict lands in its record (frame_results) - a bad frame fails alone, the call
@@ -347,8 +442,21 @@ class Engine:
         dictionary (a uint8 tensor on the engine's device): one shared dictionary for the whole batch, as LZ4F_decompress_usingDict
         applies it - the history in front of every frame (linked blocks) or every block (independent blocks); its last 64 KiB count.
         It must stay alive until the stream has run the call.  The header's dictID is not looked at.  A CDict (create_cdict) is
-        taken too: the dictionary is then its own copy."""
+        taken too: the dictionary is then its own copy.
+        dictset (create_dictset; not together with dictionary=): a dictionary per frame - frame i decodes with the member slots[i]
+        (int32 device tensor of n elements; DICT_NONE, -1: none), or with slots=None the member whose ID its own header names (no
+        dictID field: none).  A slot or an ID that is no member fails that frame alone (ERROR_GENERIC, PATH_DICT_UNKNOWN in its
+        record's path bits) and leaves its window untouched."""
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        if dictset is not None:
+            if dictionary is not None:
+                raise ValueError("give dictionary= or dictset=, not both")
+            p = self._check_dictset(dictset, slots, n, [("src", src, torch.uint8)], False)
+            _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames_usingDictSet(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
+                                                                             dst.numel(), dst_off.data_ptr(), results.data_ptr(), dictset.h, p))
+            return
+        if slots is not None:
+            raise ValueError("slots= goes with dictset=")
         if dictionary is not None:
             if isinstance(dictionary, CDict):
                 d_ptr, d_len = self._check_cdict(dictionary).data_ptr, dictionary.size
@@ -376,7 +484,8 @@ class Engine:
                                                          dst_off.data_ptr() if dst_off is not None else None, results.data_ptr()))
 
     def compress_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor, prefs: Preferences,
-                              results: torch.Tensor, dictionary: "torch.Tensor | None" = None, cdict: "CDict | None" = None):
+                              results: torch.Tensor, dictionary: "torch.Tensor | None" = None, cdict: "CDict | None" = None,
+                              dictset: "DictSet | None" = None, slots: "torch.Tensor | None" = None):
         """Enqueue a batch: input i is src[src_off[i]:src_off[i+1]], its frame is written at dst[dst_off[i]] and may use
         dst[dst_off[i]:dst_off[i+1]] (this module's frame_windows gives offsets that always suffice).  One prefs for all frames; a non-zero
         prefs.frameInfo.contentSize means every header declares its own input's length.  Tensors as for decompress_frames_async,
@@ -390,12 +499,24 @@ class Engine:
         cdict (create_cdict, of this engine; not together with dictionary=): the same dictionary prepared once - the same frames,
         byte for byte, without reading and seeding the dictionary again for every 64 KiB chunk of every call.  Levels 3-12 take a
         CDict made with create_cdict(..., hc=True) - the hash-chain search with the dictionary in front of every frame or independent
-        block - and raise compressionLevel_invalid for one made without."""
+        block - and raise compressionLevel_invalid for one made without.
+        dictset with slots (create_dictset; not together with dictionary= or cdict=): a dictionary per frame - frame i is what cdict=
+        the member slots[i] gives it alone, with that member's ID as the header's dictID (int32 device tensor of n elements;
+        DICT_NONE, -1: the plain frame with prefs as they are).  A slot that is no member fails that frame alone.  Levels 3-12 want
+        every non-empty member made with hc=True."""
         if not isinstance(prefs, Preferences):
             raise ValueError("prefs must be a Preferences")
-        if cdict is not None and dictionary is not None:
-            raise ValueError("give dictionary= or cdict=, not both")
+        if (cdict is not None) + (dictionary is not None) + (dictset is not None) > 1:
+            raise ValueError("give dictionary=, cdict= or dictset=, not more than one" if dictset is not None else "give dictionary= or cdict=, not both")
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        if dictset is not None:
+            p = self._check_dictset(dictset, slots, n, [("src", src, torch.uint8)], True)
+            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingDictSet(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
+                                                                           dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(),
+                                                                           dictset.h, p))
+            return
+        if slots is not None:
+            raise ValueError("slots= goes with dictset=")
         if cdict is not None:
             _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingCDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
                                                                          dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(),
