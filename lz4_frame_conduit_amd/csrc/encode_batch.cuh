@@ -17,8 +17,8 @@
 //   k_bc_find_*    the deterministic match finders over the chunk table: solo_find_chunk (encode_solo.cuh, a wave per chunk, levels
 //                  <= 2) or hc_find_chunk (encode_hc.cuh, a workgroup per chunk, levels 3-12) - the very functions the single call's
 //                  kernels run, so a frame's records are what they would be alone
-//                  Two kernels of one signature, k_bc_find_solo<DICT, CDICT> and k_bc_find_hc<DICT>; the call's dictionary reaches
-//                  them as one EncDict (encode.cuh).  k_bc_find_solo<true, false>: the call's shared dictionary in front of every
+//                  Two kernel templates of one signature, k_bc_find_solo<DICT, CDICT, D> and k_bc_find_hc<DICT, D>; the call's
+//                  dictionary reaches them as one EncDict (encode.cuh), D, from which bc_frame_dict gives each chunk its frame's.  k_bc_find_solo<true, false>: the call's shared dictionary in front of every
 //                  low_abs; <true, true>: a prepared dictionary, whose digested table a scope's first chunk copies;
 //                  k_bc_find_hc<true>: levels 3-12 with a prepared dictionary that carries the hash-chain digest
 //   k_bc_layout    a wave per block: layout_block_chunks (pass S's per-block step: carries, raw fallback) -> the size word
@@ -28,8 +28,9 @@
 //   k_bc_blockck   a wave per block: the block checksums (only when asked for)
 //   k_bc_content   a wave per frame: the content checksums, side by side (only when asked for)
 // A set of dictionaries (lz4f_mi355x_dev_compressFrames_usingDictSet, dictset.cuh): frame i has the member its slot names.  Three
-// launches come in a set form - k_bc_head_set (the slot held to the set, kept in BcFrame::pad), k_bc_find_solo_set / k_bc_find_hc_set
-// (the chunk's frame's EncDict from the set's table) and k_bc_frames<W, true> (the member's ID in the header) - the others are shared.
+// launches come in a set form - k_bc_head_set (the slot held to the set, kept in BcFrame::slot), the finders with D = DsView,
+// k_bc_find_solo<true, true, DsView> / k_bc_find_hc<true, DsView> (bc_frame_dict: the chunk's frame's EncDict from the set's table),
+// and k_bc_frames<W, true> (the member's ID in the header) - the others are shared.
 // Nothing is written outside a frame's window on its behalf, and nothing at all unless the whole frame fits it.
 // Limits: no sequence index, no in-band trailer, no block table comes out, and the finders are the deterministic ones only.  A big
 // input of many blocks gets a wave for its layout and one for its content checksum: send it through lz4f_mi355x_dev_compressFrame,
@@ -54,8 +55,9 @@ struct BcFrame {                            // per frame (device workspace, 72 b
     uint64_t rec_at;                        // its first record in the pool (until k_bc_place: how many it needs)
     uint64_t fsize;                         // the frame's bytes (k_bc_frames)
     uint32_t status, n_blocks, n_chunks;
-    uint32_t blk_at, chk_at, pad;           // first block / chunk entry, BC_NONE: none; pad: the set calls' slot (bc_head_body), else 0
+    uint32_t blk_at, chk_at, slot;          // first block / chunk entry, BC_NONE: none; slot: the set calls' slot (bc_head_body), else 0
 };
+static_assert(sizeof(BcFrame) == 72, "BcFrame: 72 bytes");
 struct BcBlk {                              // block table entry (32 bytes)
     uint64_t src, out;                      // the block in d_src; its payload's place in d_dst (k_bc_frames)
     uint32_t blen, word, frame, chk_at;     // input bytes, size word (k_bc_layout), frame, first chunk entry
@@ -81,7 +83,7 @@ __device__ __forceinline__ bool bc_blk_live(const BcFrame* __restrict__ frames, 
     return fi < n_frames && uni(frames[fi].status) == 0 && slice_holds(uni(frames[fi].blk_at), uni(frames[fi].n_blocks), w);
 }
 
-// SET (k_bc_head_set, the set calls): behind the offset checks the frame's slot, slot[i], is held to the set and kept in r.pad - a
+// SET (k_bc_head_set, the set calls): behind the offset checks the frame's slot, slot[i], is held to the set and kept in r.slot - a
 // member, DS_NONE, or DS_UNKNOWN for anything else, which fails the frame (ST_GENERIC: k_bc_frames marks its record)
 template <bool SET>
 __device__ __forceinline__ void bc_head_body(uint64_t src_bytes, const uint64_t* __restrict__ soff, uint64_t dst_bytes,
@@ -92,11 +94,11 @@ __device__ __forceinline__ void bc_head_body(uint64_t src_bytes, const uint64_t*
     if (i >= n_frames) return;
     BcFrame r;
     r.src = 0; r.len = 0; r.dst = 0; r.win = 0; r.rec_at = 0; r.fsize = 0;
-    r.status = 0; r.n_blocks = 0; r.n_chunks = 0; r.blk_at = BC_NONE; r.chk_at = BC_NONE; r.pad = SET ? DS_NONE : 0;
+    r.status = 0; r.n_blocks = 0; r.n_chunks = 0; r.blk_at = BC_NONE; r.chk_at = BC_NONE; r.slot = SET ? DS_NONE : 0;
     const uint64_t s0 = soff[i], s1 = soff[i + 1], d0 = doff[i], d1 = doff[i + 1];
     if (s0 > s1 || s1 > src_bytes) r.status = ST_SRCPTR;                 // nothing is read or written
     else if (d0 > d1 || d1 > dst_bytes) r.status = ST_DSTSMALL;
-    else if (SET && (r.pad = ds_given_slot(slot[i], n_members)) == DS_UNKNOWN) r.status = ST_GENERIC;
+    else if (SET && (r.slot = ds_given_slot(slot[i], n_members)) == DS_UNKNOWN) r.status = ST_GENERIC;
     else {
         r.src = s0; r.len = s1 - s0; r.dst = d0; r.win = d1 - d0;
         const uint64_t nb = (r.len + pf.block_size - 1) / pf.block_size, full = r.len / BC_CHUNK, rem = r.len % BC_CHUNK;
@@ -184,9 +186,30 @@ __device__ __forceinline__ EncPlace bc_place_of(const BcChunk& e)
     return pl;
 }
 
+// The dictionary of a chunk's frame, as the finders below take it (wave-uniform).  Their last argument is the source, D: the call's
+// one EncDict, which is every frame's - or, for a set of dictionaries (lz4f_mi355x_dev_compressFrames_usingDictSet), the set's table,
+// from which the wave (the workgroup) loads its chunk's frame's member by the frame's slot (BcFrame::slot, held to the set by
+// k_bc_head_set) and runs the prepared-dictionary finder with it: solo_find_chunk<true, true> / hc_find_chunk<true>.  Those ask the
+// dictionary for a scope's first chunk only (cs_abs == low_abs) and then load ITS digest over the whole table, or clear the table when
+// the frame has no member or one of fewer than 4 bytes (dc.len < 4: seam 0, the finder runs as without a dictionary) - so a workgroup
+// that strides from a chunk of one member to a chunk of another carries nothing over, as the one-dictionary forms carry nothing from
+// chunk to chunk.  (At levels 3-12 the host lets only hash-chain CDicts in as non-empty members: dc.hc_digest is there when seam is.)
+__device__ __forceinline__ const EncDict& bc_frame_dict(const EncDict& dc, const BcFrame* __restrict__, uint32_t) { return dc; }
+__device__ __forceinline__ EncDict bc_frame_dict(const DsView& set, const BcFrame* __restrict__ frames, uint32_t fi)
+{
+    EncDict dc;
+    const uint32_t s = uni(frames[fi].slot);
+    if (s < set.count) {
+        const DsMember* m = set.members + s;
+        dc.end = (const uint8_t*)uni64((uint64_t)m->end); dc.len = uni(m->len);
+        dc.solo_digest = (const uint4*)uni64((uint64_t)m->solo_digest); dc.hc_digest = (const uint4*)uni64((uint64_t)m->hc_digest);
+    }
+    return dc;
+}
+
 // The deterministic finder of levels <= 2 over the chunk table: a wave per chunk (a one-wave workgroup, as the single call launches it:
-// 11.25 KiB of LDS per wave bound the occupancy).  Its three instantiations (the two finder kernels share one signature, so that the
-// host picks one and launches it: `pf` is k_bc_find_hc's, `dc` is for DICT):
+// 11.25 KiB of LDS per wave bound the occupancy).  Its instantiations (the two finder kernels share one signature, so that the
+// host picks one and launches it: `pf` is k_bc_find_hc's, `dcs` is for DICT):
 //   <false, false>  no dictionary (lz4f_mi355x_dev_compressFrames)
 //   <true, false>   the batch's shared dictionary (lz4f_mi355x_dev_compressFrames_usingDict; it was k_bc_find_solo_dict): the dc.len
 //                   (<= 64 KiB) bytes that end at dc.end lie in front of every chunk's low_abs (solo_find_chunk<true>).  The dictionary
@@ -199,10 +222,11 @@ __device__ __forceinline__ EncPlace bc_place_of(const BcChunk& e)
 //                   cs_abs == low_abs itself and does not lean on that.)  Table and tags are one array here, in the digest's layout;
 //                   the same 11 520 bytes of LDS.  (The other two keep their two arrays: the one-array form costs the plain kernel
 //                   two VGPRs and an SGPR)
-template <bool DICT, bool CDICT>
+//   <true, true, DsView>  a set of prepared dictionaries (it was k_bc_find_solo_set): <true, true> with each chunk's frame's member
+template <bool DICT, bool CDICT, typename D = EncDict>
 __global__ __launch_bounds__(64) void k_bc_find_solo(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
                                                      const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                     ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, EncDict dc)
+                                                     ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, D dcs)
 {
     static_assert(DICT || !CDICT, "a digest is a dictionary's");
     uint16_t* table; uint8_t* tags;
@@ -217,8 +241,10 @@ __global__ __launch_bounds__(64) void k_bc_find_solo(const uint8_t* __restrict__
     const uint32_t total = uni(ctl[0]);
     for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
         const BcChunk e = chunks[w];
-        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
+        const uint32_t fi = uni(e.frame);
+        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
         const EncPlace pl = bc_place_of(e);
+        decltype(auto) dc = bc_frame_dict(dcs, frames, fi);
         solo_find_chunk<DICT, CDICT>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), table, tags, dc);
     }
 }
@@ -228,75 +254,27 @@ __global__ __launch_bounds__(64) void k_bc_find_solo(const uint8_t* __restrict__
 // every independent block's - loads dc.hc_digest (head and chain[0 .. D), k_hc_digest_dict) into the workgroup's LDS where the plain
 // kernel clears head, and walks on from the batch that holds the seam.  All of it is loaded again for every such chunk, so nothing
 // depends on the chunks this workgroup had before; every other chunk has 64 KiB of input in front of it and runs as without DICT.  The
-// same HcShared: the digest needs no LDS of its own
-template <bool DICT>
+// same HcShared: the digest needs no LDS of its own.  <true, DsView> (it was k_bc_find_hc_set): each chunk's frame's member
+template <bool DICT, typename D = EncDict>
 __global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
                                                               const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                              ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, EncDict dc)
+                                                              ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, D dcs)
 {
     __shared__ HcShared sh;
     const uint32_t total = uni(ctl[0]);
     for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
         const BcChunk e = chunks[w];
-        if (!bc_chunk_live(frames, n_frames, uni(e.frame), w)) continue;
+        const uint32_t fi = uni(e.frame);
+        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
         const EncPlace pl = bc_place_of(e);
+        decltype(auto) dc = bc_frame_dict(dcs, frames, fi);
         hc_find_chunk<DICT>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dc);
         __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
     }
 }
-// what the two have in common, for the host
-using BcFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, EncDict);
-
-// THE SET FORMS (lz4f_mi355x_dev_compressFrames_usingDictSet): the dictionary is the chunk's frame's, not the call's.  The wave (the
-// workgroup) loads it for every chunk from the set's table by the frame's slot (BcFrame::pad, held to the set by k_bc_head_set),
-// wave-uniform, and runs the prepared-dictionary finder with it: solo_find_chunk<true, true> / hc_find_chunk<true>.  Those ask the
-// dictionary for a scope's first chunk only (cs_abs == low_abs) and then load ITS digest over the whole table, or clear the table when
-// the frame has no member or one of fewer than 4 bytes (dc.len < 4: seam 0, the finder runs as without a dictionary) - so a workgroup
-// that strides from a chunk of one member to a chunk of another carries nothing over, as the one-dictionary forms carry nothing from
-// chunk to chunk.  (At levels 3-12 the host lets only hash-chain CDicts in as non-empty members: dc.hc_digest is there when seam is.)
-__device__ __forceinline__ EncDict bc_frame_dict(const DsView& set, const BcFrame* __restrict__ frames, uint32_t fi)
-{
-    EncDict dc;
-    const uint32_t s = uni(frames[fi].pad);
-    if (s < set.count) {
-        const DsMember* m = set.members + s;
-        dc.end = (const uint8_t*)uni64((uint64_t)m->end); dc.len = uni(m->len);
-        dc.solo_digest = (const uint4*)uni64((uint64_t)m->solo_digest); dc.hc_digest = (const uint4*)uni64((uint64_t)m->hc_digest);
-    }
-    return dc;
-}
-__global__ __launch_bounds__(64) void k_bc_find_solo_set(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
-                                                         const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                         ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, DsView set)
-{
-    __shared__ uint4 s_dig[SOLO_DIGEST_VEC];
-    const uint32_t total = uni(ctl[0]);
-    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const BcChunk e = chunks[w];
-        const uint32_t fi = uni(e.frame);
-        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
-        const EncPlace pl = bc_place_of(e);
-        const EncDict dc = bc_frame_dict(set, frames, fi);
-        solo_find_chunk<true, true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), solo_digest_table(s_dig), solo_digest_tags(s_dig), dc);
-    }
-}
-__global__ __launch_bounds__(64 * HC_WAVES) void k_bc_find_hc_set(const uint8_t* __restrict__ src, const BcFrame* __restrict__ frames, uint32_t n_frames,
-                                                                  const BcChunk* __restrict__ chunks, const uint32_t* __restrict__ ctl,
-                                                                  ChunkInfo* __restrict__ info, uint64_t* __restrict__ pool, BcPrefs pf, DsView set)
-{
-    __shared__ HcShared sh;
-    const uint32_t total = uni(ctl[0]);
-    for (uint32_t w = blockIdx.x; w < total; w += gridDim.x) {
-        const BcChunk e = chunks[w];
-        const uint32_t fi = uni(e.frame);
-        if (!bc_chunk_live(frames, n_frames, fi, w)) continue;
-        const EncPlace pl = bc_place_of(e);
-        const EncDict dc = bc_frame_dict(set, frames, fi);
-        hc_find_chunk<true>(src, pl, info + w, pool + uni64(e.rec_at), true, uni(e.max_rec), pf.hc_attempts, pf.hc_lazy, sh, dc);
-        __syncthreads();                                                  // (the chunk that had nothing to search left without a barrier)
-    }
-}
-using BcSetFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, DsView);
+// what the two have in common, for the host: the finder of a dictionary source D
+template <typename D>
+using BcFinder = void (*)(const uint8_t*, const BcFrame*, uint32_t, const BcChunk*, const uint32_t*, ChunkInfo*, uint64_t*, BcPrefs, D);
 
 // a wave per block: pass S's per-block step
 template <int W>
@@ -332,7 +310,7 @@ __global__ __launch_bounds__(64 * W) void k_bc_frames(uint8_t* dst, BcFrame* __r
     uint32_t set_id = 0;                                                  // SET: the header's dictID
     if constexpr (SET) {
         set_id = pf.dict_id;
-        const uint32_t s = uni(frames[i].pad);
+        const uint32_t s = uni(frames[i].slot);
         if (s < set.count) set_id = uni(set.members[s].id);
         else if (s != DS_NONE) {
             if (lane == 0) results[i] = ResultRec{0ull, 0ull, (uint32_t)ST_GENERIC, 0u, 0xFFFFFFFFu, (LZ4F_MI355X_PATH_BATCH | LZ4F_MI355X_PATH_DICT_UNKNOWN) << 12};

@@ -985,6 +985,18 @@ static size_t batch_end(const char* call)
     if (hipGetLastError() != hipSuccess) { set_last_error("%s: launch failed", call); return make_err(LZ4F_ERROR_GENERIC); }
     return 0;
 }
+// How a batch entry point opens.  -> true: the call ends here and returns r - no engine, or no frames and nothing to do (batch_idle);
+// its pointers, the device, the aux stream (batch_open).  The set calls judge their set between the two; the compress calls judge
+// their preferences and the level in front of `n == 0` and open for themselves (compress_frames)
+static bool batch_idle(const lz4f_mi355x_engine* e, uint32_t n, size_t& r)
+{
+    r = e ? 0 : make_err(LZ4F_ERROR_GENERIC);
+    return !e || n == 0;
+}
+static bool batch_open(lz4f_mi355x_engine* e, uint32_t n, const char* call, bool pointers_ok, size_t& r)
+{
+    return batch_idle(e, n, r) || (r = batch_begin(e, call, pointers_ok)) != 0;
+}
 // a table's entries, from the call's arguments alone (a slice's place is a 32-bit entry number)
 static uint64_t batch_table_cap(uint32_t n_frames, uint64_t shared)
 {
@@ -1002,6 +1014,12 @@ struct Carve {
     size_t take(size_t bytes, size_t align = 1) { const size_t at = (end + align - 1) & ~(align - 1); end = at + bytes; return at; }
     int ensure() { return buf.ensure(end); }
     template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
+};
+// what the decode and compress entry points pass along unchanged: the frames' spans in d_src and their windows in d_dst
+struct BatchSpans {
+    uint32_t n_frames;
+    const void* d_src; size_t srcBytes; const uint64_t* d_src_off;
+    void* d_dst; size_t dstBytes; const uint64_t* d_dst_off;
 };
 
 // A prepared dictionary (lz4f_mi355x_dev_createCDict / _createCDictHC): its engine's, never written after the stream has run its creation.
@@ -1024,6 +1042,31 @@ struct lz4f_mi355x_dictset {
     void* mem = nullptr;
     std::vector<uint8_t> staged;           // the table as it was uploaded (kept: the copy may read it after createDictSet returned)
 };
+
+// A batch call's dictionary in one value: none (BatchDict{}), one for every frame, or a set with the frames' slots
+struct BatchDict {
+    EncDict one;                           // a raw dictionary's tail (the decoders take just that, DictTail), or a prepared one's with its digests
+    bool hc_ok = false;                    // `one` was made for levels 3-12 (it may still lack one.hc_digest: 1-3 bytes, which the finder ignores)
+    const lz4f_mi355x_dictset* set = nullptr;      // frame i with the member d_slot[i] names, or (the decoder, d_slot NULL) its header
+    const uint32_t* d_slot = nullptr;
+    bool any() const { return set || one.len; }                       // (which members the frames name is known on the device only)
+    bool serves_hc() const { return set ? set->all_hc : hc_ok; }      // levels 3-12: only with the hash-chain digest, every member of a set
+};
+
+// The finder kernel of a batch (encode_batch.cuh) and the most workgroups it gets: by the level, and by what the dictionary brings
+template <typename D> struct BcFind { BcFinder<D> kernel; uint32_t most_wgs, threads; };
+static BcFind<EncDict> bc_finder(bool hc, const EncDict& dc)
+{
+    // (levels 3-12 without the digest: no dictionary, or a prepared one of 1-3 bytes, which the finder ignores)
+    if (hc) return {dc.len && dc.hc_digest ? k_bc_find_hc<true> : k_bc_find_hc<false>, BATCH_GRID / 4, 64 * HC_WAVES};
+    return {!dc.len ? k_bc_find_solo<false, false> : dc.solo_digest ? k_bc_find_solo<true, true> : k_bc_find_solo<true, false>, BATCH_GRID * 2, 64};
+}
+// (a set: the prepared-dictionary finders with each chunk's frame's member, the same grids)
+static BcFind<DsView> bc_finder(bool hc, const DsView&)
+{
+    if (hc) return {k_bc_find_hc<true, DsView>, BATCH_GRID / 4, 64 * HC_WAVES};
+    return {k_bc_find_solo<true, true, DsView>, BATCH_GRID * 2, 64};
+}
 
 extern "C" {
 
@@ -1225,75 +1268,70 @@ static DictTail batch_dict_tail(const void* d_dict, size_t dictSize)
     return t;
 }
 
-// `set` (with d_slot, which may be NULL): a set of dictionaries where d_dict / dictSize give one, each frame with the member its slot
-// or its header names (lz4f_mi355x_dev_decompressFrames_usingDictSet)
-static size_t decompress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
-                                void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results,
-                                const void* d_dict, size_t dictSize, const lz4f_mi355x_dictset* set = nullptr, const uint32_t* d_slot = nullptr)
+// `dict`: none, the call's one dictionary (its tail is all the decoders take), or a set, each frame with the member its slot or its
+// header names (lz4f_mi355x_dev_decompressFrames_usingDictSet; d_slot may be NULL)
+static size_t decompress_frames(lz4f_mi355x_engine* e, const BatchSpans& sp, lz4f_mi355x_result* d_results, const BatchDict& dict)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    const DictTail dc = batch_dict_tail(d_dict, dictSize);
-    if (const size_t r = batch_begin(e, "dev_decompressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len))) return r;
+    const uint32_t n_frames = sp.n_frames;
+    const DictTail& dc = dict.one;
+    size_t r;
+    if (batch_open(e, n_frames, "dev_decompressFrames", sp.d_src && sp.d_src_off && sp.d_dst && sp.d_dst_off && d_results && (dc.end || !dc.len), r)) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // the block table: a frame of full blocks never needs more than window / 64 KiB + 1 entries, so this bound needs nothing read back
-    const uint64_t table_cap = batch_table_cap(n_frames, dstBytes / BF_SHARE);
+    const uint64_t table_cap = batch_table_cap(n_frames, sp.dstBytes / BF_SHARE);
     Carve ws{e->bframes};
     const size_t frames_at = ws.take((size_t)n_frames * sizeof(BatchFrame)), counts_at = ws.take((size_t)n_frames * 4), ctl_at = ws.take(256, 256);
-    const size_t slots_at = set ? ws.take((size_t)n_frames * 4, 4) : 0;          // (the set call's own: the frames' resolved slots)
+    const size_t slots_at = dict.set ? ws.take((size_t)n_frames * 4, 4) : 0;     // (the set call's own: the frames' resolved slots)
     if (ws.ensure() || e->btable.ensure((size_t)table_cap * sizeof(BatchBlk))) return make_err(LZ4F_ERROR_allocation_failed);
     BatchFrame* frames = ws.at<BatchFrame>(frames_at);
     uint32_t* counts = ws.at<uint32_t>(counts_at);
     uint32_t* ctl = ws.at<uint32_t>(ctl_at);
     BatchBlk* table = (BatchBlk*)e->btable.p;
-    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
+    const uint8_t* src = (const uint8_t*)sp.d_src; uint8_t* dst = (uint8_t*)sp.d_dst;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
-    if (set) {                                                         // the same six launches in their BF_SET form
-        BfSet bs; (DsView&)bs = set->view; bs.slot = ws.at<uint32_t>(slots_at);
-        hipLaunchKernelGGL(k_bf_head<true>, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts,
-                           BfHeadSet<true>{set->view, d_slot, ws.at<uint32_t>(slots_at)});
+    // the six launches in the form F (the decoders' DICT): `hs` is the head kernel's set argument, `dcs` the decoders' dictionary
+    auto launch = [&](auto form, auto hs, auto dcs) {
+        constexpr int F = decltype(form)::value;
+        hipLaunchKernelGGL(k_bf_head<F == BF_SET>, dim3(g256), dim3(256), 0, st, src, (uint64_t)sp.srcBytes, sp.d_src_off, (uint64_t)sp.dstBytes, sp.d_dst_off,
+                           n_frames, frames, counts, hs);
         hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
         hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
-        hipLaunchKernelGGL((k_bf_blocks<W, BF_SET>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table,
-                           (const uint32_t*)ctl, bs);
-        hipLaunchKernelGGL((k_bf_serial<W, BF_SET>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, bs);
-        hipLaunchKernelGGL((k_bf_finish<W, BF_SET>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
-                           e->sw.no_content_check ? 0u : 1u, bs);
+        hipLaunchKernelGGL((k_bf_blocks<W, F>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames, n_frames, table,
+                           (const uint32_t*)ctl, dcs);
+        hipLaunchKernelGGL((k_bf_serial<W, F>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, dcs);
+        hipLaunchKernelGGL((k_bf_finish<W, F>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table, (ResultRec*)d_results,
+                           e->sw.no_content_check ? 0u : 1u, dcs);
+    };
+    if (dict.set) {
+        uint32_t* slots = ws.at<uint32_t>(slots_at);
+        launch(std::integral_constant<int, BF_SET>{}, BfHeadSet<true>{dict.set->view, dict.d_slot, slots}, BfSet{dict.set->view, slots});
         return batch_end("dev_decompressFrames_usingDictSet");
     }
-    hipLaunchKernelGGL(k_bf_head<false>, dim3(g256), dim3(256), 0, st, src, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, frames, counts,
-                       BfHeadSet<false>{});
-    hipLaunchKernelGGL(k_batch_place<BatchFrame>, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, n_frames, frames, table_cap, ctl);
-    hipLaunchKernelGGL(k_bf_table, dim3(g256), dim3(256), 0, st, src, (const BatchFrame*)frames, n_frames, table);
     // (a dictionary: the DICT instantiations, every block through the scalar-parse decoder)
-    const bool dict = dc.len != 0;
-    hipLaunchKernelGGL((dict ? k_bf_blocks<W, true> : k_bf_blocks<W, false>), batch_grid(table_cap, W), dim3(64 * W), 0, st, src, dst, (const BatchFrame*)frames,
-                       n_frames, table, (const uint32_t*)ctl, dc);
-    hipLaunchKernelGGL((dict ? k_bf_serial<W, true> : k_bf_serial<W, false>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, dc);
-    hipLaunchKernelGGL((dict ? k_bf_finish<W, true> : k_bf_finish<W, false>), dim3(gw), dim3(64 * W), 0, st, src, dst, frames, n_frames, (const BatchBlk*)table,
-                       (ResultRec*)d_results, e->sw.no_content_check ? 0u : 1u, dc);
+    if (dc.len) launch(std::integral_constant<int, 1>{}, BfHeadSet<false>{}, dc);
+    else launch(std::integral_constant<int, 0>{}, BfHeadSet<false>{}, dc);
     return batch_end("dev_decompressFrames");
 }
 
 size_t lz4f_mi355x_dev_decompressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                         void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
 {
-    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, nullptr, 0);
+    return decompress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, d_results, BatchDict{});
 }
 size_t lz4f_mi355x_dev_decompressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                   void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, lz4f_mi355x_result* d_results,
                                                   const void* d_dict, size_t dictSize)
 {
-    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, d_dict, dictSize);
+    return decompress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, d_results,
+                             BatchDict{EncDict{batch_dict_tail(d_dict, dictSize)}});
 }
 
 size_t lz4f_mi355x_dev_measureFrames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                      uint64_t* d_dst_off, lz4f_mi355x_result* d_results)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_measureFrames", d_src && d_src_off && d_results)) return r;
+    size_t r;
+    if (batch_open(e, n_frames, "dev_measureFrames", d_src && d_src_off && d_results, r)) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // the block table: sized from the call's arguments alone; frames behind an overflow are measured a wave per frame
     const uint64_t table_cap = batch_table_cap(n_frames, srcBytes / MF_SHARE);
@@ -1324,9 +1362,8 @@ size_t lz4f_mi355x_dev_packFrames(lz4f_mi355x_engine* e, uint32_t n_frames, cons
                                   const lz4f_mi355x_result* d_results, void* d_dst, size_t dstBytes, uint64_t* d_dst_off,
                                   unsigned flags, lz4f_mi355x_result* d_pack)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_packFrames", d_src && d_src_off && d_results && d_dst && d_dst_off)) return r;
+    size_t r;
+    if (batch_open(e, n_frames, "dev_packFrames", d_src && d_src_off && d_results && d_dst && d_dst_off, r)) return r;
     const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
     if (srcBytes && dstBytes && s0 < d0 + dstBytes && d0 < s0 + srcBytes) { set_last_error("dev_packFrames: d_dst overlaps d_src"); return make_err(LZ4F_ERROR_GENERIC); }
     if (e->pctl.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
@@ -1343,9 +1380,8 @@ size_t lz4f_mi355x_dev_packFrames(lz4f_mi355x_engine* e, uint32_t n_frames, cons
 size_t lz4f_mi355x_dev_readPackDirectory(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_pack, size_t packBytes, uint64_t* d_src_off,
                                          lz4f_mi355x_result* d_result)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_readPackDirectory", d_pack && d_src_off)) return r;
+    size_t r;
+    if (batch_open(e, n_frames, "dev_readPackDirectory", d_pack && d_src_off, r)) return r;
     hipLaunchKernelGGL(k_pk_readdir, dim3(1), dim3(1024), 0, (hipStream_t)e->stream, (const uint8_t*)d_pack, (uint64_t)packBytes, n_frames, d_src_off,
                        (ResultRec*)d_result);
     return batch_end("dev_readPackDirectory");
@@ -1369,9 +1405,8 @@ static uint32_t sp_rounds(uint64_t cap)
 size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e, const void* d_src, size_t srcBytes, uint32_t max_frames, uint64_t* d_src_off,
                                    lz4f_mi355x_result* d_split)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (max_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_splitFrames", d_src && d_src_off)) return r;
+    size_t r;
+    if (batch_open(e, max_frames, "dev_splitFrames", d_src && d_src_off, r)) return r;
     hipStream_t st = (hipStream_t)e->stream;
     const uint8_t* src = (const uint8_t*)d_src;
     if (e->sw.split_serial) {
@@ -1407,35 +1442,30 @@ size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e, const void* d_src, siz
     return batch_end("dev_splitFrames");
 }
 
-// The finder kernel of a batch (encode_batch.cuh) and the most workgroups it gets: by the level, and by what the dictionary brings
-struct BcFind { BcFinder kernel; uint32_t most_wgs, threads; };
-static BcFind bc_finder(bool hc, const EncDict& dc)
-{
-    // (levels 3-12 without the digest: no dictionary, or a prepared one of 1-3 bytes, which the finder ignores)
-    if (hc) return BcFind{dc.len && dc.hc_digest ? k_bc_find_hc<true> : k_bc_find_hc<false>, BATCH_GRID / 4, 64 * HC_WAVES};
-    return BcFind{!dc.len ? k_bc_find_solo<false, false> : dc.solo_digest ? k_bc_find_solo<true, true> : k_bc_find_solo<true, false>, BATCH_GRID * 2, 64};
-}
-
-// `dc`: the call's dictionary (EncDict{}: none) - a raw one's tail, or a prepared one's with its digests.  `dict_hc`: it is a prepared
-// one made for levels 3-12 (which may still come without dc.hc_digest: fewer than 4 bytes, which the finder ignores)
-// `set` (with d_slot): a set of dictionaries where `dc` gives one, frame i with the member d_slot[i] names
-// (lz4f_mi355x_dev_compressFrames_usingDictSet, which has checked the set against the level)
-static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
-                              void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
-                              lz4f_mi355x_result* d_results, const EncDict& dc, bool dict_hc,
-                              const lz4f_mi355x_dictset* set = nullptr, const uint32_t* d_slot = nullptr)
+// `dict`: the call's dictionary - none, one (a raw one's tail, or a prepared one's with its digests), or a set, frame i with the
+// member d_slot[i] names (lz4f_mi355x_dev_compressFrames_usingDictSet)
+static size_t compress_frames(lz4f_mi355x_engine* e, const BatchSpans& sp, const LZ4F_preferences_t* prefs, lz4f_mi355x_result* d_results,
+                              const BatchDict& dict)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    const uint32_t n_frames = sp.n_frames;
     LZ4F_preferences_t p; size_t bs;
-    if (const size_t r = resolve_prefs(prefs, p, bs)) return r;
+    const size_t bad_prefs = resolve_prefs(prefs, p, bs);
+    // Of a level the dictionary does not serve and a block size that does not exist, the one-dictionary calls report the block size,
+    // the set call the level: it always judged its set against the level in front of the preferences
+    if (bad_prefs && !dict.set) return bad_prefs;
     // (levels 3-12 take a dictionary only with the hash-chain digest: seeding a raw one costs up to 69 barrier rounds in front of
     // every chunk.  Nothing is enqueued)
-    if (dc.len && p.compressionLevel >= 3 && !dict_hc) {
-        set_last_error("dev_compressFrames_usingDict: levels 3-12 take a dictionary only as a CDict of dev_createCDictHC");
+    if (dict.any() && p.compressionLevel >= 3 && !dict.serves_hc()) {
+        set_last_error(dict.set ? "dev_compressFrames_usingDictSet: levels 3-12 take only members made by dev_createCDictHC"
+                                : "dev_compressFrames_usingDict: levels 3-12 take a dictionary only as a CDict of dev_createCDictHC");
         return make_err(LZ4F_ERROR_compressionLevel_invalid);
     }
+    if (bad_prefs) return bad_prefs;
     if (n_frames == 0) return 0;
-    if (const size_t r = batch_begin(e, "dev_compressFrames", d_src && d_src_off && d_dst && d_dst_off && d_results && (dc.end || !dc.len) && (d_slot || !set))) return r;
+    const EncDict& dc = dict.one;
+    if (const size_t r = batch_begin(e, "dev_compressFrames", sp.d_src && sp.d_src_off && sp.d_dst && sp.d_dst_off && d_results && (dc.end || !dc.len) &&
+                                                              (dict.d_slot || !dict.set))) return r;
     hipStream_t st = (hipStream_t)e->stream;
     // what the frames have in common; the header is each frame's own (k_bc_frames: frame_head_write with its content size)
     const LZ4F_frameInfo_t& f = p.frameInfo;
@@ -1446,8 +1476,8 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     if (hc) { const HcLevel hl = hc_level_of(p.compressionLevel, e->sw); pf.hc_attempts = hl.attempts; pf.hc_lazy = hl.lazy; }
     // the tables and the pool, from the call's arguments alone: chunks are 64 KiB whatever the block size (pick_chunk_size), so spans
     // that do not overlap have at most n_frames + srcBytes / 64 KiB chunks, no more blocks, and a record per 4 bytes + one per chunk
-    const uint64_t cap = batch_table_cap(n_frames, srcBytes / BC_CHUNK);
-    const uint64_t rec_cap = (uint64_t)srcBytes / 4 + cap;
+    const uint64_t cap = batch_table_cap(n_frames, sp.srcBytes / BC_CHUNK);
+    const uint64_t rec_cap = (uint64_t)sp.srcBytes / 4 + cap;
     Carve ws{e->cframes};
     const size_t frames_at = ws.take((size_t)n_frames * sizeof(BcFrame)), ctl_at = ws.take(256, 256);
     const size_t recs_had = e->recs.cap;
@@ -1464,40 +1494,35 @@ static size_t compress_frames(lz4f_mi355x_engine* e, uint32_t n_frames, const vo
     // call's per-chunk list offsets (rec_offs) and `info`: both are a call's own - every single-call finder writes the offset and the
     // ChunkInfo of every chunk it later reads before anything reads them, and nothing is carried from one call to the next.
     uint64_t* pool = (uint64_t*)e->recs.p + 8;
-    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dst = (uint8_t*)d_dst;
+    const uint8_t* src = (const uint8_t*)sp.d_src; uint8_t* dst = (uint8_t*)sp.d_dst;
     constexpr int W = 4;
     const uint32_t g256 = (n_frames + 255) / 256, gw = (n_frames + W - 1) / W;
     const dim3 g_ent = batch_grid(cap, W);                             // (a wave per entry, striding over the entries in use)
-    const BcFind find = bc_finder(hc, dc);                             // (the set forms: the same grids)
-    if (set) {                                                         // head, finder and header writer in their set forms
-        hipLaunchKernelGGL(k_bc_head_set, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames,
-                           d_slot, set->view.count);
+    // the launches, for a dictionary source D (the finders' last argument): `head` with its set arguments, and k_bc_frames' set argument
+    auto launch = [&](const auto& dcs, auto fs, auto head, auto... head_set) {
+        constexpr bool SET = std::is_same<decltype(fs), BcFramesSet<true>>::value;
+        const auto find = bc_finder(hc, dcs);
+        hipLaunchKernelGGL(head, dim3(g256), dim3(256), 0, st, (uint64_t)sp.srcBytes, sp.d_src_off, (uint64_t)sp.dstBytes, sp.d_dst_off, n_frames, pf, frames,
+                           head_set...);
         hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
         hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
-        const BcSetFinder sfind = hc ? k_bc_find_hc_set : k_bc_find_solo_set;
-        hipLaunchKernelGGL(sfind, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
-                           (const uint32_t*)ctl, info, pool, pf, set->view);
+        hipLaunchKernelGGL(find.kernel, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
+                           (const uint32_t*)ctl, info, pool, pf, dcs);
         hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
-        BcFramesSet<true> fs; (DsView&)fs = set->view;
-        hipLaunchKernelGGL((k_bc_frames<W, true>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results, fs);
-    } else {
-    hipLaunchKernelGGL(k_bc_head, dim3(g256), dim3(256), 0, st, (uint64_t)srcBytes, d_src_off, (uint64_t)dstBytes, d_dst_off, n_frames, pf, frames);
-    hipLaunchKernelGGL(k_bc_place, dim3(1), dim3(1024), 0, st, frames, n_frames, cap, cap, rec_cap, ctl);
-    hipLaunchKernelGGL((k_bc_table<W>), dim3(gw), dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, pf, blocks, chunks);
-    hipLaunchKernelGGL(find.kernel, batch_grid(cap, 1, find.most_wgs), dim3(find.threads), 0, st, src, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks,
-                       (const uint32_t*)ctl, info, pool, pf, dc);
-    hipLaunchKernelGGL((k_bc_layout<W>), g_ent, dim3(64 * W), 0, st, (const BcFrame*)frames, n_frames, blocks, (const uint32_t*)ctl, info);
-    hipLaunchKernelGGL((k_bc_frames<W, false>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results, BcFramesSet<false>{});
-    }
-    hipLaunchKernelGGL((k_bc_emit<W>), g_ent, dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
-                       (const ChunkInfo*)info, (const uint64_t*)pool);
-    if (pf.block_checksum) {
-        if (bs > (256u << 10))                                         // (few big blocks: the four-lane chain, as the single call's k_xxh32_blocks4)
-            hipLaunchKernelGGL((k_bc_blockck<W, true>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
-        else
-            hipLaunchKernelGGL((k_bc_blockck<W, false>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
-    }
-    if (pf.content_checksum) hipLaunchKernelGGL((k_bc_content<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames);
+        hipLaunchKernelGGL((k_bc_frames<W, SET>), dim3(gw), dim3(64 * W), 0, st, dst, frames, n_frames, pf, blocks, info, (ResultRec*)d_results, fs);
+        hipLaunchKernelGGL((k_bc_emit<W>), g_ent, dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames, (const BcChunk*)chunks, (const uint32_t*)ctl,
+                           (const ChunkInfo*)info, (const uint64_t*)pool);
+        if (pf.block_checksum) {
+            if (bs > (256u << 10))                                     // (few big blocks: the four-lane chain, as the single call's k_xxh32_blocks4)
+                hipLaunchKernelGGL((k_bc_blockck<W, true>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+            else
+                hipLaunchKernelGGL((k_bc_blockck<W, false>), g_ent, dim3(64 * W), 0, st, dst, (const BcFrame*)frames, n_frames, (const BcBlk*)blocks, (const uint32_t*)ctl);
+        }
+        if (pf.content_checksum) hipLaunchKernelGGL((k_bc_content<W>), dim3(gw), dim3(64 * W), 0, st, src, dst, (const BcFrame*)frames, n_frames);
+    };
+    // (a set: head, finder and header writer in their set forms)
+    if (dict.set) launch(dict.set->view, BcFramesSet<true>{dict.set->view}, k_bc_head_set, dict.d_slot, dict.set->view.count);
+    else launch(dc, BcFramesSet<false>{}, k_bc_head);
     return batch_end("dev_compressFrames");
 }
 
@@ -1505,13 +1530,14 @@ size_t lz4f_mi355x_dev_compressFrames(lz4f_mi355x_engine* e, uint32_t n_frames, 
                                       void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
                                       lz4f_mi355x_result* d_results)
 {
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false);
+    return compress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, prefs, d_results, BatchDict{});
 }
 size_t lz4f_mi355x_dev_compressFrames_usingDict(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                                 void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
                                                 lz4f_mi355x_result* d_results, const void* d_dict, size_t dictSize)
 {
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{batch_dict_tail(d_dict, dictSize)}, false);
+    return compress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, prefs, d_results,
+                           BatchDict{EncDict{batch_dict_tail(d_dict, dictSize)}});
 }
 
 // ---- the prepared dictionary: the dictionary's last 64 KiB, owned, and the finder's table seeded from them once (createCDictHC: the
@@ -1568,16 +1594,23 @@ size_t lz4f_mi355x_dev_createCDictHC(lz4f_mi355x_engine* e, lz4f_mi355x_cdict** 
 }
 int lz4f_mi355x_cdict_has_hc(const lz4f_mi355x_cdict* c) { return c && c->hc ? 1 : 0; }
 
+// a device allocation that kernels on its engine's stream may still read goes: the stream's work first, then the memory (which goes
+// even when the wait failed).  `who`: the call's name in the message
+static size_t free_behind_stream(const lz4f_mi355x_engine* e, void* mem, const char* who)
+{
+    if (!mem) return 0;                                                    // (an empty one owns nothing and has nothing in flight)
+    size_t r = 0;
+    if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize((hipStream_t)e->stream) != hipSuccess) {
+        (void)hipGetLastError(); set_last_error("%s: waiting for the engine's stream failed", who); r = make_err(LZ4F_ERROR_GENERIC);
+    }
+    (void)hipFree(mem);
+    return r;
+}
+
 size_t lz4f_mi355x_dev_freeCDict(lz4f_mi355x_cdict* c)
 {
     if (!c) return 0;
-    size_t r = 0;
-    if (c->mem) {                                                          // (an empty one owns nothing and has nothing in flight)
-        if (hipSetDevice(c->engine->device) != hipSuccess || hipStreamSynchronize((hipStream_t)c->engine->stream) != hipSuccess) {
-            (void)hipGetLastError(); set_last_error("dev_freeCDict: waiting for the engine's stream failed"); r = make_err(LZ4F_ERROR_GENERIC);
-        }
-        (void)hipFree(c->mem);
-    }
+    const size_t r = free_behind_stream(c->engine, c->mem, "dev_freeCDict");
     delete c;
     return r;
 }
@@ -1593,12 +1626,13 @@ size_t lz4f_mi355x_dev_compressFrames_usingCDict(lz4f_mi355x_engine* e, uint32_t
                                                  lz4f_mi355x_result* d_results, const lz4f_mi355x_cdict* cdict)
 {
     if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (!cdict || !cdict->dict.len) return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false);
+    const BatchSpans sp{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off};
+    if (!cdict || !cdict->dict.len) return compress_frames(e, sp, prefs, d_results, BatchDict{});
     if (cdict->engine != e) { set_last_error("dev_compressFrames_usingCDict: cdict belongs to another engine"); return make_err(LZ4F_ERROR_GENERIC); }
     // (a dictionary of 1-3 bytes: the finder ignores it, its digest is the cleared table - the _usingDict kernel, as that call launches it)
     EncDict dc = cdict->dict;
     if (dc.len < 4) dc.solo_digest = dc.hc_digest = nullptr;
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, dc, cdict->hc);
+    return compress_frames(e, sp, prefs, d_results, BatchDict{dc, cdict->hc});
 }
 
 // ---- a set of prepared dictionaries: one chosen per frame, by slot or by the header's dictID (dictset.cuh) ----
@@ -1667,13 +1701,7 @@ size_t lz4f_mi355x_dev_createDictSet(lz4f_mi355x_engine* e, lz4f_mi355x_dictset*
 size_t lz4f_mi355x_dev_freeDictSet(lz4f_mi355x_dictset* s)
 {
     if (!s) return 0;
-    size_t r = 0;
-    if (s->mem) {                                                          // (an empty one owns nothing and has nothing in flight)
-        if (hipSetDevice(s->engine->device) != hipSuccess || hipStreamSynchronize((hipStream_t)s->engine->stream) != hipSuccess) {
-            (void)hipGetLastError(); set_last_error("dev_freeDictSet: waiting for the engine's stream failed"); r = make_err(LZ4F_ERROR_GENERIC);
-        }
-        (void)hipFree(s->mem);
-    }
+    const size_t r = free_behind_stream(s->engine, s->mem, "dev_freeDictSet");
     delete s;
     return r;
 }
@@ -1691,10 +1719,9 @@ static size_t check_dictset(const lz4f_mi355x_engine* e, const lz4f_mi355x_dicts
 size_t lz4f_mi355x_dev_resolveDictIDs(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
                                       const lz4f_mi355x_dictset* set, uint32_t* d_slot)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = check_dictset(e, set, "dev_resolveDictIDs")) return r;
-    if (const size_t r = batch_begin(e, "dev_resolveDictIDs", d_src && d_src_off && d_slot)) return r;
+    size_t r;
+    if (batch_idle(e, n_frames, r) || (r = check_dictset(e, set, "dev_resolveDictIDs")) != 0) return r;
+    if ((r = batch_begin(e, "dev_resolveDictIDs", d_src && d_src_off && d_slot)) != 0) return r;
     hipLaunchKernelGGL(k_ds_resolve, dim3((n_frames + 255) / 256), dim3(256), 0, (hipStream_t)e->stream, (const uint8_t*)d_src, (uint64_t)srcBytes, d_src_off,
                        n_frames, set->view, d_slot);
     return batch_end("dev_resolveDictIDs");
@@ -1704,25 +1731,19 @@ size_t lz4f_mi355x_dev_compressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32
                                                    void* d_dst, size_t dstBytes, const uint64_t* d_dst_off, const LZ4F_preferences_t* prefs,
                                                    lz4f_mi355x_result* d_results, const lz4f_mi355x_dictset* set, const uint32_t* d_slot)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = check_dictset(e, set, "dev_compressFrames_usingDictSet")) return r;
-    // (which members the frames name is known on the device only: the rule of levels 3-12 holds for every member.  Nothing is enqueued)
-    if (prefs && prefs->compressionLevel >= 3 && !set->all_hc) {
-        set_last_error("dev_compressFrames_usingDictSet: levels 3-12 take only members made by dev_createCDictHC");
-        return make_err(LZ4F_ERROR_compressionLevel_invalid);
-    }
-    return compress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, prefs, d_results, EncDict{}, false, set, d_slot);
+    // (a set call of no frames returns before its set, its preferences and the level are looked at; the one-dictionary calls judge theirs first)
+    size_t r;
+    if (batch_idle(e, n_frames, r) || (r = check_dictset(e, set, "dev_compressFrames_usingDictSet")) != 0) return r;
+    return compress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, prefs, d_results, BatchDict{EncDict{}, false, set, d_slot});
 }
 
 size_t lz4f_mi355x_dev_decompressFrames_usingDictSet(lz4f_mi355x_engine* e, uint32_t n_frames, const void* d_src, size_t srcBytes,
                                                      const uint64_t* d_src_off, void* d_dst, size_t dstBytes, const uint64_t* d_dst_off,
                                                      lz4f_mi355x_result* d_results, const lz4f_mi355x_dictset* set, const uint32_t* d_slot)
 {
-    if (!e) return make_err(LZ4F_ERROR_GENERIC);
-    if (n_frames == 0) return 0;
-    if (const size_t r = check_dictset(e, set, "dev_decompressFrames_usingDictSet")) return r;
-    return decompress_frames(e, n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off, d_results, nullptr, 0, set, d_slot);
+    size_t r;
+    if (batch_idle(e, n_frames, r) || (r = check_dictset(e, set, "dev_decompressFrames_usingDictSet")) != 0) return r;
+    return decompress_frames(e, BatchSpans{n_frames, d_src, srcBytes, d_src_off, d_dst, dstBytes, d_dst_off}, d_results, BatchDict{EncDict{}, false, set, d_slot});
 }
 
 size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off, const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out)

@@ -448,25 +448,21 @@ class Engine:
         dictID field: none).  A slot or an ID that is no member fails that frame alone (ERROR_GENERIC, PATH_DICT_UNKNOWN in its
         record's path bits) and leaves its window untouched."""
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        call, tail = self.L.lz4f_mi355x_dev_decompressFrames, ()
         if dictset is not None:
             if dictionary is not None:
                 raise ValueError("give dictionary= or dictset=, not both")
             p = self._check_dictset(dictset, slots, n, [("src", src, torch.uint8)], False)
-            _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames_usingDictSet(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
-                                                                             dst.numel(), dst_off.data_ptr(), results.data_ptr(), dictset.h, p))
-            return
-        if slots is not None:
+            call, tail = self.L.lz4f_mi355x_dev_decompressFrames_usingDictSet, (dictset.h, p)
+        elif slots is not None:
             raise ValueError("slots= goes with dictset=")
-        if dictionary is not None:
+        elif dictionary is not None:
+            call = self.L.lz4f_mi355x_dev_decompressFrames_usingDict
             if isinstance(dictionary, CDict):
-                d_ptr, d_len = self._check_cdict(dictionary).data_ptr, dictionary.size
+                tail = (self._check_cdict(dictionary).data_ptr, dictionary.size)
             else:
-                d_ptr, d_len = self._check_dictionary(dictionary)
-            _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
-                                                                          dst.numel(), dst_off.data_ptr(), results.data_ptr(), d_ptr, d_len))
-            return
-        _chk(self.L, self.L.lz4f_mi355x_dev_decompressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
-                                                            dst_off.data_ptr(), results.data_ptr()))
+                tail = self._check_dictionary(dictionary)
+        _chk(self.L, call(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(), dst_off.data_ptr(), results.data_ptr(), *tail))
 
     def measure_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, results: torch.Tensor, dst_off: "torch.Tensor | None" = None):
         """Enqueue a measurement: what frame i, the first frame in src[src_off[i]:src_off[i+1]], decodes to - its size from the tokens,
@@ -509,26 +505,18 @@ class Engine:
         if (cdict is not None) + (dictionary is not None) + (dictset is not None) > 1:
             raise ValueError("give dictionary=, cdict= or dictset=, not more than one" if dictset is not None else "give dictionary= or cdict=, not both")
         n = _check_batch_args(src, src_off, dst, dst_off, results, self.RESULT_BYTES)
+        call, tail = self.L.lz4f_mi355x_dev_compressFrames, ()
         if dictset is not None:
             p = self._check_dictset(dictset, slots, n, [("src", src, torch.uint8)], True)
-            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingDictSet(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
-                                                                           dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(),
-                                                                           dictset.h, p))
-            return
-        if slots is not None:
+            call, tail = self.L.lz4f_mi355x_dev_compressFrames_usingDictSet, (dictset.h, p)
+        elif slots is not None:
             raise ValueError("slots= goes with dictset=")
-        if cdict is not None:
-            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingCDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
-                                                                         dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(),
-                                                                         self._check_cdict(cdict).h))
-            return
-        if dictionary is not None:
-            d_ptr, d_len = self._check_dictionary(dictionary)
-            _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames_usingDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(),
-                                                                        dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr(), d_ptr, d_len))
-            return
-        _chk(self.L, self.L.lz4f_mi355x_dev_compressFrames(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(),
-                                                          dst_off.data_ptr(), ctypes.byref(prefs), results.data_ptr()))
+        elif cdict is not None:
+            call, tail = self.L.lz4f_mi355x_dev_compressFrames_usingCDict, (self._check_cdict(cdict).h,)
+        elif dictionary is not None:
+            call, tail = self.L.lz4f_mi355x_dev_compressFrames_usingDict, self._check_dictionary(dictionary)
+        _chk(self.L, call(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dst.data_ptr(), dst.numel(), dst_off.data_ptr(), ctypes.byref(prefs),
+                          results.data_ptr(), *tail))
 
     def pack_frames_async(self, src: torch.Tensor, src_off: torch.Tensor, results: torch.Tensor, dst: torch.Tensor, dst_off: torch.Tensor,
                           directory: bool = False, record: "torch.Tensor | None" = None):
