@@ -264,6 +264,30 @@ typedef struct {
     uint32_t flags;       /* decoded FLG byte (decompress) */
 } lz4f_mi355x_result;
 
+/* WHICH FLAW DECIDES.  A frame with more than one flaw gets the verdict of the first of them in this order, from every one-shot
+ * call - lz4f_mi355x_decompressFrame, lz4f_mi355x_dev_decompressFrame under every switch, lz4f_mi355x_dev_decompressBlocks and the
+ * batch calls lz4f_mi355x_dev_decompressFrames[_usingDict / _usingDictSet] (tests/flaw_pairs.py: one_shot_verdict is this paragraph
+ * in Python; tests/test_gpu_flaw_pairs.py holds the calls to it on frames with two flaws):
+ *   1. the span and the offsets (batch calls: ERROR_srcPtr_wrong, ERROR_dstMaxSize_tooSmall);
+ *   2. the header;
+ *   3. the walk over ALL the size words, before any block is looked at: per block in frame order a size word above maxBlockSize
+ *      (ERROR_maxBlockSize_invalid), a span that ends inside the word, the payload or the block checksum
+ *      (ERROR_frameHeader_incomplete), and - device-pointer calls, linked frames too - a block whose provisional place,
+ *      b * maxBlockSize, lies outside the window (ERROR_dstMaxSize_tooSmall); behind the EndMark the content checksum's word
+ *      (ERROR_frameHeader_incomplete).  first_bad_block stays 0xFFFFFFFF.  So a bad size word or a truncation ANYWHERE in the frame
+ *      beats a block that does not decode in front of it - where liblz4, which meets the blocks one by one, names that block;
+ *   4. the blocks in order, in each block its checksum (ERROR_blockChecksum_invalid) before its decode (ERROR_GENERIC; or
+ *      ERROR_dstMaxSize_tooSmall where the block decodes but not into the room the window leaves it): first_bad_block is that
+ *      block - the first one, with one stated exception: for a malformed LINKED frame lz4f_mi355x_dev_decompressFrame and
+ *      lz4f_mi355x_dev_decompressBlocks may name a later block of the same frame, with the same status (the batch calls name
+ *      the first).  lz4f_mi355x_decompressFrame puts the blocks back to back and wants each to fit what is left of dst;
+ *      lz4f_mi355x_dev_decompressBlocks has no level 3, 5 or 6: the table is the caller's;
+ *   5. the content size (ERROR_frameSize_wrong);
+ *   6. the content checksum (ERROR_contentChecksum_invalid).
+ * lz4f_mi355x_dev_measureFrames keeps the same order over what it looks at (no checksum, no window).  The LZ4F_* streaming calls of
+ * PART 1 and the conduits are drop-ins and have no order of their own: their answer is liblz4's, which is "the first flaw a
+ * sequential reader meets" (tests/golden/flaw_pairs.json records it). */
+
 /* Block table entry: where block i lives in the frame and in the output. */
 typedef struct {
     uint64_t src_off;     /* offset of the payload (after the 4-byte size word) in the frame */

@@ -338,18 +338,21 @@ void decompressBatched(const Await& await, const Yield& yield, size_t batchBytes
         const size_t max_block = block_size_of(fi.blockSizeID);
         // runs of whole blocks
         size_t run = 0;                                                    // bytes of whole blocks behind `off`
+        auto decode_run = [&] { if (run) { handleLz4Error(lz4f_mi355x_fdec_blocks(dec.d, to_yield, &ctx, buf.data() + off, run)); off += run; run = 0; } };
+        // (The walk runs ahead of the decode, and liblz4 meets the blocks in order: where the walk ends on a bad size word or on the
+        // stream's end, the whole blocks in front of it are decoded first - a flaw of theirs is the verdict, as it is liblz4's.)
         for (;;) {
-            if (!ensure(run + 4)) throw std::runtime_error("lz4 decompress error: stream ended before EndMark");
+            if (!ensure(run + 4)) { decode_run(); throw std::runtime_error("lz4 decompress error: stream ended before EndMark"); }
             const uint32_t w = le32(run);
             if (is_endmark(w)) break;
             const size_t csz = word_size(w);
-            if (csz > max_block) handleLz4Error(make_err(LZ4F_ERROR_maxBlockSize_invalid));
+            if (csz > max_block) { decode_run(); handleLz4Error(make_err(LZ4F_ERROR_maxBlockSize_invalid)); }
             const size_t step = 4 + csz + crc;
-            if (!ensure(run + step)) throw std::runtime_error("lz4 decompress error: stream ended before EndMark");
+            if (!ensure(run + step)) { decode_run(); throw std::runtime_error("lz4 decompress error: stream ended before EndMark"); }
             run += step;
-            if (run >= batchBytes) { handleLz4Error(lz4f_mi355x_fdec_blocks(dec.d, to_yield, &ctx, buf.data() + off, run)); off += run; run = 0; }
+            if (run >= batchBytes) decode_run();
         }
-        if (run) { handleLz4Error(lz4f_mi355x_fdec_blocks(dec.d, to_yield, &ctx, buf.data() + off, run)); off += run; }
+        decode_run();
         const size_t tail = 4 + (fi.contentChecksumFlag ? 4 : 0);
         if (!ensure(tail)) throw std::runtime_error("lz4 decompress error: stream ended before EndMark");
         handleLz4Error(lz4f_mi355x_fdec_end(dec.d, buf.data() + off, tail));

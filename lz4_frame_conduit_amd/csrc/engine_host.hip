@@ -200,7 +200,7 @@ static DecodeStaging decode_staging(bool one_up, bool src_pinned, size_t tbytes,
 
 size_t lz4f_mi355x_engine::slab_decode(const uint8_t* frame_part, size_t part_len, const std::vector<lz4f_mi355x_block>& entries,
                                        const ParsedHeader& ph, const uint8_t* hist, size_t hist_len, bool src_pinned, size_t* got,
-                                       uint8_t* fetch_to, size_t fetch_room)
+                                       uint8_t* fetch_to, size_t fetch_room, uint32_t* bad_block)
 {   // fetch_to (one small block): the output comes back with the result record, before the ONE synchronisation of the call - a block's
     // worth is copied whatever the block decodes to, and what it did decode to goes to fetch_to
     HIP_TRY(hipSetDevice(device));
@@ -245,7 +245,10 @@ size_t lz4f_mi355x_engine::slab_decode(const uint8_t* frame_part, size_t part_le
     if (with_out) HIP_TRY(hipMemcpyAsync(h_out.p, j.d_dst, ph.max_block, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(hr, res.p, sizeof(ResultRec), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (hr->status != ST_OK) { set_last_error("device decode status %u at block %u", hr->status, hr->first_bad_block); return make_err((int)hr->status); }
+    if (hr->status != ST_OK) {
+        if (bad_block) *bad_block = hr->first_bad_block;
+        set_last_error("device decode status %u at block %u", hr->status, hr->first_bad_block); return make_err((int)hr->status);
+    }
     *got = hr->size;
     if (fetch_to) {
         if (hr->size > fetch_room) return make_err(LZ4F_ERROR_dstMaxSize_tooSmall);

@@ -170,6 +170,9 @@ size_t pipe_decompress_frame(const uint8_t* s, size_t n, const ParsedHeader& ph,
         sl.count++; sl.src_len = pos - sl.src_at;
     }
     if (endmark) pos += 4;
+    // (the walk takes in the content checksum's word, as the device calls' walk does: a span that ends in front of it is
+    // frameHeader_incomplete before any block is decoded - lz4f_mi355x.h, WHICH FLAW DECIDES)
+    if (!carry && ph.info.contentChecksumFlag && !frame_word_fits(n - pos)) return make_err(LZ4F_ERROR_frameHeader_incomplete);
     const size_t nslab = slabs.size();
     const bool src_pinned = is_pinned_host(s), dst_pinned = flat && is_pinned_host(flat);
     Xxh32State cck_here; cck_here.reset(0);
@@ -200,9 +203,26 @@ size_t pipe_decompress_frame(const uint8_t* s, size_t n, const ParsedHeader& ph,
                     if (flat) { hl = std::min(turns.offset, (size_t)65536); hist = flat + turns.offset - hl; }
                     else { hl = hist_keep.size(); hist = hist_keep.data(); }
                 }
-                size_t got = 0;
-                size_t rr = e->slab_decode(s + sl.src_at, sl.src_len, ent, ph, hist, hl, src_pinned, &got);
-                if (is_err(rr)) { errs[slot] = last_error(); turns.fail(rr); return; }
+                size_t got = 0; uint32_t bad = 0xFFFFFFFFu;
+                size_t rr = e->slab_decode(s + sl.src_at, sl.src_len, ent, ph, hist, hl, src_pinned, &got, nullptr, 0, &bad);
+                if (is_err(rr)) {
+                    errs[slot] = last_error();
+                    // The blocks in order (lz4f_mi355x.h, WHICH FLAW DECIDES): the blocks in front of the bad one come first, and where
+                    // they do not fit the caller's buffer, that is the verdict.  What they decode to is found by decoding them alone
+                    // (a failed call only); should one of THEM fail - a linked frame's kernels may have named a later block - it is
+                    // the earlier flaw, and the question goes to the blocks in front of it.
+                    if (flat && turns.enter(k)) {
+                        while (bad != 0xFFFFFFFFu && bad > 0 && bad < ent.size()) {
+                            const std::vector<lz4f_mi355x_block> front(ent.begin(), ent.begin() + bad);
+                            size_t fits = 0; uint32_t bad2 = 0xFFFFFFFFu;
+                            const size_t r2 = e->slab_decode(s + sl.src_at, sl.src_len, front, ph, hist, hl, src_pinned, &fits, nullptr, 0, &bad2);
+                            if (!is_err(r2)) { if (turns.offset + fits > flat_cap) rr = make_err(LZ4F_ERROR_dstMaxSize_tooSmall); break; }
+                            if (bad2 >= bad) break;
+                            rr = r2; errs[slot] = last_error(); bad = bad2;
+                        }
+                    }
+                    turns.fail(rr); return;
+                }
                 if (!turns.enter(k)) return;
                 const size_t at = turns.offset;
                 if (flat) {
