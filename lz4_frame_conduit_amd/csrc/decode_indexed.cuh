@@ -38,10 +38,10 @@
 namespace lz4f {
 
 // The index header is checked on the device (no host round trip on this path): usable at all, made for this geometry, its
-// tables inside the buffer the caller named, its sequences inside the descriptor workspace the engine has.  flags[0] != 0
-// sends the call to the generic decoder; flags[8] / flags[9] carry the entry and sequence counts to the kernels behind.
+// tables inside the buffer the caller named, its sequences inside the descriptor workspace the engine has.  ctl->gave_up != 0
+// sends the call to the generic decoder; ctl->n_entries / ctl->n_seqs carry the entry and sequence counts to the kernels behind.
 __global__ void k_check_index(const void* __restrict__ ix, uint64_t ix_size, uint32_t n_max, uint32_t chunks_per_block, uint32_t chunk_size,
-                              uint64_t seq_cap, uint32_t* __restrict__ flags, const ResultRec* __restrict__ res = nullptr)
+                              uint64_t seq_cap, IxCtl* __restrict__ ctl, const ResultRec* __restrict__ res = nullptr)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     // the index is laid out for the frame's block count: the walk's (res), of which the host knows an upper bound (its own
@@ -52,10 +52,10 @@ __global__ void k_check_index(const void* __restrict__ ix, uint64_t ix_size, uin
                     hd.total_entries <= (uint64_t)n_blocks * chunks_per_block * ix_max_entries_per_chunk(chunk_size) &&
                     hd.total_seqs <= (uint64_t)hd.total_entries * (IX_STRIDE + 1) && hd.total_seqs <= seq_cap &&
                     ix_entries_at(n_blocks, chunks_per_block) + (uint64_t)hd.total_entries * sizeof(IxEntry) <= ix_size;
-    flags[7] = n_blocks;
-    flags[8] = ok ? hd.total_entries : 0u;
-    flags[9] = ok ? hd.total_seqs : 0u;
-    if (!ok) atomicOr(flags, 1u);
+    ctl->n_blocks = n_blocks;
+    ctl->n_entries = ok ? hd.total_entries : 0u;
+    ctl->n_seqs = ok ? hd.total_seqs : 0u;
+    if (!ok) atomicOr(&ctl->gave_up, IX_UNUSABLE);
 }
 
 // The index's block table, judged for the whole grid before any kernel behind writes a descriptor or an output byte: a lane per
@@ -65,13 +65,13 @@ __global__ void k_check_index(const void* __restrict__ ix, uint64_t ix_size, uin
 // copy kernels check their own block's links as well; those verdicts come too late to stop a neighbour's writes (a table that
 // breaks one link and shifts every block behind it would send those workgroups' descriptors past the workspace).
 __global__ __launch_bounds__(256) void k_check_blocks(const void* __restrict__ ix, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
-                                                      uint32_t n_max, uint32_t* __restrict__ flags)
+                                                      uint32_t n_max, IxCtl* __restrict__ ctl)
 {
-    if (res->status != ST_OK || *flags) return;                          // (k_check_index refused the header: nothing behind reads the table)
+    if (res->status != ST_OK || ctl->gave_up) return;                          // (k_check_index refused the header: nothing behind reads the table)
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n) return;
-    const uint64_t n_seqs = flags[9], n_entries = flags[8];
+    const uint64_t n_seqs = ctl->n_seqs, n_entries = ctl->n_entries;
     const IxBlock* blocks = ix_blocks(ix);
     const IxBlock bk = blocks[b];
     const bool stored = (table[b].word >> 31) != 0;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_check_blocks(const void* __restrict__ i
     if (b == 0) wrong |= bk.seq_base != 0 || bk.entry_base != 0;
     if (b + 1 < n) { const IxBlock nb = blocks[b + 1]; wrong |= nb.seq_base != seq_end || nb.entry_base != ent_end; }
     else wrong |= seq_end != n_seqs || ent_end != n_entries;
-    if (wrong) atomicOr(flags, 1u);
+    if (wrong) atomicOr(&ctl->gave_up, IX_UNUSABLE);
 }
 
 // `my_nseq` sequences of the payload in[0, csize) from `pos` on (output position `op`): their descriptors -> out[0 .. my_nseq).
@@ -173,13 +173,13 @@ __device__ __forceinline__ bool parse_run(const uint8_t* __restrict__ in, uint32
 }
 
 // k_parse_indexed, one lane per index entry.  (The index structures and k_build_index live in encode.cuh: pass E2 writes the entries.)
-// Input-side rules only (the feeder wave checks the ones that need output positions).  `flags[0]` is set when anything
+// Input-side rules only (the feeder wave checks the ones that need output positions).  `ctl->gave_up` is set when anything
 // disagrees with the index: the caller then falls back to the generic decoder.  Every entry must end exactly where the next
 // one starts and the first one of a block at payload byte 0, so the descriptors are a complete parse of the payload itself:
 // a wrong index can make the call fall back, never change the bytes that come out.
 __device__ __forceinline__ void parse_entry(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                             const void* __restrict__ ix, uint32_t n_blocks, uint32_t n_entries,
-                                            SeqDesc* __restrict__ desc, uint64_t desc_cap, uint32_t* __restrict__ flags, uint32_t gid, uint32_t linked, uint64_t hist0)
+                                            SeqDesc* __restrict__ desc, uint64_t desc_cap, IxCtl* __restrict__ ctl, uint32_t gid, uint32_t linked, uint64_t hist0)
 {
     const IxBlock* blocks = ix_blocks(ix);
     if (gid < n_blocks) {
@@ -192,19 +192,19 @@ __device__ __forceinline__ void parse_entry(const uint8_t* __restrict__ frame, u
         const uint64_t seq_end = (uint64_t)bk.seq_base + bk.nseq, ent_end = (uint64_t)bk.entry_base + bk.nentries;
         if (gid + 1 < n_blocks) wrong |= blocks[gid + 1].seq_base != seq_end || blocks[gid + 1].entry_base != ent_end;
         else wrong |= seq_end != desc_cap || ent_end != n_entries;
-        if (wrong) atomicOr(flags, 1u);
+        if (wrong) atomicOr(&ctl->gave_up, IX_UNUSABLE);
     }
     if (gid >= n_entries) return;
     const IxEntry* entries = ix_entries(ix, n_blocks);
     const IxEntry me = entries[gid];
     const uint32_t b = me.nseq_blk >> 8, my_nseq = me.nseq_blk & 0xFFu;
-    if (b >= n_blocks) { atomicOr(flags, 1u); return; }
+    if (b >= n_blocks) { atomicOr(&ctl->gave_up, IX_UNUSABLE); return; }
     const IxBlock blk = blocks[b];
     const BlockOut e = table[b];
     const uint32_t csize = e.word & 0x7FFFFFFFu;
     bool bad = (e.word >> 31) != 0 || e.src_off + csize > frame_cap || me.in_off >= csize || my_nseq == 0 || gid < blk.entry_base ||
                gid >= blk.entry_base + blk.nentries || (uint64_t)me.seq_off + my_nseq > blk.nseq || (uint64_t)blk.seq_base + blk.nseq > desc_cap;
-    if (bad) { atomicOr(flags, 1u); return; }
+    if (bad) { atomicOr(&ctl->gave_up, IX_UNUSABLE); return; }
     const bool is_head = gid == blk.entry_base, is_tail = gid + 1 == blk.entry_base + blk.nentries;
     const uint32_t stop = is_tail ? csize : entries[gid + 1].in_off;           // where the next entry of this block starts (or the payload ends)
     if (is_head && (me.in_off != 0 || me.out_pos != 0 || me.seq_off != 0)) bad = true;      // the entries must cover the payload from its first byte
@@ -216,7 +216,7 @@ __device__ __forceinline__ void parse_entry(const uint8_t* __restrict__ frame, u
     uint32_t pos = me.in_off;
     if (!bad) bad = parse_run(in, csize, readable, pos, me.out_pos, my_nseq, is_tail, out, linked, e.dst_off + hist0);
     if (!bad && pos != stop) bad = true;                                       // must end exactly where the next entry starts
-    if (bad) atomicOr(flags, 1u);
+    if (bad) atomicOr(&ctl->gave_up, IX_UNUSABLE);
 }
 
 // The rules that need the room (liblz4's: maxBlockSize, whatever the caller gives) on the descriptors k_parse_indexed / k_spx_parse
@@ -225,9 +225,9 @@ __device__ __forceinline__ void parse_entry(const uint8_t* __restrict__ frame, u
 // gave up (the generic decoders, which check the rules themselves, decoded then).
 __global__ __launch_bounds__(256) void k_check_tails(BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
                                                      const void* __restrict__ ix, const SeqDesc* __restrict__ desc, uint64_t desc_cap,
-                                                     uint32_t block_size, const uint32_t* __restrict__ flags)
+                                                     uint32_t block_size, const IxCtl* __restrict__ ctl)
 {
-    if (res->status != ST_OK || *flags) return;
+    if (res->status != ST_OK || ctl->gave_up) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n || (table[b].word >> 31)) return;
@@ -240,15 +240,15 @@ __global__ __launch_bounds__(256) void k_check_tails(BlockOut* __restrict__ tabl
 
 __global__ __launch_bounds__(256) void k_parse_indexed(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                        const void* __restrict__ ix, uint32_t n_max,
-                                                       SeqDesc* __restrict__ desc, uint32_t* __restrict__ flags, uint32_t linked, uint64_t hist0)
+                                                       SeqDesc* __restrict__ desc, IxCtl* __restrict__ ctl, uint32_t linked, uint64_t hist0)
 {
-    if (*flags) return;
-    const uint32_t n_blocks = flags[7] < n_max ? flags[7] : n_max;      // (k_check_index: the frame's block count)
-    const uint32_t n_entries = flags[8];
-    const uint64_t desc_cap = flags[9];
+    if (ctl->gave_up) return;
+    const uint32_t n_blocks = ctl->n_blocks < n_max ? ctl->n_blocks : n_max;      // (k_check_index: the frame's block count)
+    const uint32_t n_entries = ctl->n_entries;
+    const uint64_t desc_cap = ctl->n_seqs;
     const uint32_t n_lanes = n_entries > n_blocks ? n_entries : n_blocks;
     for (uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x; gid < n_lanes; gid += gridDim.x * blockDim.x)
-        parse_entry(frame, frame_cap, table, ix, n_blocks, n_entries, desc, desc_cap, flags, gid, linked, hist0);
+        parse_entry(frame, frame_cap, table, ix, n_blocks, n_entries, desc, desc_cap, ctl, gid, linked, hist0);
 }
 
 
@@ -259,15 +259,15 @@ __global__ __launch_bounds__(256) void k_parse_indexed(const uint8_t* __restrict
 // every block its place) to write an entry every IX_STRIDE sequences - and the frame goes through the same kernels as
 // one with the compressor's index (k_parse_indexed checks every entry against the payload as usual).  A lane walks at memory
 // latency (~1.5 us per sequence), all blocks at once: 0.2 ms for 64 KiB blocks of 1 KiB sequences, ~12 ms for 4 MiB blocks.
-// MODE 0: count (cnt[b], osz[b]); MODE 1: write the entries.  Anything odd sets flags[0]: the generic kernels then decode
+// MODE 0: count (cnt[b], osz[b]); MODE 1: write the entries.  Anything odd sets ctl->gave_up: the generic kernels then decode
 // the frame and give the verdict.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_selfindex_walk(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                         const ResultRec* __restrict__ res, uint32_t n_max, uint32_t* __restrict__ cnt,
-                                                        uint32_t* __restrict__ osz, void* __restrict__ ix, uint32_t* __restrict__ flags,
+                                                        uint32_t* __restrict__ osz, void* __restrict__ ix, IxCtl* __restrict__ ctl,
                                                         const uint32_t* __restrict__ only_if = nullptr)
 {
-    if (res->status != ST_OK || (MODE == 1 && *flags)) return;
+    if (res->status != ST_OK || (MODE == 1 && ctl->gave_up)) return;
     if (only_if && *only_if == 0) return;                                // (k_density_probe: dense payloads go to k_selfindex_walk_wave)
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void k_selfindex_walk(const uint8_t* __restric
     const BlockOut e = table[b];
     const uint32_t csize = e.word & 0x7FFFFFFFu;
     if (e.word >> 31) { if (MODE == 0) { cnt[b] = 0; osz[b] = csize; } return; }
-    if (csize == 0 || e.src_off + csize > frame_cap) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
+    if (csize == 0 || e.src_off + csize > frame_cap) { atomicOr(&ctl->gave_up, IX_UNUSABLE); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
     const uint8_t* in = frame + e.src_off;
     const uint64_t readable = frame_cap - e.src_off;
     IxEntry* ent = nullptr;
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void k_selfindex_walk(const uint8_t* __restric
         op += lit + mlen + 4;
         if (op > (1u << 23)) { bad = true; break; }
     }
-    if (bad || (MODE == 1 && k != total)) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
+    if (bad || (MODE == 1 && k != total)) { atomicOr(&ctl->gave_up, IX_UNUSABLE); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
     if (MODE == 0) { cnt[b] = k; osz[b] = op; }
 }
 
@@ -318,10 +318,10 @@ __global__ __launch_bounds__(256) void k_selfindex_walk(const uint8_t* __restric
 template <int MODE, int WAVES_PER_WG>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_selfindex_walk_wave(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                                            const ResultRec* __restrict__ res, uint32_t n_max, uint32_t* __restrict__ cnt,
-                                                                           uint32_t* __restrict__ osz, void* __restrict__ ix, uint32_t* __restrict__ flags,
+                                                                           uint32_t* __restrict__ osz, void* __restrict__ ix, IxCtl* __restrict__ ctl,
                                                                            const uint32_t* __restrict__ only_if = nullptr)
 {
-    if (res->status != ST_OK || (MODE == 1 && *flags)) return;
+    if (res->status != ST_OK || (MODE == 1 && ctl->gave_up)) return;
     if (only_if && *only_if == 0) return;                                // (k_density_probe: sparse payloads go to k_selfindex_walk, a lane per block)
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = uni(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6)), lane = lane_id();
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_selfindex_walk_wave(const
     const BlockOut e = table[b];
     const uint32_t csize = e.word & 0x7FFFFFFFu;
     if (e.word >> 31) { if (MODE == 0) { cnt[b] = 0; osz[b] = csize; } return; }
-    if (csize == 0 || e.src_off + csize > frame_cap) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
+    if (csize == 0 || e.src_off + csize > frame_cap) { atomicOr(&ctl->gave_up, IX_UNUSABLE); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
     const uint8_t* in = frame + e.src_off;
     const uint64_t readable = frame_cap - e.src_off;
     IxEntry* ent = nullptr;
@@ -383,26 +383,26 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_selfindex_walk_wave(const
         pos = c.pos;
         if (op > (1u << 23)) { bad = true; break; }
     }
-    if (bad || (MODE == 1 && k != total)) { atomicOr(flags, 1u); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
+    if (bad || (MODE == 1 && k != total)) { atomicOr(&ctl->gave_up, IX_UNUSABLE); if (MODE == 0) { cnt[b] = 0; osz[b] = 0; } return; }
     if (MODE == 0) { cnt[b] = k; osz[b] = op; }
 }
 
 // One workgroup: exclusive scans over the blocks (sequences, entries, output bytes) -> the index's block table and header,
-// and every block's place in the output.  flags[8] / flags[9] get the totals (the host reads them to size the workspaces).
+// and every block's place in the output.  ctl->n_entries / ctl->n_seqs get the totals (the host reads them to size the workspaces).
 __global__ __launch_bounds__(1024) void k_selfindex_scan(BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
                                                          const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ osz, void* __restrict__ ix,
-                                                         uint32_t chunks_per_block, uint64_t dst_cap, uint32_t block_size, uint32_t* __restrict__ flags,
+                                                         uint32_t chunks_per_block, uint64_t dst_cap, uint32_t block_size, IxCtl* __restrict__ ctl,
                                                          uint32_t strict = 0)
 {
     __shared__ uint64_t s_a[1024], s_b[1024], s_c[1024];
     __shared__ uint64_t c_a, c_b, c_c;
     if (res->status != ST_OK) return;
-    if (strict && *flags) return;                                        // (independent blocks: the table stays what the generic decoder needs)
+    if (strict && ctl->gave_up) return;                                        // (independent blocks: the table stays what the generic decoder needs)
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t t = threadIdx.x;
     IxBlock* blocks = ix_blocks(ix);
     // A thread takes K consecutive blocks.  First it only JUDGES while it sums them up: a block that decodes to more than block_size, a short block inside
-    // the frame, an output that does not fit dst_cap, counts beyond 32 bits - any of these raises flags[0] and nothing is written, so the table the generic
+    // the frame, an output that does not fit dst_cap, counts beyond 32 bits - any of these raises ctl->gave_up and nothing is written, so the table the generic
     // decoders fall back on keeps the walk's capacity-clamped entries (a payload's claimed sizes never reach them).  Only a clean verdict lets it go over
     // its blocks again and write the index's block table and every block's place in the output.  (Round 4: one scan over the 1024 threads' sums between the
     // two; until then a scan per 1024 blocks and per pass - 133 us for the 16384 blocks of a GiB in 64 KiB blocks, the longest step of a foreign linked
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(1024) void k_selfindex_scan(BlockOut* __restrict__ 
         odd |= vc > block_size || (b + 1 < n && vc != block_size);          // (short blocks inside a frame: the generic kernels)
         la += va; lb += (va + IX_STRIDE - 1) / IX_STRIDE; lc += vc;
     }
-    if (odd) atomicOr(flags, 1u);
+    if (odd) atomicOr(&ctl->gave_up, IX_UNUSABLE);
     s_a[t] = la; s_b[t] = lb; s_c[t] = lc;
     __syncthreads();
     for (uint32_t off = 1; off < 1024; off <<= 1) {
@@ -427,11 +427,11 @@ __global__ __launch_bounds__(1024) void k_selfindex_scan(BlockOut* __restrict__ 
     }
     if (t == 1023) {
         c_a = s_a[1023]; c_b = s_b[1023]; c_c = s_c[1023];
-        if (c_c > dst_cap || c_a >= (1ull << 32) || c_b >= (1ull << 32)) atomicOr(flags, 1u);
+        if (c_c > dst_cap || c_a >= (1ull << 32) || c_b >= (1ull << 32)) atomicOr(&ctl->gave_up, IX_UNUSABLE);
     }
     __threadfence_block();
     __syncthreads();
-    if (__hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;      // (uniform: every thread reads the word behind the barrier)
+    if (__hip_atomic_load(&ctl->gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;      // (uniform: every thread reads the word behind the barrier)
     {
         uint64_t ea = s_a[t] - la, eb = s_b[t] - lb, ec = s_c[t] - lc;      // what the blocks in front of mine add up to
         for (uint32_t b = b0; b < b1; b++) {
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(1024) void k_selfindex_scan(BlockOut* __restrict__ 
     }
     if (t == 0) {
         *(IxHeader*)ix = IxHeader{IX_MAGIC, n, chunks_per_block, (uint32_t)c_a, (uint32_t)c_b, IX_STRIDE, 1u, 0u};
-        flags[8] = (uint32_t)c_b; flags[9] = (uint32_t)c_a;
+        ctl->n_entries = (uint32_t)c_b; ctl->n_seqs = (uint32_t)c_a;
     }
 }
 
@@ -455,28 +455,24 @@ __global__ __launch_bounds__(1024) void k_selfindex_scan(BlockOut* __restrict__ 
 // a few hops at most.  Anything else (a source that straddles two runs, run-length matches) stays a match for the chain.
 // The descriptors are only read here; the answer goes to dsrc[i] (IX_NOT_DIRECT = none) and the feeder wave merges it in.
 constexpr uint32_t IXR_HOPS = 6;
-constexpr uint32_t IXL_PUB = 8;                                // set-aside destinations a block publishes for the block behind (more: that one waits for all of it)
 constexpr uint32_t IX_NOT_DIRECT = 0xFFFFFFFFu;
 // In a linked frame the source may start in the block before (offsets reach 64 KiB back): the search then runs over that
 // block's descriptors - or, if that block is stored, its payload IS its output.  The answer is the payload position
 // relative to the asking block's payload (negative for the block before) + IX_SRC_BIAS.
-constexpr uint32_t IXT_FLAG = 24;                               // flags[IXT_FLAG] != 0: a dense frame, decoded by the tracers below (2: decided before k_resolve_direct, which was skipped)
 constexpr uint32_t IXT_SAMPLE_ALL = 256;                         // frames of up to this many blocks count every block's first workgroup
-constexpr uint32_t IXT_CHAIN = 32;                               // flags[32..63]: matches left on the chain (striped; summed into flags[10] by the gate)
-constexpr uint32_t IXT_DECIDED = 25;                            // flags[IXT_DECIDED]: what the gate decided (kept for the host: the next call's hint)
 // a tracer gives up (too deep, or something inconsistent).  If the resolved sources exist (gate value 1) the copier workgroups
 // launched behind take the frame - they check everything themselves; otherwise the generic kernels do
-__device__ __forceinline__ void ixt_fail(uint32_t* flags)
+__device__ __forceinline__ void ixt_fail(IxCtl* ctl)
 {
-    if (__hip_atomic_load(flags + IXT_FLAG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2u) atomicOr(flags, 2u);
-    else __hip_atomic_store(flags + IXT_FLAG, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__hip_atomic_load(&ctl->dense, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 2u) atomicOr(&ctl->gave_up, IX_COPY_FAILED);
+    else __hip_atomic_store(&ctl->dense, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __global__ __launch_bounds__(256) void k_resolve_direct(void* __restrict__ ix, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
                                                         uint32_t n_max, const SeqDesc* __restrict__ desc, uint32_t* __restrict__ dsrc,
-                                                        uint32_t* __restrict__ flags, uint32_t count_it, uint32_t linked)
+                                                        IxCtl* __restrict__ ctl, uint32_t count_it, uint32_t linked)
 {
-    if (res->status != ST_OK || *flags || flags[IXT_FLAG]) return;      // (dense by the early gate: nobody will ask for the resolved sources)
-    const uint64_t desc_cap = flags[9];
+    if (res->status != ST_OK || ctl->gave_up || ctl->dense) return;      // (dense by the early gate: nobody will ask for the resolved sources)
+    const uint64_t desc_cap = ctl->n_seqs;
     const uint32_t b = blockIdx.x;                             // (gridDim.y workgroups per block)
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     if (b >= n) return;
@@ -503,7 +499,7 @@ __global__ __launch_bounds__(256) void k_resolve_direct(void* __restrict__ ix, c
                         cb--;
                         const BlockOut pe = table[cb];
                         s0 += pe.dst_size;
-                        if (s0 < 0) { if (count_it & 1u) atomicAdd(flags + 12, 1u); break; }                      // further back than one block: leave it to the chain
+                        if (s0 < 0) { if (count_it & 1u) atomicAdd(&ctl->why_far, 1u); break; }                      // further back than one block: leave it to the chain
                         pay = (int64_t)pe.src_off - (int64_t)my_pay;
                         if (pe.word >> 31) {                    // stored: output position == payload position
                             if ((uint64_t)s0 + ml <= pe.dst_size) { const int64_t v = pay + s0 + IX_SRC_BIAS; if (v >= 0 && v < (1 << 23)) found = (uint32_t)v; }
@@ -528,20 +524,20 @@ __global__ __launch_bounds__(256) void k_resolve_direct(void* __restrict__ ix, c
                         if (v >= 0 && v < (1 << 23)) found = (uint32_t)v;
                         break;
                     }
-                    if (key < dmj || (uint64_t)key + ml > (uint64_t)dmj + mlj) { if (count_it & 1u) atomicAdd(flags + 13, 1u); break; }                              // straddles
+                    if (key < dmj || (uint64_t)key + ml > (uint64_t)dmj + mlj) { if (count_it & 1u) atomicAdd(&ctl->why_straddle, 1u); break; }                              // straddles
                     if (dj.w >> 31) {                                                                              // in a direct match (marked by the parse)
                         const int64_t v = pay + (int64_t)(fj | (((dj.w >> 24) & 0x7Fu) << 16)) + (key - dmj);      // (already biased)
                         if (v >= 0 && v < (1 << 23)) found = (uint32_t)v;
                         break;
                     }
-                    if (fj == 0 || mlj > fj) { if (count_it & 1u) atomicAdd(flags + 14, 1u); break; }                                                                // in a run-length match
-                    if ((count_it & 1u) && hop + 1 == IXR_HOPS) atomicAdd(flags + 15, 1u);
+                    if (fj == 0 || mlj > fj) { if (count_it & 1u) atomicAdd(&ctl->why_runlen, 1u); break; }                                                                // in a run-length match
+                    if ((count_it & 1u) && hop + 1 == IXR_HOPS) atomicAdd(&ctl->why_hops, 1u);
                     s0 -= fj; hi = lo;                                                                             // in a plain match: follow it (possibly into the block before)
                 }
             }
-            if (count_it & 1u) atomicAdd(flags + (found != IX_NOT_DIRECT ? 5 : 6), 1u);
-            if ((count_it & 1u) && linked && found == IX_NOT_DIRECT && off > dm) atomicAdd(flags + 11, 1u);
-        } else if ((count_it & 1u) && ml) atomicAdd(flags + 4, 1u);
+            if (count_it & 1u) atomicAdd(found != IX_NOT_DIRECT ? &ctl->m_resolved : &ctl->m_chain, 1u);
+            if ((count_it & 1u) && linked && found == IX_NOT_DIRECT && off > dm) atomicAdd(&ctl->m_reach_front, 1u);
+        } else if ((count_it & 1u) && ml) atomicAdd(&ctl->m_direct, 1u);
         chain_mine += (ml != 0 && !(d.w >> 31) && found == IX_NOT_DIRECT) ? 1u : 0u;      // how long is the chain that stays?
         dsrc[blk.seq_base + i] = found;
     }
@@ -550,7 +546,7 @@ __global__ __launch_bounds__(256) void k_resolve_direct(void* __restrict__ ix, c
         // (a SAMPLE: the first of the gridDim.y workgroups of a block, of every eighth block when there are many - the gate scales it up;
         // an atomic from every wave of the grid cost the headline 0.14 ms)
         const bool sampled = blockIdx.y == 0 && (n <= IXT_SAMPLE_ALL || (b & 7u) == 0);
-        if (sampled && (threadIdx.x & 63u) == 0 && chain_mine) atomicAdd(flags + IXT_CHAIN + ((b * 4 + (threadIdx.x >> 6)) & 31u), chain_mine);
+        if (sampled && (threadIdx.x & 63u) == 0 && chain_mine) atomicAdd(ctl->chain + ((b * 4 + (threadIdx.x >> 6)) & 31u), chain_mine);
     }
 }
 
@@ -568,41 +564,41 @@ constexpr uint32_t IXT_MAX_HOPS = 4096;                         // then the fram
 
 // early != 0: before k_resolve_direct, from the sequence density alone (under 20 output bytes per sequence: text) - such a
 // frame goes to the doubling kernels, which do not need the resolved sources, so k_resolve_direct is skipped (flag value 2)
-__global__ void k_dense_gate(uint32_t* __restrict__ flags, uint32_t on, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max, uint32_t early, uint32_t resolve_gy)
+__global__ void k_dense_gate(IxCtl* __restrict__ ctl, uint32_t on, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max, uint32_t early, uint32_t resolve_gy)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (early) {
         uint32_t v = 0;
-        if (on && !*flags && res->status == ST_OK) {
+        if (on && !ctl->gave_up && res->status == ST_OK) {
             const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
             const uint64_t total = n ? table[n - 1].dst_off + table[n - 1].dst_size : 0;
-            if ((uint64_t)flags[9] * 20 > total) v = 2u;
+            if ((uint64_t)ctl->n_seqs * 20 > total) v = 2u;
         }
-        flags[IXT_FLAG] = v; flags[IXT_DECIDED] = v;
+        ctl->dense = ctl->dense_decided = v;
         return;
     }
-    if (flags[IXT_FLAG]) return;
+    if (ctl->dense) return;
     uint64_t chain = 0;
-    for (uint32_t q = 0; q < 32; q++) chain += flags[IXT_CHAIN + q];
+    for (uint32_t q = 0; q < 32; q++) chain += ctl->chain[q];
     const uint32_t nb = res->n_blocks < n_max ? res->n_blocks : n_max;
     chain *= (uint64_t)resolve_gy * (nb <= IXT_SAMPLE_ALL ? 1u : 8u);             // (k_resolve_direct counted a sample)
-    flags[10] = chain > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)chain;
-    const bool dense = !*flags && chain * 2 > flags[9];
-    flags[IXT_FLAG] = (on && !*flags && (on > 1 || dense)) ? 1u : 0u;
-    flags[IXT_DECIDED] = dense || flags[IXT_FLAG];             // (also when the tracers were not on offer this time: the host's hint for the next call)
+    ctl->chain_total = chain > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)chain;
+    const bool dense = !ctl->gave_up && chain * 2 > ctl->n_seqs;
+    ctl->dense = (on && !ctl->gave_up && (on > 1 || dense)) ? 1u : 0u;
+    ctl->dense_decided = dense || ctl->dense;             // (also when the tracers were not on offer this time: the host's hint for the next call)
 }
 
 __global__ __launch_bounds__(256) void k_build_postab(void* __restrict__ ix, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
-                                                      const SeqDesc* __restrict__ desc, uint32_t* __restrict__ postab, uint32_t* __restrict__ flags)
+                                                      const SeqDesc* __restrict__ desc, uint32_t* __restrict__ postab, IxCtl* __restrict__ ctl)
 {
-    if (res->status != ST_OK || *flags || !flags[IXT_FLAG]) return;
+    if (res->status != ST_OK || ctl->gave_up || !ctl->dense) return;
     const uint32_t b = blockIdx.x;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     if (b >= n) return;
     const BlockOut e = table[b];
     if (e.word >> 31) return;
     const IxBlock blk = ix_blocks((const void*)ix)[b];
-    if ((uint64_t)blk.seq_base + blk.nseq > flags[9] || (e.dst_off & 63u)) { ixt_fail(flags); return; }
+    if ((uint64_t)blk.seq_base + blk.nseq > ctl->n_seqs || (e.dst_off & 63u)) { ixt_fail(ctl); return; }
     const SeqDesc* bd = desc + blk.seq_base;
     uint32_t* T = postab + (e.dst_off >> 6);
     for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < blk.nseq; i += gridDim.y * 256) {
@@ -610,7 +606,7 @@ __global__ __launch_bounds__(256) void k_build_postab(void* __restrict__ ix, con
         const uint32_t op = d.z, end = op + (d.y & 0xFFFFFFu) + (d.w & 0xFFFFFFu);
         // the descriptors must tile [0, size): first at 0, each where the one before ends, the last at the block's size
         const bool okay = (i == 0 ? op == 0 : true) && (i + 1 < blk.nseq ? bd[i + 1].z == end : end == e.dst_size) && end >= op && end <= e.dst_size;
-        if (!okay) { ixt_fail(flags); continue; }
+        if (!okay) { ixt_fail(ctl); continue; }
         for (uint32_t k = (op + 63u) >> 6; (k << 6) < end; k++) T[k] = i;                 // I hold output positions 64k in [op, end)
     }
 }
@@ -630,14 +626,14 @@ static_assert(IXT_REGION == IXT_WG_BYTES, "one workgroup per region");
 
 __global__ __launch_bounds__(256) void k_trace_copy(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint8_t* dst, const BlockOut* __restrict__ table,
                                                     const ResultRec* __restrict__ res, uint32_t n_max, void* __restrict__ ix, const SeqDesc* __restrict__ desc,
-                                                    const uint32_t* __restrict__ dsrc, const uint32_t* __restrict__ postab, uint32_t* flags,
+                                                    const uint32_t* __restrict__ dsrc, const uint32_t* __restrict__ postab, IxCtl* ctl,
                                                     uint32_t linked, uint32_t block_size, uint64_t hist0, uint32_t* region_cnt, uint32_t count_it, uint32_t n_wg)
 {   // n_wg: 4 KiB pieces of output, a workgroup's work each; the grid strides over them (the kernel is launched for every linked frame and returns at once
     // unless the frame is dense: as a grid of a workgroup per piece that was 57 us of empty dispatches per GiB, a tenth of a sparse frame's decode)
     __shared__ uint32_t go;
     __shared__ uint64_t stk_g[IXT_STACK][256];                          // per thread: the ranges set aside where a trace split (see below)
     __shared__ uint32_t stk_s[IXT_STACK][256];
-    if (threadIdx.x == 0) go = (res->status == ST_OK && !__hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) && flags[IXT_FLAG]) ? 1u : 0u;
+    if (threadIdx.x == 0) go = (res->status == ST_OK && !__hip_atomic_load(&ctl->gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) && ctl->dense) ? 1u : 0u;
     __syncthreads();
     if (!go) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
@@ -650,7 +646,7 @@ __global__ __launch_bounds__(256) void k_trace_copy(const uint8_t* __restrict__ 
         const uint32_t k = wgi / per_k, rem = wgi % per_k;
         wg_pos = (uint64_t)(rem / (IXT_REGION / IXT_WG_BYTES)) * block_size + (uint64_t)k * IXT_REGION + (uint64_t)(rem % (IXT_REGION / IXT_WG_BYTES)) * IXT_WG_BYTES;
     }
-    const bool have_dsrc = flags[IXT_FLAG] != 2u;                      // (2: k_resolve_direct was skipped)
+    const bool have_dsrc = ctl->dense != 2u;                      // (2: k_resolve_direct was skipped)
     const uint64_t gpos = wg_pos + threadIdx.x * IXT_TB;
     const uint32_t my_region = (uint32_t)(wg_pos >> IXT_REGION_LOG);
     const uint32_t b = (uint32_t)(wg_pos / block_size);
@@ -765,9 +761,9 @@ __global__ __launch_bounds__(256) void k_trace_copy(const uint8_t* __restrict__ 
                 else { g = gpos + got; span = want - got; }
             } else if (!moved || ++hops >= IXT_MAX_HOPS) bad = true;
         }
-        if (count_it) { atomicAdd((unsigned long long*)(flags + 26), (unsigned long long)n_turns); atomicAdd(flags + 28, n_pieces); atomicAdd(flags + 29, n_fromout); atomicMax(flags + 30, n_turns); }
+        if (count_it) { atomicAdd(&ctl->t_turns, (unsigned long long)n_turns); atomicAdd(&ctl->t_pieces, n_pieces); atomicAdd(&ctl->t_from_out, n_fromout); atomicMax(&ctl->t_deepest, n_turns); }
     }
-    if (bad) ixt_fail(flags);
+    if (bad) ixt_fail(ctl);
     // this workgroup's bytes are in memory: count them into the region
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -795,17 +791,17 @@ constexpr uint32_t IXP_STRIPES = 64;                             // the count of
 
 __global__ __launch_bounds__(256) void k_pd_init(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint8_t* dst, const BlockOut* __restrict__ table,
                                                  const ResultRec* __restrict__ res, uint32_t n_max, void* __restrict__ ix, const SeqDesc* __restrict__ desc,
-                                                 const uint32_t* __restrict__ dsrc, const uint32_t* __restrict__ postab, uint32_t* flags,
+                                                 const uint32_t* __restrict__ dsrc, const uint32_t* __restrict__ postab, IxCtl* ctl,
                                                  uint32_t linked, uint32_t block_size, uint64_t hist0, uint32_t* __restrict__ ptr, uint32_t* __restrict__ remaining)
 {
-    if (res->status != ST_OK || *flags || !flags[IXT_FLAG]) return;
+    if (res->status != ST_OK || ctl->gave_up || !ctl->dense) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
-    const bool have_dsrc = flags[IXT_FLAG] != 2u;                      // (2: k_resolve_direct was skipped)
+    const bool have_dsrc = ctl->dense != 2u;                      // (2: k_resolve_direct was skipped)
     const uint64_t gpos = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * IXT_TB;
     const uint32_t b = (uint32_t)(gpos / block_size);
     if (b >= n) return;
     const BlockOut e = table[b];
-    if (e.dst_off != (uint64_t)b * block_size) { ixt_fail(flags); return; }            // (all blocks but the last are full: checked when the index was made)
+    if (e.dst_off != (uint64_t)b * block_size) { ixt_fail(ctl); return; }            // (all blocks but the last are full: checked when the index was made)
     const uint32_t i0 = (uint32_t)(gpos - e.dst_off);
     if (i0 >= e.dst_size) return;
     const uint32_t want = e.dst_size - i0 < IXT_TB ? e.dst_size - i0 : IXT_TB;
@@ -819,7 +815,7 @@ __global__ __launch_bounds__(256) void k_pd_init(const uint8_t* __restrict__ fra
         for (uint32_t q = 0; q < want; q++) { out[q] = frame[e.src_off + i0 + q]; pout[q] = IXP_DONE; }
         return;
     }
-    if (blk.nseq == 0) { ixt_fail(flags); return; }
+    if (blk.nseq == 0) { ixt_fail(ctl); return; }
     const uint32_t last = blk.nseq - 1;
     uint32_t sq = postab[(e.dst_off >> 6) + (i0 >> 6)];
     while (got < want && !bad) {
@@ -865,16 +861,16 @@ __global__ __launch_bounds__(256) void k_pd_init(const uint8_t* __restrict__ fra
         for (uint32_t q = 0; q < span; q++) { out[got + q] = origin[q]; pout[got + q] = IXP_DONE; }
         got += span;
     }
-    if (bad) ixt_fail(flags);
+    if (bad) ixt_fail(ctl);
     for (int o = 32; o; o >>= 1) open += __shfl_xor(open, o);
     if ((threadIdx.x & 63u) == 0 && open) atomicAdd(remaining + ((blockIdx.x * 4 + (threadIdx.x >> 6)) % IXP_STRIPES), open);
 }
 
 // one round; 4 output bytes per thread.  remaining[r][stripe] count the bytes still open after round r (r = 0: after k_pd_init)
 __global__ __launch_bounds__(256) void k_pd_round(uint8_t* dst, uint32_t* ptr, const BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
-                                                  uint32_t round, uint32_t* __restrict__ remaining, uint32_t* flags, uint8_t* __restrict__ grp = nullptr, uint32_t n_grp = 0)
+                                                  uint32_t round, uint32_t* __restrict__ remaining, IxCtl* ctl, uint8_t* __restrict__ grp = nullptr, uint32_t n_grp = 0)
 {
-    if (res->status != ST_OK || *flags || !flags[IXT_FLAG]) return;
+    if (res->status != ST_OK || ctl->gave_up || !ctl->dense) return;
     if (__ballot(remaining[(round - 1) * IXP_STRIPES + (threadIdx.x & 63u)] != 0) == 0) return;      // nothing was open after the round before
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     if (n == 0) return;
@@ -899,7 +895,7 @@ __global__ __launch_bounds__(256) void k_pd_round(uint8_t* dst, uint32_t* ptr, c
         const uint64_t i = base + k * 64;
         cur[k] = i < total ? ptr[i] : IXP_DONE;
         st[k] = cur[k] < IXP_DONE ? 1u : 0u;
-        if (st[k] && cur[k] >= i) { ixt_fail(flags); st[k] = 0; }  // (sources lie in front: anything else is a corrupted descriptor)
+        if (st[k] && cur[k] >= i) { ixt_fail(ctl); st[k] = 0; }  // (sources lie in front: anything else is a corrupted descriptor)
     }
     // IXP_JUMPS steps along the trail per round (each word read may already be this round's: any value it has held is valid)
 #pragma unroll
@@ -911,7 +907,7 @@ __global__ __launch_bounds__(256) void k_pd_round(uint8_t* dst, uint32_t* ptr, c
         for (uint32_t k = 0; k < 4; k++) {
             if (st[k] != 1u) continue;
             if (v[k] >= IXP_DONE) { st[k] = (v[k] - IXP_DONE < round) ? 2u : 3u; }      // finished earlier: copy it; in this very round: not visible yet, wait here
-            else if (v[k] >= cur[k]) { ixt_fail(flags); st[k] = 0; }
+            else if (v[k] >= cur[k]) { ixt_fail(ctl); st[k] = 0; }
             else cur[k] = v[k];
         }
     }
@@ -929,9 +925,9 @@ __global__ __launch_bounds__(256) void k_pd_round(uint8_t* dst, uint32_t* ptr, c
     if (grp && (threadIdx.x & 63u) == 0 && gw < n_grp) grp[(size_t)(round & 1u) * n_grp + gw] = open ? 1 : 0;
 }
 
-__global__ void k_pd_verdict(uint32_t* flags, const uint32_t* __restrict__ remaining)
+__global__ void k_pd_verdict(IxCtl* ctl, const uint32_t* __restrict__ remaining)
 {
-    if (blockIdx.x == 0 && threadIdx.x < IXP_STRIPES && flags[IXT_FLAG] && !*flags && remaining[IXP_ROUNDS * IXP_STRIPES + threadIdx.x] != 0) ixt_fail(flags);      // deeper than 2^16: the generic kernels
+    if (blockIdx.x == 0 && threadIdx.x < IXP_STRIPES && ctl->dense && !ctl->gave_up && remaining[IXP_ROUNDS * IXP_STRIPES + threadIdx.x] != 0) ixt_fail(ctl);      // deeper than 2^16: the generic kernels
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -940,12 +936,12 @@ __global__ void k_pd_verdict(uint32_t* flags, const uint32_t* __restrict__ remai
 template <class C>
 __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(const uint8_t* __restrict__ frame, uint8_t* dst, BlockOut* __restrict__ table,
                                                                    const ResultRec* __restrict__ res, uint32_t n_max, void* __restrict__ ix,
-                                                                   const SeqDesc* __restrict__ desc, const uint32_t* __restrict__ dsrc, uint32_t* __restrict__ flags,
+                                                                   const SeqDesc* __restrict__ desc, const uint32_t* __restrict__ dsrc, IxCtl* __restrict__ ctl,
                                                                    unsigned long long* prof, uint32_t linked, uint32_t* __restrict__ done, uint32_t group, uint64_t hist0,
                                                                    uint64_t wait_ticks)
 {   // group: consecutive blocks per workgroup (1 except for small blocks of a linked frame, see below)
     __shared__ FzShared<C> sh;
-    if (res->status != ST_OK || *flags || flags[IXT_FLAG]) return;           // index unusable: the generic kernel launched behind does the work; dense: traced
+    if (res->status != ST_OK || ctl->gave_up || ctl->dense) return;           // index unusable: the generic kernel launched behind does the work; dense: traced
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t g = blockIdx.x, tid = threadIdx.x;
     const uint32_t b0 = g * group;
@@ -955,7 +951,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
     // That is still 1.4-2x faster than the window kernel on such data (text 64 MiB: 2.5 vs 3.4 s; `datagen.structured` 48 MiB:
     // 0.15 vs 0.30 s), so there is no gate any more; LZ4F_MI355X_CHAIN_GATE=n leaves frames with more than 1/n of their
     // sequences on the chain to decode_linked.cuh.)
-    if (linked > 1u && (uint64_t)flags[10] * (linked >> 1) > flags[9]) { if (g == 0 && tid == 0) atomicOr(flags, 4u); return; }
+    if (linked > 1u && (uint64_t)ctl->chain_total * (linked >> 1) > ctl->n_seqs) { if (g == 0 && tid == 0) atomicOr(&ctl->gave_up, IX_CHAIN_GATED); return; }
     if (!linked) {                                                           // (group == 1)
         const uint32_t b = b0;
         const BlockOut e = table[b];
@@ -976,7 +972,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
         }
         // A block that did not come out (descriptors that do not tile the output, a bad offset, no room) is left as it was and
         // the generic kernel launched behind decodes the frame again: its verdict is the one the caller gets.
-        if (tid == 0) { if (got < 0) atomicOr(flags, 2u); else table[b].dst_size = (uint32_t)got; }
+        if (tid == 0) { if (got < 0) atomicOr(&ctl->gave_up, IX_COPY_FAILED); else table[b].dst_size = (uint32_t)got; }
         return;
     }
     // ---- linked frame ----
@@ -1024,8 +1020,8 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
     }
     __syncthreads();
     const uint32_t np = failed ? 0u : uni(sh.pend_n);
-    uint32_t* pcnt = done + n_max;
-    uint32_t* prange = done + 2 * (size_t)n_max + (size_t)g * 2 * IXL_PUB;
+    uint32_t* pcnt = ixctl_pcnt(done, n_max);
+    uint32_t* prange = ixctl_ranges(done, n_max, g);
     if (np) {
         // (state 3 is one more release fence: worth it for big blocks, where every block sets something aside and the replays would
         // otherwise form a chain through the whole frame; groups of small blocks just wait for all of the group in front)
@@ -1047,13 +1043,13 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
                 v = 2u;
             };
             poll(false);
-            if (prof && lane_id() == 0) { atomicAdd(flags + 22, 1u); if (v == 1u) atomicAdd(flags + 23, 1u); }
+            if (prof && lane_id() == 0) { atomicAdd(&ctl->l_setaside, 1u); if (v == 1u) atomicAdd(&ctl->l_front_done, 1u); }
             if (v == 3u) {                                                   // (group == 1) do my sources touch what it still has to write?
                 const uint32_t pc = pcnt[g - 1];
                 bool hit = pc == 0xFFFFFFFFu;
                 if (!hit) {
                     const int32_t psz = (int32_t)table[b0 - 1].dst_size;
-                    const uint32_t* pr = done + 2 * (size_t)n_max + (size_t)(g - 1) * 2 * IXL_PUB;
+                    const uint32_t* pr = ixctl_ranges(done, n_max, g - 1);
                     for (uint32_t q = 0; q < np && !hit; q++) {
                         const int32_t s0 = (int32_t)sh.pend_dst[q] - (int32_t)sh.pend_off[q];
                         if (s0 >= 0) continue;
@@ -1061,7 +1057,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
                         for (uint32_t k = 0; k < pc; k++) hit |= lo < (int32_t)pr[2 * k + 1] && hi > (int32_t)pr[2 * k];
                     }
                 }
-                if (prof && lane_id() == 0) { atomicAdd(flags + 20, 1u); if (hit) atomicAdd(flags + 21, 1u); }
+                if (prof && lane_id() == 0) { atomicAdd(&ctl->l_state3, 1u); if (hit) atomicAdd(&ctl->l_state3_waited, 1u); }
                 if (hit) poll(true);
             }
             if (v == 2u) sh.status = -1;
@@ -1075,7 +1071,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
         failed = failed || (int32_t)uni((uint32_t)sh.status) < 0;
     }
     if (tid == 0) {
-        if (failed) atomicOr(flags, 2u);
+        if (failed) atomicOr(&ctl->gave_up, IX_COPY_FAILED);
         // (this release is what a linked frame of small blocks costs, hence the groups)
         __threadfence();
         __hip_atomic_store(done + g, failed ? 2u : 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1099,7 +1095,7 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_indexed(cons
 //     that is not dense) stays on the chain.
 //   * then the slot is checked (tiling, room, offsets) and published exactly as fz_feeder does.
 // A block's feeder needs ~0.3 ms of its ~1.4; the copiers are never the ones waiting after the first round.  Anything odd sets
-// flags bit 1 and the generic decoder launched behind decodes the frame again, as with k_copy_indexed.
+// IX_COPY_FAILED and the generic decoder launched behind decodes the frame again, as with k_copy_indexed.
 template <class C> struct FzOpr { static constexpr uint32_t N = (2u * (C::STAGE + FZ_OVER) >= 16384u) ? 4096u : (2u * (C::STAGE + FZ_OVER) >= 8192u) ? 2048u : 1024u; };
 static_assert(FzOpr<FzCfgS8>::N * 4 <= 2 * (FzCfgS8::STAGE + FZ_OVER) && FzOpr<FzCfgS4>::N * 4 <= 2 * (FzCfgS4::STAGE + FZ_OVER), "the ring of output positions lives in the stage area");
 
@@ -1327,16 +1323,16 @@ struct FzSrcIx {
 template <class C, class RSRC>
 __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_selffed(const uint8_t* __restrict__ frame, uint64_t frame_cap, uint8_t* dst, BlockOut* __restrict__ table,
                                                                    const ResultRec* __restrict__ res, uint32_t n_max, const void* __restrict__ ix,
-                                                                   SeqDesc* desc, uint32_t* __restrict__ flags, unsigned long long* prof, RSRC rsrc, uint32_t round_max,
+                                                                   SeqDesc* desc, IxCtl* __restrict__ ctl, unsigned long long* prof, RSRC rsrc, uint32_t round_max,
                                                                    uint32_t block_size)
 {
     __shared__ FzShared<C> sh;
-    if (res->status != ST_OK || *flags || flags[IXT_FLAG]) return;           // index unusable (k_check_index): the generic kernel launched behind does the work
+    if (res->status != ST_OK || ctl->gave_up || ctl->dense) return;           // index unusable (k_check_index): the generic kernel launched behind does the work
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
     const unsigned long long wg_t0 = prof ? __builtin_amdgcn_s_memrealtime() : 0ull, wg_c0 = prof ? clock64() : 0ull;
     if (b >= n) return;
-    const uint64_t desc_cap = flags[9];
+    const uint64_t desc_cap = ctl->n_seqs;
     const BlockOut e = table[b];
     const uint32_t csz = e.word & 0x7FFFFFFFu;
     const IxBlock* blocks = ix_blocks(ix);
@@ -1362,11 +1358,11 @@ __global__ __launch_bounds__(64 * C::WAVES, FZ_FED_OCC) void k_copy_selffed(cons
             }
         } else {
             typename RSRC::Runs runs;
-            if (rsrc.make(b, blk, csz, flags[8], runs))
+            if (rsrc.make(b, blk, csz, ctl->n_entries, runs))
                 got = fz_decode_block_self<C>(sh, runs, frame + e.src_off, csz, frame_cap - e.src_off, dst + e.dst_off, e.dst_size, frame, prof, desc + blk.seq_base, blk.nseq, round_max, block_size);
         }
     }
-    if (tid == 0) { if (got < 0) atomicOr(flags, 2u); else table[b].dst_size = (uint32_t)got; }
+    if (tid == 0) { if (got < 0) atomicOr(&ctl->gave_up, IX_COPY_FAILED); else table[b].dst_size = (uint32_t)got; }
     if (prof && tid == 0) {                                                  // developer aid: how the workgroups of the grid spread in time
         const unsigned long long t1 = __builtin_amdgcn_s_memrealtime(), cc = clock64() - wg_c0;
         atomicMax(prof + 64, cc); atomicAdd(prof + 65, cc); atomicMin(prof + 70, wg_t0); atomicMax(prof + 71, wg_t0); atomicMax(prof + 72, t1); atomicMin(prof + 75, t1);

@@ -18,7 +18,7 @@
 // Every wave walks every slot of every block in order, so block bases and the end of the frame need
 // no extra hand-off: the last sequence of a block is the one without a match.  Hand-offs are LDS words, no barriers.
 // Restriction: every block but the last must decode to exactly the block size (true for frames written without
-// LZ4F_flush / autoFlush); otherwise the kernel sets `*fallback` and leaves the frame to decode_fused.cuh.
+// LZ4F_flush / autoFlush); otherwise the kernel sets `fallback->gave_up` and leaves the frame to decode_fused.cuh.
 #pragma once
 #include "common.cuh"
 #include "decode.cuh"
@@ -370,7 +370,7 @@ __device__ __forceinline__ lk_v4 lk_win_read16_nowait(const uint8_t* win, uint32
     return v;
 }
 __device__ __forceinline__ void lk_chain(LkShared& sh, uint8_t* out, BlockOut* __restrict__ table, uint32_t n, uint32_t block_size, uint64_t dst_cap,
-                                         uint64_t hist0, uint32_t* __restrict__ fallback)
+                                         uint64_t hist0, LinkedFallback* __restrict__ fallback)
 {
     const uint32_t lane = lane_id();
     LkCursor c; c.n0 = c.n1 = c.n2 = c.n3 = 0; c.block = 0; c.base = 0; c.gslot = 0;
@@ -380,7 +380,7 @@ __device__ __forceinline__ void lk_chain(LkShared& sh, uint8_t* out, BlockOut* _
         if (!lk_next_slot(sh, c, p, idx, count)) return;
         LkRing& rg = sh.ring[p];
         if (c.base != (uint64_t)c.block * block_size) {                       // an earlier block was short: not this kernel's case
-            if (lane == 0) { *fallback = 1u; sh.why = 7; sh.status = -3; }
+            if (lane == 0) { fallback->gave_up = 1u; sh.why = 7; sh.status = -3; }
             return;
         }
         const uint4 d = rg.desc[idx][lane];
@@ -519,16 +519,16 @@ __device__ __forceinline__ void lk_chain(LkShared& sh, uint8_t* out, BlockOut* _
 
 __global__ __launch_bounds__(64 * LK_WAVES) void k_decode_linked(const uint8_t* __restrict__ frame, uint8_t* dst, uint64_t dst_cap,
                                                                  BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
-                                                                 uint32_t n_max, uint32_t block_size, uint64_t hist0, uint32_t* __restrict__ fallback,
+                                                                 uint32_t n_max, uint32_t block_size, uint64_t hist0, LinkedFallback* __restrict__ fallback,
                                                                  const uint32_t* __restrict__ only_if = nullptr)
-{   // fallback[0]: 1 = frame left to the generic kernel; fallback[1..2] (debug): which check stopped this kernel, at which block
+{   // fallback (records.hpp): 1 = frame left to the generic kernel; (debug) which check stopped this kernel, at which block
     // only_if: launched behind the indexed kernels (decode_indexed.cuh), runs only if they gave the frame up
     __shared__ LkShared sh;
     if (res->status != ST_OK) return;
-    if (only_if && *only_if == 0) { if (threadIdx.x == 0) *fallback = 0u; return; }
+    if (only_if && *only_if == 0) { if (threadIdx.x == 0) fallback->gave_up = 0u; return; }
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t tid = threadIdx.x, wave = uni(tid >> 6);
-    if (tid == 0) { sh.next_match_dst = 0; sh.status = 0; sh.bad_block = LK_NONE; *fallback = 0u; sh.why = 0; }
+    if (tid == 0) { sh.next_match_dst = 0; sh.status = 0; sh.bad_block = LK_NONE; fallback->gave_up = 0u; sh.why = 0; }
     if (tid < LK_PARSERS) {
         LkRing& rg = sh.ring[tid];
         rg.produced = 0;
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(64 * LK_WAVES) void k_decode_linked(const uint8_t* 
     }
     __syncthreads();
     const int32_t st = (int32_t)uni((uint32_t)sh.status);
-    if (tid == 0) { fallback[1] = st < 0 ? sh.why : 0u; fallback[2] = sh.bad_block; }
+    if (tid == 0) { fallback->why = st < 0 ? sh.why : 0u; fallback->block = sh.bad_block; }
     if (st < 0 && st != -3) {
         uint32_t bb = uni(sh.bad_block); if (bb >= n) bb = 0;
         for (uint32_t k = bb + tid; k < n; k += 64 * LK_WAVES) table[k].dst_size = (k == bb) ? (uint32_t)st : 0u;

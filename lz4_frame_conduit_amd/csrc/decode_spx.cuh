@@ -27,7 +27,7 @@
 //                 - the code k_parse_indexed runs per index entry, same rules, same direct-match marking.  Every stretch must end
 //                 exactly where the next one starts, the last at the payload's end with the block's last sequence.
 // Behind them k_resolve_direct and k_copy_indexed run as for a frame that came with the compressor's index.  Anything odd - a
-// malformed payload, short blocks inside the frame, a stretch that does not end where it should - sets flags[0], and the generic
+// malformed payload, short blocks inside the frame, a stretch that does not end where it should - sets ctl->gave_up, and the generic
 // decoder launched behind decodes the frame and gives the verdict.
 #pragma once
 #include "decode_indexed.cuh"
@@ -93,7 +93,7 @@ __device__ __forceinline__ bool spx_likely_token(const uint8_t* __restrict__ in,
 // T (SPX_MAXPT + 1 points per block): T[k] = where run k starts (k = 0: byte 0) - a stretch's start, or what its lane noted on the way -, T[runs] = the payload's end; nr[b]: runs.
 __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                    const ResultRec* __restrict__ res, uint32_t n_max, uint32_t* __restrict__ cnt, uint32_t* __restrict__ osz,
-                                                   SpxPoint* __restrict__ T, uint32_t* __restrict__ nr, uint32_t* __restrict__ flags,
+                                                   SpxPoint* __restrict__ T, uint32_t* __restrict__ nr, IxCtl* __restrict__ ctl,
                                                    const uint32_t* __restrict__ only_if)
 {
     __shared__ uint32_t s_g[SPX_MAXSEG + 1];                    // where lane u starts: its guess (lane 0: byte 0); [lanes]: SPX_NONE
@@ -111,11 +111,11 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x, u = threadIdx.x;
     if (b >= n) return;
-    if (only_if && *only_if == 0) { if (u == 0) { cnt[b] = 0; osz[b] = 0; nr[b] = 0; atomicOr(flags, 1u); } return; }      // (dense payloads: not this path)
+    if (only_if && *only_if == 0) { if (u == 0) { cnt[b] = 0; osz[b] = 0; nr[b] = 0; atomicOr(&ctl->gave_up, IX_UNUSABLE); } return; }      // (dense payloads: not this path)
     const BlockOut e = table[b];
     const uint32_t csize = e.word & 0x7FFFFFFFu;
     if (e.word >> 31) { if (u == 0) { cnt[b] = 0; osz[b] = csize; nr[b] = 0; } return; }
-    if (csize == 0 || e.src_off + csize > frame_cap) { if (u == 0) { atomicOr(flags, 1u); cnt[b] = 0; osz[b] = 0; nr[b] = 0; } return; }
+    if (csize == 0 || e.src_off + csize > frame_cap) { if (u == 0) { atomicOr(&ctl->gave_up, IX_UNUSABLE); cnt[b] = 0; osz[b] = 0; nr[b] = 0; } return; }
     const uint8_t* in = frame + e.src_off;
     const uint64_t readable = frame_cap - e.src_off;
     const uint32_t nl = spx_lanes(csize);
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
                 }
                 longs += ((uint32_t)c.w & 0xF0u) == 0xF0u ? 1u : 0u;
 #ifdef SPX_PROF
-                if (hops > SPX_LANE_HOPS) atomicAdd(&flags[48], 1u);
+                if (hops > SPX_LANE_HOPS) atomicAdd(&ctl->spx_prof.hop_cap, 1u);
 #endif
                 if (hops > SPX_LANE_HOPS) break;                             // (a chain that crawls is a wrong guess: the stitching thread walks this stretch)
                 const int r = spx_step(in, csize, readable, c);
@@ -225,10 +225,10 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
         }
         s_b[u] = pb; s_end[u] = ended; s_nsub[u] = pb.pos != SPX_NONE ? nsub : 0u;
 #ifdef SPX_PROF
-        if (s_g[u] == SPX_NONE) atomicAdd(&flags[49], 1u);
-        else if (u && s_g[u] == u * SPX_SEG) atomicAdd(&flags[50], 1u);
-        if (pb.pos == SPX_NONE && s_g[u] != SPX_NONE) atomicAdd(&flags[51], 1u);
-        atomicMax(&flags[52], pb.seq);
+        if (s_g[u] == SPX_NONE) atomicAdd(&ctl->spx_prof.no_start, 1u);
+        else if (u && s_g[u] == u * SPX_SEG) atomicAdd(&ctl->spx_prof.at_seg_start, 1u);
+        if (pb.pos == SPX_NONE && s_g[u] != SPX_NONE) atomicAdd(&ctl->spx_prof.ran_into, 1u);
+        atomicMax(&ctl->spx_prof.most_seqs, pb.seq);
 #endif
     }
 #ifdef SPX_PROF
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
     __syncthreads();
 #ifdef SPX_PROF
     const unsigned long long z4 = clock64();
-    if ((u & 63) == 0) { atomicMax(&flags[40], (uint32_t)(z1 - z0)); atomicMax(&flags[41], (uint32_t)(z3 - z2)); atomicAdd(&flags[44], (uint32_t)((z1 - z0) >> 8)); atomicAdd(&flags[45], (uint32_t)((z3 - z2) >> 8)); }
+    if ((u & 63) == 0) { atomicMax(&ctl->spx_prof.guess_max, (uint32_t)(z1 - z0)); atomicMax(&ctl->spx_prof.walk_max, (uint32_t)(z3 - z2)); atomicAdd(&ctl->spx_prof.guess_sum, (uint32_t)((z1 - z0) >> 8)); atomicAdd(&ctl->spx_prof.walk_sum, (uint32_t)((z3 - z2) >> 8)); }
 #endif
     // ---- the stitch: lane 0 starts at byte 0 and is true; lane k + 1 is true iff the true chain lands exactly on its start.  A lane
     // ---- that is not (a wrong guess) is skipped: the thread walks on from where the true chain stands until it meets a later lane's start.
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
                 // the first lane it meets (or the end); that lane's own walk is the true chain again
                 if (kn < nl && (s_g[kn] == SPX_NONE || s_g[kn] < nx.pos)) { kn++; continue; }      // (a lane without a start, or one whose start lies behind us already)
                 const uint32_t stop = kn < nl ? s_g[kn] : SPX_NONE;
-                atomicAdd(&flags[2], 1u);                                    // (how often: a developer's number, LZ4F_MI355X_PROF prints it)
+                atomicAdd(&ctl->spx_stitched, 1u);                                    // (how often: a developer's number, LZ4F_MI355X_PROF prints it)
                 SpxCur c{{nx.pos, 0}, nx.seq, nx.out};
                 spx_begin(in, readable, c);
                 for (;;) {
@@ -284,9 +284,9 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
             k = kn; cur = nx;
         }
 #ifdef SPX_PROF
-        { const unsigned long long z5 = clock64(); atomicMax(&flags[42], (uint32_t)(z5 - z4)); atomicMax(&flags[43], (uint32_t)(z5 - z0)); atomicAdd(&flags[46], (uint32_t)((z5 - z4) >> 8)); }
+        { const unsigned long long z5 = clock64(); atomicMax(&ctl->spx_prof.stitch_max, (uint32_t)(z5 - z4)); atomicMax(&ctl->spx_prof.wg_max, (uint32_t)(z5 - z0)); atomicAdd(&ctl->spx_prof.stitch_sum, (uint32_t)((z5 - z4) >> 8)); }
 #endif
-        if (bad || total_seq == 0) { atomicOr(flags, 1u); cnt[b] = 0; osz[b] = 0; nr[b] = 0; s_fail = 1; }
+        if (bad || total_seq == 0) { atomicOr(&ctl->gave_up, IX_UNUSABLE); cnt[b] = 0; osz[b] = 0; nr[b] = 0; s_fail = 1; }
         else {
             Tb[tpos] = SpxPoint{csize, total_seq, total_out};                // the end, as the last run's stop
             cnt[b] = total_seq; osz[b] = total_out; nr[b] = tpos;
@@ -306,18 +306,18 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
 __global__ __launch_bounds__(128) void k_spx_parse(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
                                                   const ResultRec* __restrict__ res, uint32_t n_max, const void* __restrict__ ix,
                                                   const SpxPoint* __restrict__ T, const uint32_t* __restrict__ nr, SeqDesc* __restrict__ desc,
-                                                  uint32_t* __restrict__ flags)
+                                                  IxCtl* __restrict__ ctl)
 {
-    if (res->status != ST_OK || *flags) return;
+    if (res->status != ST_OK || ctl->gave_up) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
     const uint32_t b = blockIdx.x;
     if (b >= n) return;
     const uint32_t stretches = nr[b];
-    const uint64_t desc_cap = flags[9];
+    const uint64_t desc_cap = ctl->n_seqs;
     const IxBlock blk = ix_blocks(ix)[b];
     const BlockOut e = table[b];
     const uint32_t csize = e.word & 0x7FFFFFFFu;
-    if (stretches && ((e.word >> 31) || e.src_off + csize > frame_cap || (uint64_t)blk.seq_base + blk.nseq > desc_cap)) { if (threadIdx.x == 0) atomicOr(flags, 1u); return; }
+    if (stretches && ((e.word >> 31) || e.src_off + csize > frame_cap || (uint64_t)blk.seq_base + blk.nseq > desc_cap)) { if (threadIdx.x == 0) atomicOr(&ctl->gave_up, IX_UNUSABLE); return; }
     const SpxPoint* Tb = T + (size_t)b * (SPX_MAXPT + 1);
     for (uint32_t k = threadIdx.x; k < stretches; k += blockDim.x) {
         const SpxPoint from = Tb[k], to = Tb[k + 1];
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(128) void k_spx_parse(const uint8_t* __restrict__ f
         uint32_t pos = from.pos;
         if (!bad) bad = parse_run(frame + e.src_off, csize, frame_cap - e.src_off, pos, from.out, to.seq - from.seq, is_tail, desc + blk.seq_base + from.seq, 0u, 0ull);
         if (!bad && pos != to.pos) bad = true;                                   // must end exactly where the next stretch starts
-        if (bad) atomicOr(flags, 1u);
+        if (bad) atomicOr(&ctl->gave_up, IX_UNUSABLE);
     }
 }
 

@@ -426,9 +426,9 @@ void lz4f_mi355x_engine::enc_emit(const CompressJob& j, const EncodePlan& p, uin
     if (!j.block_checksum) return;
     tick(3, false);
     if (p.xxh_lane4)                                                   // (lane4_xxh32)
-        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(g.n_blocks), dim3(64), XXH_SPREAD_LDS, st, d_dst, tbl, rec, g.n_blocks, 0u, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(g.n_blocks), dim3(64), XXH_SPREAD_LDS, st, d_dst, tbl, rec, g.n_blocks, 0u, (FinishVerdict*)nullptr);
     else
-        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, d_dst, tbl, rec, g.n_blocks, 0u, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((g.n_blocks + W - 1) / W), dim3(64 * W), 0, st, d_dst, tbl, rec, g.n_blocks, 0u, (FinishVerdict*)nullptr);
     tick(3, true);
 }
 
@@ -550,6 +550,14 @@ lz4f_mi355x_engine::IxRoute lz4f_mi355x_engine::ix_route(const DecompressJob& j,
     r.gate = !trace_can ? 0u : sw.trace_always ? 2u : (j.linked || r.doubling) ? 1u : 0u;
     return r;
 }
+// a DevBuf carved into arrays: take() them in order, ensure(), then at()
+struct Carve {
+    DevBuf& buf;
+    size_t end = 0;
+    size_t take(size_t bytes, size_t align = 1) { const size_t at = (end + align - 1) & ~(align - 1); end = at + bytes; return at; }
+    int ensure() { return buf.ensure(end); }
+    template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
+};
 // developer aid (LZ4F_MI355X_PROF): wait for the stream, then copy n bytes of the device's counters back
 static bool prof_read(hipStream_t st, void* to, const void* from, size_t n) { return hipStreamSynchronize(st) == hipSuccess && hipMemcpy(to, from, n, hipMemcpyDeviceToHost) == hipSuccess; }
 
@@ -565,7 +573,7 @@ size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p
             HIP_TRY(hipMemcpyAsync(tbl, j.d_table, (size_t)n_max * sizeof(BlockOut), hipMemcpyDeviceToDevice, st));
         if (p.begin_small)
             hipLaunchKernelGGL(k_begin_table_small, dim3(1), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
-                               j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, res, (uint32_t*)bad.p);
+                               j.block_size, j.block_checksum ? 1u : 0u, j.linked ? 1u : 0u, res, (FinishVerdict*)bad.p);
         else {
             hipLaunchKernelGGL(k_init_result, dim3(1), dim3(64), 0, st, res, n_max, 0u);
             if (n_max) hipLaunchKernelGGL(k_check_table, dim3(std::min<uint32_t>((n_max + 255) / 256, 1024u)), dim3(256), 0, st, (const BlockOut*)tbl, n_max, (uint64_t)j.frame_cap, (uint64_t)j.dst_cap,
@@ -588,13 +596,14 @@ size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p
             *path |= LZ4F_MI355X_PATH_TRAILER;
         } else if (p.walk == DecodePlan::WALK_PARALLEL) {
             const uint32_t n_chunks = (uint32_t)((j.frame_cap + WK_CHUNK - 1) / WK_CHUNK);
-            const size_t at_chunks = 256, at_list = at_chunks + (size_t)n_chunks * sizeof(WalkChunk), at_list2 = at_list + list_cap * 8, at_mark = at_list2 + list_cap * 8;
-            if (walkbuf.ensure(at_mark + list_cap * 4)) return make_err(LZ4F_ERROR_allocation_failed);
-            ws = (WalkState*)walkbuf.p;
-            WalkChunk* ch = (WalkChunk*)((uint8_t*)walkbuf.p + at_chunks);
-            uint64_t* list1 = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
-            uint64_t* list2 = (uint64_t*)((uint8_t*)walkbuf.p + at_list2);
-            uint32_t* mark = (uint32_t*)((uint8_t*)walkbuf.p + at_mark);
+            Carve wb{walkbuf};
+            const size_t at_state = wb.take(256), at_chunks = wb.take((size_t)n_chunks * sizeof(WalkChunk)), at_list = wb.take(list_cap * 8), at_list2 = wb.take(list_cap * 8), at_mark = wb.take(list_cap * 4);
+            if (wb.ensure()) return make_err(LZ4F_ERROR_allocation_failed);
+            ws = wb.at<WalkState>(at_state);
+            WalkChunk* ch = wb.at<WalkChunk>(at_chunks);
+            uint64_t* list1 = wb.at<uint64_t>(at_list);
+            uint64_t* list2 = wb.at<uint64_t>(at_list2);
+            uint32_t* mark = wb.at<uint32_t>(at_mark);
             HIP_TRY(hipMemsetAsync(mark, 0, list_cap * 4, st));
             hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
             hipLaunchKernelGGL(k_walk_cand, dim3(n_chunks), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, ch);
@@ -606,12 +615,13 @@ size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p
         } else if (p.walk == DecodePlan::WALK_SEEDED) {
             // big blocks: seeds found in parallel, a lane per seed walking to the next one (frame_dev.cuh); the list is checked link by
             // link like the small blocks' candidates, and k_walk_frame behind walks the frame itself if it is not the chain
-            const size_t at_seeds = 256, at_list = at_seeds + (WK_SEEDS + 1) * 8;
-            if (walkbuf.ensure(at_list + list_cap * 8)) return make_err(LZ4F_ERROR_allocation_failed);
-            ws = (WalkState*)walkbuf.p;
-            unsigned long long* seeds = (unsigned long long*)((uint8_t*)walkbuf.p + at_seeds);
+            Carve wb{walkbuf};
+            const size_t at_state = wb.take(256), at_seeds = wb.take((WK_SEEDS + 1) * 8), at_list = wb.take(list_cap * 8);
+            if (wb.ensure()) return make_err(LZ4F_ERROR_allocation_failed);
+            ws = wb.at<WalkState>(at_state);
+            unsigned long long* seeds = wb.at<unsigned long long>(at_seeds);
             HIP_TRY(hipMemsetAsync(seeds, 0xFF, (WK_SEEDS + 1) * 8, st));
-            uint64_t* list1 = (uint64_t*)((uint8_t*)walkbuf.p + at_list);
+            uint64_t* list1 = wb.at<uint64_t>(at_list);
             hipLaunchKernelGGL(k_walk_head, dim3(1), dim3(64), 0, st, j.d_frame, j.frame_cap, ws);
             hipLaunchKernelGGL(k_walk_seeds, dim3(WK_SEEDS * wk_seed_pieces(j.block_size)), dim3(256), 0, st, j.d_frame, j.frame_cap, (const WalkState*)ws, seeds);
             hipLaunchKernelGGL(k_walk_chains, dim3(1), dim3(WK_SEEDS), 0, st, j.d_frame, j.frame_cap, ws, (const unsigned long long*)seeds, list1, (uint32_t)std::min<size_t>(list_cap, 0xFFFFFFFFu));
@@ -629,8 +639,8 @@ size_t lz4f_mi355x_engine::dec_table(const DecompressJob& j, const DecodePlan& p
         tick(4, true);
     }
     if (!p.begin_small) {                                              // (k_begin_table_small set them)
-        HIP_TRY(hipMemsetAsync(bad.p, 0xFF, 8, st));                 // [0] block-checksum verdict, [1] first failed block
-        HIP_TRY(hipMemsetAsync((uint8_t*)bad.p + 8, 0, 24, st));    // [2] "something has to move", [4..5] sum of sizes (k_finish_check)
+        HIP_TRY(hipMemsetAsync(bad.p, 0xFF, FINISH_ONES, st));       // the two "first block that ..." words
+        HIP_TRY(hipMemsetAsync((uint8_t*)bad.p + FINISH_ONES, 0, sizeof(FinishVerdict) - FINISH_ONES, st));
     }
     *tbl_out = tbl;
     return 0;
@@ -649,9 +659,9 @@ size_t lz4f_mi355x_engine::dec_checksums(const DecompressJob& j, const DecodePla
     if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_fork, st)); HIP_TRY(hipStreamWaitEvent(xs, (hipEvent_t)ev_fork, 0)); }
     tick(5, false, xs);
     if (n_max < XXH_LANE4_BELOW)
-        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(n_max), dim3(64), beside ? (12u << 10) : XXH_SPREAD_LDS, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (uint32_t*)bad.p);
+        hipLaunchKernelGGL((k_xxh32_blocks4<1>), dim3(n_max), dim3(64), beside ? (12u << 10) : XXH_SPREAD_LDS, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (FinishVerdict*)bad.p);
     else
-        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (uint32_t*)bad.p);
+        hipLaunchKernelGGL((k_xxh32_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, xs, (uint8_t*)j.d_frame, tbl, res, n_max, 1u, (FinishVerdict*)bad.p);
     tick(5, true, xs);
     if (beside) { HIP_TRY(hipEventRecord((hipEvent_t)ev_join, xs)); aux_pending = true; }
     return 0;
@@ -693,50 +703,60 @@ size_t lz4f_mi355x_engine::dec_index(const DecompressJob& j, const DecodePlan& p
 // independent blocks' (spx_walk): lanes that start at guessed tokens cut the blocks into stretches, stitched where they meet (decode_spx.cuh).
 // A scan places the blocks; its totals, read back (a host synchronisation), size the index.  Dense payloads (k_density_probe) and anything
 // odd leave the frame to the generic decoders.
+// the stretch points' workspace (decode_spx.cuh): SPX_MAXPT + 1 points per block, then a count per block.  Returns where the counts are.
+static size_t spx_carve(Carve& c, uint32_t n_max)
+{
+    c.take((size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint));
+    return c.take((size_t)n_max * 4 + 64);
+}
 size_t lz4f_mi355x_engine::dec_self_index(const DecompressJob& j, const DecodePlan& p, ResultRec* res, BlockOut* tbl, bool spx_walk, IndexSrc* ix)
 {
     hipStream_t st = (hipStream_t)stream; const uint32_t n_max = p.n_max, cpb = j.block_size / pick_chunk_size(j.block_size);
-    const size_t fixed = ix_entries_at(n_max, cpb), spx_at = (size_t)n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint);
-    if (selfcnt.ensure((size_t)n_max * 8 + 64) || seqcnt.ensure(256 + (size_t)n_max * (8 + 8 * IXL_PUB)) || selfix.ensure(fixed + 64) || density.ensure(64) ||
-        (spx_walk && spx.ensure((size_t)n_max * ((SPX_MAXPT + 1) * sizeof(SpxPoint) + 4) + 64)))
+    const size_t fixed = ix_entries_at(n_max, cpb);
+    Carve sp{spx}; const size_t spx_cnt_at = spx_carve(sp, n_max);
+    if (selfcnt.ensure((size_t)n_max * 8 + 64) || seqcnt.ensure(ixctl_bytes(n_max)) || selfix.ensure(fixed + 64) || density.ensure(64) || (spx_walk && sp.ensure()))
         return make_err(LZ4F_ERROR_allocation_failed);
     uint32_t* cnt = (uint32_t*)selfcnt.p; uint32_t* osz = cnt + n_max;
-    HIP_TRY(hipMemsetAsync(seqcnt.p, 0, spx_walk ? 256 : 64, st));
-    hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, res, n_max, (uint32_t*)density.p);
+    IxCtl* ctl = (IxCtl*)seqcnt.p; Density* dens = (Density*)density.p;
+    HIP_TRY(hipMemsetAsync(ctl, 0, spx_walk ? sizeof(IxCtl) : offsetof(IxCtl, window), st));      // (the walkers and the scan use the words in front of `window`; SPX_PROF counts further back)
+    hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, res, n_max, dens);
     if (spx_walk)
         hipLaunchKernelGGL(k_spx_index, dim3(n_max), dim3(SPX_MAXSEG), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, res, n_max, cnt, osz,
-                           (SpxPoint*)spx.p, (uint32_t*)((uint8_t*)spx.p + spx_at), (uint32_t*)seqcnt.p, sw.no_density_probe ? (const uint32_t*)nullptr : (const uint32_t*)density.p + 1);
+                           sp.at<SpxPoint>(0), sp.at<uint32_t>(spx_cnt_at), ctl, sw.no_density_probe ? (const uint32_t*)nullptr : (const uint32_t*)&dens->not_dense);
     else {
         hipLaunchKernelGGL((k_selfindex_walk_wave<0, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                           res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
+                           res, n_max, cnt, osz, (void*)nullptr, ctl, (const uint32_t*)&dens->dense);
         hipLaunchKernelGGL(k_selfindex_walk<0>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                           res, n_max, cnt, osz, (void*)nullptr, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
+                           res, n_max, cnt, osz, (void*)nullptr, ctl, (const uint32_t*)&dens->not_dense);
     }
-    uint32_t tot[10];
+    IxCtl tot;                                                           // (the scan's verdict and totals: the words in front of chain_total are read back)
     for (int pass = 0; pass < 2; pass++) {
         hipLaunchKernelGGL(k_selfindex_scan, dim3(1), dim3(1024), 0, st, tbl, res, n_max, (const uint32_t*)cnt, (const uint32_t*)osz,
-                           selfix.p, cpb, (uint64_t)j.dst_cap, j.block_size, (uint32_t*)seqcnt.p, spx_walk ? 1u : 0u);
+                           selfix.p, cpb, (uint64_t)j.dst_cap, j.block_size, ctl, spx_walk ? 1u : 0u);
         if (pass == 1) break;
-        HIP_TRY(hipMemcpyAsync(tot, seqcnt.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&tot, ctl, offsetof(IxCtl, chain_total), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (spx_walk && sw.prof) fprintf(stderr, "spx: flags %u, %u sequences in %u blocks, %u stretches walked by the stitching thread\n", tot[0], tot[9], n_max, tot[2]);
+        if (spx_walk && sw.prof) fprintf(stderr, "spx: flags %u, %u sequences in %u blocks, %u stretches walked by the stitching thread\n", tot.gave_up, tot.n_seqs, n_max, tot.spx_stitched);
 #ifdef SPX_PROF
-        if (spx_walk) { uint32_t y[8]; if (hipMemcpy(y, (uint32_t*)seqcnt.p + 48, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx lanes: hit the hop cap %u, without a start %u, started at their segment's first byte %u, ran into something %u; most sequences in one lane %u\n", y[0], y[1], y[2], y[3], y[4]); }
-        if (spx_walk) { uint32_t z[8]; if (hipMemcpy(z, (uint32_t*)seqcnt.p + 40, 32, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "spx cycles: guess max %u avg %u, walk max %u avg %u, stitch max %u avg %u, workgroup max %u (waves %u)\n", z[0], (unsigned)(((unsigned long long)z[4] << 8) / (2 * n_max)), z[1], (unsigned)(((unsigned long long)z[5] << 8) / (2 * n_max)), z[2], (unsigned)(((unsigned long long)z[6] << 8) / n_max), z[3], 2 * n_max); }
+        SpxProf y;
+        if (spx_walk && hipMemcpy(&y, &ctl->spx_prof, sizeof(y), hipMemcpyDeviceToHost) == hipSuccess) {
+            fprintf(stderr, "spx lanes: hit the hop cap %u, without a start %u, started at their segment's first byte %u, ran into something %u; most sequences in one lane %u\n", y.hop_cap, y.no_start, y.at_seg_start, y.ran_into, y.most_seqs);
+            fprintf(stderr, "spx cycles: guess max %u avg %u, walk max %u avg %u, stitch max %u avg %u, workgroup max %u (waves %u)\n", y.guess_max, (unsigned)(((unsigned long long)y.guess_sum << 8) / (2 * n_max)), y.walk_max, (unsigned)(((unsigned long long)y.walk_sum << 8) / (2 * n_max)), y.stitch_max, (unsigned)(((unsigned long long)y.stitch_sum << 8) / n_max), y.wg_max, 2 * n_max);
+        }
 #endif
-        if (tot[0] != 0 || tot[9] == 0) break;
+        if (tot.gave_up != 0 || tot.n_seqs == 0) break;
         const void* before = selfix.p;
-        if (selfix.ensure(fixed + (size_t)tot[8] * sizeof(IxEntry) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
+        if (selfix.ensure(fixed + (size_t)tot.n_entries * sizeof(IxEntry) + 64)) return make_err(LZ4F_ERROR_allocation_failed);
         if (selfix.p == before) break;                                   // (same buffer: the block table is already in it)
     }
-    if (tot[0] != 0 || tot[9] == 0) return 0;
+    if (tot.gave_up != 0 || tot.n_seqs == 0) return 0;
     if (!spx_walk) {                                                     // (the linked frame's walkers again, filling the index in)
         hipLaunchKernelGGL((k_selfindex_walk_wave<1, 4>), dim3((n_max + 3) / 4), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                           res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p);
+                           res, n_max, cnt, osz, selfix.p, ctl, (const uint32_t*)&dens->dense);
         hipLaunchKernelGGL(k_selfindex_walk<1>, dim3((n_max + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl,
-                           res, n_max, cnt, osz, selfix.p, (uint32_t*)seqcnt.p, (const uint32_t*)density.p + 1);
+                           res, n_max, cnt, osz, selfix.p, ctl, (const uint32_t*)&dens->not_dense);
     }
-    *ix = IndexSrc{spx_walk ? IndexSrc::SPX : IndexSrc::SELF_LINKED, selfix.p, fixed + (size_t)tot[8] * sizeof(IxEntry), tot[9], tot[8]};
+    *ix = IndexSrc{spx_walk ? IndexSrc::SPX : IndexSrc::SELF_LINKED, selfix.p, fixed + (size_t)tot.n_entries * sizeof(IxEntry), tot.n_seqs, tot.n_entries};
     return 0;
 }
 
@@ -750,18 +770,21 @@ size_t lz4f_mi355x_engine::dec_indexed(const DecompressJob& j, const DecodePlan&
     const uint32_t chunk = pick_chunk_size(j.block_size), cpb = j.block_size / chunk, n_ix = p.n_ix;
     if ((size_t)ix.seqs + 4096 > ix_seq_cap) ix_seq_cap = (size_t)ix.seqs + ix.seqs / 4 + 4096;
     if (!ix.seqs) return 0;
-    const size_t dsrc_at = (ix_seq_cap + 64) * sizeof(SeqDesc);
-    if (desc.ensure(dsrc_at + (ix_seq_cap + 64) * 4) || seqcnt.ensure(256 + (size_t)p.n_max * (8 + 8 * IXL_PUB))) return make_err(LZ4F_ERROR_allocation_failed);
-    HIP_TRY(hipMemsetAsync(seqcnt.p, 0, 256 + (j.linked ? (size_t)p.n_max * 8 : 0), st));      // flags (+ per block of a linked frame: the "done" word and the count of published ranges)
+    Carve dc{desc}; dc.take((ix_seq_cap + 64) * sizeof(SeqDesc));              // the descriptors, then a resolved source per descriptor
+    const size_t dsrc_at = dc.take((ix_seq_cap + 64) * 4);
+    if (dc.ensure() || seqcnt.ensure(ixctl_bytes(p.n_max))) return make_err(LZ4F_ERROR_allocation_failed);
+    IxCtl* ctl = (IxCtl*)seqcnt.p;
+    HIP_TRY(hipMemsetAsync(ctl, 0, j.linked ? ixctl_cleared(p.n_max) : sizeof(IxCtl), st));      // the control block (+ per block of a linked frame: the "done" word and the count of published ranges)
+    Carve sp{spx}; const size_t spx_cnt_at = spx_carve(sp, p.n_max);              // (dec_self_index filled it, if the index is its stretches)
     unsigned long long* iprof = (unsigned long long*)(sw.prof ? prof_buf() : nullptr);
     tick(8, false);
     hipLaunchKernelGGL(k_check_index, dim3(1), dim3(64), 0, st, (const void*)d_index, (uint64_t)ix.size, n_ix, cpb, chunk,
-                       (uint64_t)ix_seq_cap, (uint32_t*)seqcnt.p, (const ResultRec*)res);
+                       (uint64_t)ix_seq_cap, ctl, (const ResultRec*)res);
     // the whole block table, before any kernel behind writes (the index is input)
     hipLaunchKernelGGL(k_check_blocks, dim3((n_ix + 255) / 256), dim3(256), 0, st, (const void*)d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
-                       (uint32_t*)seqcnt.p);
+                       ctl);
     const IxRoute r = ix_route(j, sw, n_ix, ix.seqs);
-    *ix_flags = (const uint32_t*)seqcnt.p;
+    *ix_flags = &ctl->gave_up;
     *path |= LZ4F_MI355X_PATH_INDEXED;
     if (r.selffed) {
         tick(8, true); tick(9, false);
@@ -770,87 +793,92 @@ size_t lz4f_mi355x_engine::dec_indexed(const DecompressJob& j, const DecodePlan&
             using S = decltype(src);
             if (j.block_size <= (1u << 20))
                 hipLaunchKernelGGL((k_copy_selffed<FzCfgS4, S>), dim3(n_ix), dim3(64 * 4), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)res, n_ix,
-                                   (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
+                                   (const void*)d_index, (SeqDesc*)desc.p, ctl, iprof, src, sw.feed_round, j.block_size);
             else
                 hipLaunchKernelGGL((k_copy_selffed<FzCfgS8, S>), dim3(n_ix), dim3(64 * 8), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, tbl, (const ResultRec*)res, n_ix,
-                                   (const void*)d_index, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, iprof, src, sw.feed_round, j.block_size);
+                                   (const void*)d_index, (SeqDesc*)desc.p, ctl, iprof, src, sw.feed_round, j.block_size);
         };
-        if (ix.from == IndexSrc::SPX) selffed(FzSrcSpx{(const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)p.n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint))});
+        if (ix.from == IndexSrc::SPX) selffed(FzSrcSpx{sp.at<const SpxPoint>(0), sp.at<const uint32_t>(spx_cnt_at)});
         else selffed(FzSrcIx{(const void*)d_index, n_ix});
         tick(9, true);
         return 0;
     }
     // the chain: parse, resolve direct matches, trace dense frames, copy, check the tails
-    uint32_t* done = (uint32_t*)seqcnt.p + 64;
+    uint32_t* done = ixctl_done(ctl);
     const uint32_t lk = j.linked ? 1u | (uint32_t)sw.chain_gate << 1 : 0u;      // (bits 1..: chain gate, see k_copy_indexed)
     const uint32_t n_lanes = ix.entries > n_ix ? ix.entries : n_ix;     // (grid-stride inside: a hint is enough)
     if (ix.from == IndexSrc::SPX)                                                 // (no entries: the stretches between the blocks' check lines)
         hipLaunchKernelGGL(k_spx_parse, dim3(n_ix), dim3(128), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
-                           d_index, (const SpxPoint*)spx.p, (const uint32_t*)((const uint8_t*)spx.p + (size_t)p.n_max * (SPX_MAXPT + 1) * sizeof(SpxPoint)),
-                           (SeqDesc*)desc.p, (uint32_t*)seqcnt.p);
+                           d_index, sp.at<const SpxPoint>(0), sp.at<const uint32_t>(spx_cnt_at), (SeqDesc*)desc.p, ctl);
     else
         hipLaunchKernelGGL(k_parse_indexed, dim3((n_lanes + 255) / 256), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap,
-                           (const BlockOut*)tbl, d_index, n_ix, (SeqDesc*)desc.p, (uint32_t*)seqcnt.p, lk, (uint64_t)j.hist0);
+                           (const BlockOut*)tbl, d_index, n_ix, (SeqDesc*)desc.p, ctl, lk, (uint64_t)j.hist0);
     const uint64_t trace_span = (uint64_t)n_ix * j.block_size;            // (the last block may be short)
     const uint32_t res_gy = j.block_size >= (1u << 19) ? j.block_size >> 18 : 1u;
     uint32_t gate = r.gate;
-    if (gate && postab.ensure((size_t)(trace_span >> 6) * 4 + 512 + ((size_t)(trace_span >> IXT_REGION_LOG) + 4) * 4)) gate = 0;      // (no memory for the position table: the copiers do it)
+    Carve pt{postab}; pt.take((size_t)(trace_span >> 6) * 4);          // a word per 64 output bytes, then the regions' byte counts
+    const size_t region_at = pt.take(((size_t)(trace_span >> IXT_REGION_LOG) + 4) * 4 + 512, 256);
+    if (gate && pt.ensure()) gate = 0;                              // (no memory for the position table: the copiers do it)
     if (gate && r.doubling)                                        // (dense by the sequence density: no need to resolve anything)
-        hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 1u, 1u);
-    uint32_t* dsrc = sw.no_resolve ? nullptr : (uint32_t*)((uint8_t*)desc.p + dsrc_at);
+        hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, ctl, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 1u, 1u);
+    uint32_t* dsrc = sw.no_resolve ? nullptr : dc.at<uint32_t>(dsrc_at);
     if (dsrc)
         hipLaunchKernelGGL(k_resolve_direct, dim3(n_ix, res_gy), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, (const SeqDesc*)desc.p,
-                           dsrc, (uint32_t*)seqcnt.p, (iprof ? 1u : 0u) | (gate ? 2u : 0u), lk);
+                           dsrc, ctl, (iprof ? 1u : 0u) | (gate ? 2u : 0u), lk);
     if (iprof) {                                                   // developer aid: how many matches are direct
-        uint32_t c[8]; if (prof_read(st, c, seqcnt.p, 32)) fprintf(stderr, "indexed: flags %u, matches direct after parse %u, resolved %u, left to the chain %u\n", c[0], c[4], c[5], c[6]);
-        uint32_t x[6] = {0, 0, 0, 0, 0, 0}; if (hipMemcpy(x, (uint32_t*)seqcnt.p + 10, 24, hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "indexed (linked): %u matches stay on the chain, %u of them reach into the block in front (%u blocks); not resolved because: beyond one block %u, source straddles two runs %u, run-length source %u, hop limit %u\n", x[0], x[1], n_ix, x[2], x[3], x[4], x[5]);
+        IxCtl c;
+        if (prof_read(st, &c, ctl, sizeof(c))) {
+            fprintf(stderr, "indexed: flags %u, matches direct after parse %u, resolved %u, left to the chain %u\n", c.gave_up, c.m_direct, c.m_resolved, c.m_chain);
+            fprintf(stderr, "indexed (linked): %u matches stay on the chain, %u of them reach into the block in front (%u blocks); not resolved because: beyond one block %u, source straddles two runs %u, run-length source %u, hop limit %u\n", c.chain_total, c.m_reach_front, n_ix, c.why_far, c.why_straddle, c.why_runlen, c.why_hops);
+        }
     }
     // dense frames (text): no chain at all, every output byte traced to its literal (see k_trace_copy)
-    hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 0u, res_gy);
+    hipLaunchKernelGGL(k_dense_gate, dim3(1), dim3(64), 0, st, ctl, gate, (const BlockOut*)tbl, (const ResultRec*)res, n_ix, 0u, res_gy);
     if (gate) {
         hipLaunchKernelGGL(k_build_postab, dim3(n_ix, res_gy), dim3(256), 0, st, d_index, (const BlockOut*)tbl, (const ResultRec*)res, n_ix,
-                           (const SeqDesc*)desc.p, (uint32_t*)postab.p, (uint32_t*)seqcnt.p);
+                           (const SeqDesc*)desc.p, (uint32_t*)postab.p, ctl);
         const uint64_t n_thr = (trace_span + IXT_TB - 1) / IXT_TB;
         // if the last index seen here was of a dense stream (the device decides about THIS one, but the
         // scratch - 4 bytes per output byte - and 18 launches are the host's to spend): one hop per byte, then pointer doubling
         const uint32_t pd_grid = (uint32_t)((trace_span / 4 + 255) / 256), pd_ngrp = pd_grid * 4u;      // (k_pd_round: a wave per 256 bytes)
-        const size_t pd_grp_at = (((size_t)trace_span * 4 + 255) & ~(size_t)255) + (((IXP_ROUNDS + 1) * IXP_STRIPES * 4 + 255) & ~(size_t)255);
-        if (r.doubling && !pdbuf.ensure(pd_grp_at + 2 * (size_t)pd_ngrp + 256)) {
+        Carve pd{pdbuf}; pd.take((size_t)trace_span * 4);              // a word per output byte, the bytes still open after each round, a byte pair per group
+        const size_t remaining_at = pd.take((IXP_ROUNDS + 1) * IXP_STRIPES * 4, 256), pd_grp_at = pd.take(2 * (size_t)pd_ngrp + 256, 256);
+        if (r.doubling && !pd.ensure()) {
             *path |= LZ4F_MI355X_PATH_DOUBLING;
-            uint32_t* remaining = (uint32_t*)((uint8_t*)pdbuf.p + (((size_t)trace_span * 4 + 255) & ~(size_t)255));
+            uint32_t* remaining = pd.at<uint32_t>(remaining_at);
             if (hipMemsetAsync(remaining, 0, (IXP_ROUNDS + 1) * IXP_STRIPES * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
             hipLaunchKernelGGL(k_pd_init, dim3((uint32_t)((n_thr + 255) / 256)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
-                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
+                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, ctl,
                                lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, (uint32_t*)pdbuf.p, remaining);
             for (uint32_t rd = 1; rd <= IXP_ROUNDS; rd++)
                 hipLaunchKernelGGL(k_pd_round, dim3(pd_grid), dim3(256), 0, st, j.d_dst, (uint32_t*)pdbuf.p, (const BlockOut*)tbl,
-                                   (const ResultRec*)res, n_ix, rd, remaining, (uint32_t*)seqcnt.p, (uint8_t*)pdbuf.p + pd_grp_at, pd_ngrp);
-            hipLaunchKernelGGL(k_pd_verdict, dim3(1), dim3(64), 0, st, (uint32_t*)seqcnt.p, (const uint32_t*)remaining);
+                                   (const ResultRec*)res, n_ix, rd, remaining, ctl, pd.at<uint8_t>(pd_grp_at), pd_ngrp);
+            hipLaunchKernelGGL(k_pd_verdict, dim3(1), dim3(64), 0, st, ctl, (const uint32_t*)remaining);
             if (iprof) { static uint32_t t[(IXP_ROUNDS + 1) * IXP_STRIPES]; if (prof_read(st, t, remaining, sizeof(t))) { fprintf(stderr, "doubling: bytes open after each round:"); for (uint32_t rd = 0; rd <= IXP_ROUNDS; rd++) { uint64_t sum = 0; for (uint32_t q = 0; q < IXP_STRIPES; q++) sum += t[rd * IXP_STRIPES + q]; fprintf(stderr, " %llu", (unsigned long long)sum); } fprintf(stderr, "\n"); } }
         } else {
             *path |= LZ4F_MI355X_PATH_TRACE_HOPS;
-            uint32_t* region_cnt = (uint32_t*)((uint8_t*)postab.p + (((size_t)(trace_span >> 6) * 4 + 255) & ~(size_t)255));
+            uint32_t* region_cnt = pt.at<uint32_t>(region_at);
             if (hipMemsetAsync(region_cnt, 0, ((size_t)(trace_span >> IXT_REGION_LOG) + 2) * 4, st) != hipSuccess) return make_err(LZ4F_ERROR_GENERIC);
             const uint32_t tc_wg = (uint32_t)((n_thr + 255) / 256);
             hipLaunchKernelGGL(k_trace_copy, dim3(std::min<uint32_t>(tc_wg, 8192u)), dim3(256), 0, st, j.d_frame, (uint64_t)j.frame_cap, j.d_dst, (const BlockOut*)tbl,
-                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, (uint32_t*)seqcnt.p,
+                               (const ResultRec*)res, n_ix, d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (const uint32_t*)postab.p, ctl,
                                lk & 1u, (uint32_t)j.block_size, (uint64_t)j.hist0, region_cnt, iprof ? 1u : 0u, tc_wg);
-            uint32_t t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (iprof && prof_read(st, t, (uint32_t*)seqcnt.p + 24, 32) && t[0]) fprintf(stderr, "traced: %llu turns for %u pieces (%u read from the output), deepest thread %u turns\n", (unsigned long long)t[2] | ((unsigned long long)t[3] << 32), t[4], t[5], t[6]);
+            IxCtl t;
+            if (iprof && prof_read(st, &t, ctl, sizeof(t)) && t.dense) fprintf(stderr, "traced: %llu turns for %u pieces (%u read from the output), deepest thread %u turns\n", t.t_turns, t.t_pieces, t.t_from_out, t.t_deepest);
         }
     }
     tick(8, true); tick(9, false);
     auto copy = [&](auto cfg) {
         using C = decltype(cfg);
         hipLaunchKernelGGL(k_copy_indexed<C>, dim3((n_ix + p.group - 1) / p.group), dim3(64 * C::WAVES), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)res, n_ix,
-                           d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, (uint32_t*)seqcnt.p, iprof, lk, done, p.group, (uint64_t)j.hist0, p.wait_ticks);
+                           d_index, (const SeqDesc*)desc.p, (const uint32_t*)dsrc, ctl, iprof, lk, done, p.group, (uint64_t)j.hist0, p.wait_ticks);
     };
     if (j.block_size <= (1u << 20)) copy(FzCfg<4>()); else copy(FzCfg<8>());
     tick(9, true);
-    uint32_t y[4] = {0, 0, 0, 0};
-    if (iprof && j.linked && prof_read(st, y, (uint32_t*)seqcnt.p + 20, 16)) fprintf(stderr, "indexed (linked): blocks that found the block in front at state 3: %u (of those, had to wait for all of it: %u); blocks with set-aside matches %u (block in front already done: %u)\n", y[0], y[1], y[2], y[3]);
+    IxCtl y;
+    if (iprof && j.linked && prof_read(st, &y, ctl, sizeof(y))) fprintf(stderr, "indexed (linked): blocks that found the block in front at state 3: %u (of those, had to wait for all of it: %u); blocks with set-aside matches %u (block in front already done: %u)\n", y.l_state3, y.l_state3_waited, y.l_setaside, y.l_front_done);
     hipLaunchKernelGGL(k_check_tails, dim3((n_ix + 255) / 256), dim3(256), 0, st, tbl, (const ResultRec*)res, n_ix, d_index,
-                       (const SeqDesc*)desc.p, (uint64_t)ix_seq_cap, j.block_size, (const uint32_t*)seqcnt.p);
+                       (const SeqDesc*)desc.p, (uint64_t)ix_seq_cap, j.block_size, (const IxCtl*)ctl);
     return 0;
 }
 
@@ -866,27 +894,29 @@ size_t lz4f_mi355x_engine::dec_generic(const DecompressJob& j, const DecodePlan&
         if (p.windowed) {
             *path |= LZ4F_MI355X_PATH_WINDOW;
             if (!indexed && seqcnt.ensure(256)) return make_err(LZ4F_ERROR_allocation_failed);
-            uint32_t* fb = (uint32_t*)seqcnt.p + (indexed ? 16 : 0);                  // (word 0 is the indexed kernels' flag)
+            // (behind the indexed kernels the verdict has its place in their control block; without them the buffer holds nothing else)
+            LinkedFallback* fb = indexed ? &((IxCtl*)seqcnt.p)->window : (LinkedFallback*)seqcnt.p;
             hipLaunchKernelGGL(k_decode_linked, dim3(1), dim3(64 * LK_WAVES), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl,
                                (const ResultRec*)res, n_max, j.block_size, j.hist0, fb, only_if);
-            only_if = fb;
-            uint32_t dbg[3] = {0, 0, 0};                                  // developer aid: why the windowed kernel stopped, if it did
-            if (sw.prof && prof_read(st, dbg, fb, 12)) fprintf(stderr, "k_decode_linked: fallback %u why %u block %u\n", dbg[0], dbg[1], dbg[2]);
+            only_if = &fb->gave_up;
+            LinkedFallback dbg;                                           // developer aid: why the windowed kernel stopped, if it did
+            if (sw.prof && prof_read(st, &dbg, fb, sizeof(dbg))) fprintf(stderr, "k_decode_linked: fallback %u why %u block %u\n", dbg.gave_up, dbg.why, dbg.block);
         }
         *path |= LZ4F_MI355X_PATH_FUSED;
         // big independent blocks and no index to go by: a look at the payload decides between the fused workgroups and - dense data -
         // the wave-per-block decoder (k_density_probe); both are launched, one of them returns at once
         if (!indexed && !j.linked && !sw.no_density_probe) {
             if (density.ensure(64)) return make_err(LZ4F_ERROR_allocation_failed);
-            hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)res, n_max, (uint32_t*)density.p);
+            Density* dens = (Density*)density.p;
+            hipLaunchKernelGGL(k_density_probe, dim3(1), dim3(64), 0, st, j.d_frame, (uint64_t)j.frame_cap, (const BlockOut*)tbl, (const ResultRec*)res, n_max, dens);
             if (p.relay) {
                 *path |= LZ4F_MI355X_PATH_WORKGROUP_PER_BLOCK;
                 hipLaunchKernelGGL((k_decode_blocks_relay<RELAY_W, RELAY_S>), dim3(n_max), dim3(64 * (RELAY_W + RELAY_S + 3)), 0, st, j.d_frame, j.d_dst, tbl, (const ResultRec*)res, n_max, (uint64_t)j.frame_cap,
-                                   (const uint32_t*)density.p);
+                                   (const uint32_t*)&dens->dense);
             } else
                 hipLaunchKernelGGL((k_decode_blocks<W>), dim3((n_max + W - 1) / W), dim3(64 * W), 0, st, j.d_frame, j.d_dst, j.dst_cap, tbl, (const ResultRec*)res,
-                                   n_max, 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap, (const uint32_t*)density.p);
-            only_if = (const uint32_t*)density.p + 1;
+                                   n_max, 0u, j.block_size, j.hist0, (uint64_t)j.frame_cap, (const uint32_t*)&dens->dense);
+            only_if = &dens->not_dense;
             *path |= LZ4F_MI355X_PATH_WAVE_PER_BLOCK;
         }
         auto fused = [&](auto cfg) {                                   // (a linked frame: one workgroup, in the 8-wave shape)
@@ -917,9 +947,9 @@ size_t lz4f_mi355x_engine::dec_finish(const DecompressJob& j, const DecodePlan& 
                            (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, (uint64_t)j.hist0, (uint8_t*)tight.p);
     }
     const bool check_here = n_max <= 64;                              // (the finishing wave looks at a few blocks itself: a launch less)
-    if (n_max && !check_here) hipLaunchKernelGGL(k_finish_check, dim3((n_max + 255) / 256), dim3(256), 0, st, (const BlockOut*)tbl, (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, (uint32_t*)bad.p);
+    if (n_max && !check_here) hipLaunchKernelGGL(k_finish_check, dim3((n_max + 255) / 256), dim3(256), 0, st, (const BlockOut*)tbl, (const ResultRec*)res, n_max, j.linked ? 1u : 0u, j.block_size, (FinishVerdict*)bad.p);
     hipLaunchKernelGGL(k_finish_decode, dim3(1), dim3(64), 0, st, j.d_dst, tbl, res, n_max, j.linked ? 1u : 0u, j.block_size,
-                       (const uint32_t*)bad.p, j.block_checksum ? 1u : 0u, path, ix_flags, check_here ? 1u : 0u, (uint64_t)j.dst_cap);
+                       (const FinishVerdict*)bad.p, j.block_checksum ? 1u : 0u, path, ix_flags, check_here ? 1u : 0u, (uint64_t)j.dst_cap);
     if (j.content_checksum && !p.given && !sw.no_content_check)      // (a whole frame was walked: res->consumed is behind its checksum word)
         hipLaunchKernelGGL(k_xxh32_content, dim3(1), dim3(64), 0, st, (const uint8_t*)j.d_dst, 0ull, (uint8_t*)j.d_frame, res, 1u);
     tick(7, true);
@@ -1007,14 +1037,6 @@ static dim3 batch_grid(uint64_t items, uint32_t per_wg, uint32_t most = BATCH_GR
 {
     return dim3((uint32_t)std::min<uint64_t>((items + per_wg - 1) / per_wg, most));
 }
-// a DevBuf carved into arrays: take() them in order, ensure(), then at()
-struct Carve {
-    DevBuf& buf;
-    size_t end = 0;
-    size_t take(size_t bytes, size_t align = 1) { const size_t at = (end + align - 1) & ~(align - 1); end = at + bytes; return at; }
-    int ensure() { return buf.ensure(end); }
-    template <typename T> T* at(size_t off) const { return (T*)((uint8_t*)buf.p + off); }
-};
 // what the decode and compress entry points pass along unchanged: the frames' spans in d_src and their windows in d_dst
 struct BatchSpans {
     uint32_t n_frames;

@@ -74,7 +74,7 @@ struct lz4f_mi355x_engine {
     lz4f::DevBuf pdbuf;                                    // dense frames by pointer doubling: a word per output byte
     lz4f::DevBuf tight;                                    // the last block when the caller's buffer leaves it less than a block of room (k_redo_tight_block)
     lz4f::DevBuf postab;                                   // dense frames: output position / 64 -> sequence (k_build_postab)
-    lz4f::DevBuf desc, seqcnt;                             // two-kernel decode: sequence descriptors, per-block counts
+    lz4f::DevBuf desc, seqcnt;                             // indexed decode: sequence descriptors; its control block (records.hpp: IxCtl)
     lz4f::DevBuf d_in, d_out;                              // staging for the host-pointer paths
     lz4f::DevBuf bframes, btable;                          // dev_decompressFrames: per-frame records + control words, the batch's block table
     lz4f::DevBuf mframes, mtable;                          // dev_measureFrames: per-frame records, windows, counts + control words, the batch's block table

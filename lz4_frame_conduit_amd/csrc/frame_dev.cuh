@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_ranges(const uint8_
 // mode 1: compare with the stored word; on mismatch flag the block (decompress)
 template <int WAVES_PER_WG>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks(uint8_t* frame, BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
-                                                                    uint32_t n_max, uint32_t mode, uint32_t* __restrict__ bad)
+                                                                    uint32_t n_max, uint32_t mode, FinishVerdict* __restrict__ verdict)
 {
     const uint32_t b = uni(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6));
     const uint32_t n = res ? res->n_blocks : n_max;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks(uint8_t* fra
     if (lane_id() == 0) {
         uint8_t* c = frame + off + len;
         if (mode == 0) st32le(c, h);
-        else if (rd32le(c) != h) atomicMin(bad, b);
+        else if (rd32le(c) != h) atomicMin(&verdict->ck_bad, b);
     }
 }
 
@@ -179,7 +179,7 @@ constexpr uint32_t XXH_LANE4_BELOW = 16384;     // fewer blocks than this: the f
 // with the scalar form
 template <int WAVES_PER_WG>
 __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks4(uint8_t* frame, BlockOut* __restrict__ table, const ResultRec* __restrict__ res,
-                                                                     uint32_t n_max, uint32_t mode, uint32_t* __restrict__ bad)
+                                                                     uint32_t n_max, uint32_t mode, FinishVerdict* __restrict__ verdict)
 {
     __shared__ __attribute__((aligned(16))) uint32_t park[WAVES_PER_WG][XXH_PARK / 4];
     const uint32_t wv = uni(threadIdx.x >> 6);
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_WG) void k_xxh32_blocks4(uint8_t* fr
     if (lane_id() == 0) {
         uint8_t* c = frame + off + len;
         if (mode == 0) st32le(c, h);
-        else if (rd32le(c) != h) atomicMin(bad, b);
+        else if (rd32le(c) != h) atomicMin(&verdict->ck_bad, b);
     }
 }
 
@@ -733,13 +733,13 @@ __global__ __launch_bounds__(256) void k_check_table(const BlockOut* __restrict_
     check_table_entries(table, n, frame_cap, dst_cap, block_size, bck, linked, res);
 }
 // The same for a table of a few blocks (the streaming API: one block per call) in ONE launch with what else a decode call begins with: the
-// result record's initial state and the verdict words of the finishing kernels (`w`: [0] block-checksum verdict, [1] first failed block,
-// [2] "something has to move", [4..5] sum of the sizes).  One workgroup: the record is set before anybody checks against it.
+// result record's initial state and the finishing kernels' verdict words (records.hpp: FinishVerdict, preset as the host presets it).
+// One workgroup: the record is set before anybody checks against it.
 __global__ __launch_bounds__(256) void k_begin_table_small(const BlockOut* __restrict__ table, uint32_t n, uint64_t frame_cap, uint64_t dst_cap, uint32_t block_size,
-                                                           uint32_t bck, uint32_t linked, ResultRec* res, uint32_t* __restrict__ w)
+                                                           uint32_t bck, uint32_t linked, ResultRec* res, FinishVerdict* __restrict__ verdict)
 {
     if (threadIdx.x == 0) { res->size = 0; res->consumed = 0; res->status = ST_OK; res->n_blocks = n; res->first_bad_block = 0xFFFFFFFFu; res->flags = 0u; }
-    if (threadIdx.x < 8) w[threadIdx.x] = threadIdx.x < 2 ? 0xFFFFFFFFu : 0u;
+    if (threadIdx.x < sizeof(FinishVerdict) / 4) ((uint32_t*)verdict)[threadIdx.x] = threadIdx.x < FINISH_ONES / 4 ? 0xFFFFFFFFu : 0u;
     __threadfence_block(); __syncthreads();
     check_table_entries(table, n, frame_cap, dst_cap, block_size, bck, linked, res);
 }
@@ -750,9 +750,9 @@ __global__ void k_set_block(BlockOut* t, BlockOut e) { if (threadIdx.x == 0 && b
 // per GiB) - where the wave-per-block decoder, whose lanes find the tokens, takes a fifth of that although it leaves most of the
 // machine idle.  So 64 lanes each read the first 512 payload bytes of a block (spread over the frame) and count sequences - not
 // the first one, which is the literal run of a block that has nothing to refer to yet (at 192 bytes it alone made text look sparse):
-// under 24 payload bytes per sequence -> flags[0] = 1 (dense: k_decode_blocks), else flags[1] = 1 (k_decode_blocks_fused).
+// under 24 payload bytes per sequence -> dense = 1 (k_decode_blocks), else not_dense = 1 (k_decode_blocks_fused).
 __global__ __launch_bounds__(64) void k_density_probe(const uint8_t* __restrict__ frame, uint64_t frame_cap, const BlockOut* __restrict__ table,
-                                                      const ResultRec* __restrict__ res, uint32_t n_max, uint32_t* __restrict__ flags)
+                                                      const ResultRec* __restrict__ res, uint32_t n_max, Density* __restrict__ d)
 {
     const uint32_t lane = lane_id();
     uint32_t seqs = 0, bytes = 0;
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(64) void k_density_probe(const uint8_t* __restrict_
     uint32_t st = seqs, bt = bytes;
 #pragma unroll
     for (int sft = 1; sft < 64; sft <<= 1) { st += __shfl_xor(st, sft); bt += __shfl_xor(bt, sft); }
-    if (lane == 0) { const bool dense = st != 0 && bt < 24u * st; flags[0] = dense ? 1u : 0u; flags[1] = dense ? 0u : 1u; flags[2] = st ? bt / st : 0u; }      // [2]: payload bytes per sequence in the sample (0: no sequence seen)
+    if (lane == 0) { const bool dense = st != 0 && bt < 24u * st; d->dense = dense ? 1u : 0u; d->not_dense = dense ? 0u : 1u; d->bytes_per_seq = st ? bt / st : 0u; }
 }
 
 // `hist0`: valid bytes directly in front of dst (streaming API: the previous blocks' last 64 KiB).
@@ -868,10 +868,9 @@ __global__ __launch_bounds__(64) void k_redo_tight_block(const uint8_t* __restri
 // What k_finish_decode has to know about the block table, found by a thread per block instead of one wave walking it 64
 // entries per dependent load (16384 blocks: 0.22 ms): the first failed block, whether every block already sits where its
 // predecessors end (independent frames: all blocks but the last decoded to full size, at b * blockSize), the sum of the sizes.
-//   w[0] block-checksum verdict (k_xxh32_blocks), w[1] first failed block (preset 0xFFFFFFFF), w[2] != 0: something has to move,
-//   w[4..5] sum of the decoded sizes (preset 0)
+// They go into the verdict words (records.hpp: FinishVerdict), next to the block-checksum verdict k_xxh32_blocks left there.
 __global__ __launch_bounds__(256) void k_finish_check(const BlockOut* __restrict__ table, const ResultRec* __restrict__ res, uint32_t n_max,
-                                                      uint32_t linked, uint32_t block_size, uint32_t* __restrict__ w)
+                                                      uint32_t linked, uint32_t block_size, FinishVerdict* __restrict__ verdict)
 {
     if (res->status != ST_OK) return;
     const uint32_t n = res->n_blocks < n_max ? res->n_blocks : n_max;
@@ -880,23 +879,23 @@ __global__ __launch_bounds__(256) void k_finish_check(const BlockOut* __restrict
     const uint32_t sz = in ? table[b].dst_size : 0u;
     const uint64_t at = in ? table[b].dst_off : 0ull;
     const bool bad = in && (int32_t)sz < 0;
-    if (bad) atomicMin(&w[1], b);
+    if (bad) atomicMin(&verdict->first_bad, b);
     const bool moves = in && !linked && (at != (uint64_t)b * block_size || (b + 1 < n && sz != block_size));
     const uint64_t mv = __ballot(moves);
     uint32_t sum = bad ? 0u : sz;                                      // (<= 64 * 4 MiB per wave: fits)
 #pragma unroll
     for (int sft = 1; sft < 64; sft <<= 1) sum += __shfl_xor(sum, sft);
     if (lane == 0) {
-        if (mv) atomicOr(&w[2], 1u);
-        if (sum) atomicAdd((unsigned long long*)(w + 4), (unsigned long long)sum);
+        if (mv) atomicOr(&verdict->moves, 1u);
+        if (sum) atomicAdd(&verdict->size_sum, (unsigned long long)sum);
     }
 }
 
 __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __restrict__ table, ResultRec* res, uint32_t n_max,
-                                                      uint32_t linked, uint32_t block_size, const uint32_t* __restrict__ bad_ck, uint32_t with_ck,
+                                                      uint32_t linked, uint32_t block_size, const FinishVerdict* __restrict__ verdict, uint32_t with_ck,
                                                       uint32_t plan = 0, const uint32_t* __restrict__ ix_flags = nullptr, uint32_t check_here = 0,
                                                       uint64_t dst_cap = ~0ull)
-{   // check_here (n_max <= 64): what k_finish_check leaves in bad_ck[1], [2], [4..5] is worked out by this wave itself - a launch less for calls of a few blocks
+{   // check_here (n_max <= 64): what k_finish_check leaves in the verdict words is worked out by this wave itself - a launch less for calls of a few blocks
     // which way the call went (lz4f_mi355x.h: LZ4F_MI355X_PATH_*): what the host launched, and whether the indexed kernels gave up
     // (and whether a list walk's list became the table: k_walk_verdict's bit, the only one that comes in with the record)
     if (lane_id() == 0) res->flags = (res->flags & (0xFFFu | (LZ4F_MI355X_PATH_WALK_DELIVERED << 12))) | (plan << 12) | ((ix_flags && *ix_flags) ? (LZ4F_MI355X_PATH_INDEX_DROPPED << 12) : 0u);
@@ -917,11 +916,11 @@ __global__ __launch_bounds__(64) void k_finish_decode(uint8_t* dst, BlockOut* __
 #pragma unroll
         for (int sft = 1; sft < 64; sft <<= 1) sum += __shfl_xor(sum, sft);
         w45 = sum;
-    } else { w1 = bad_ck[1]; w2 = bad_ck[2]; w45 = *(const uint64_t*)(bad_ck + 4); }
+    } else { w1 = verdict->first_bad; w2 = verdict->moves; w45 = verdict->size_sum; }
     // first failed block (k_finish_check)
     const uint32_t first_bad = w1 < n ? w1 : 0xFFFFFFFFu;
     const uint32_t bad_kind = first_bad != 0xFFFFFFFFu ? table[first_bad].dst_size : 0u;
-    const uint32_t ck = with_ck ? bad_ck[0] : 0xFFFFFFFFu;
+    const uint32_t ck = with_ck ? verdict->ck_bad : 0xFFFFFFFFu;
     if (ck != 0xFFFFFFFFu && ck <= first_bad) {
         if (lane == 0) { res->status = ST_BLOCKCK; res->first_bad_block = ck; }
         return;
