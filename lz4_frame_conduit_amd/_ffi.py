@@ -116,6 +116,11 @@ _SIGS = {
     "lz4f_mi355x_fdec_end": (c_size_t, [c_void_p, c_void_p, c_size_t]), "lz4f_mi355x_fdec_free": (None, [c_void_p]),
 }
 DECLARED_SYMBOLS = tuple(_SIGS)
+# development entry points: exported, not in the header; bound where the library has them (a variant build of an earlier tree may not)
+_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
+DEV_SIGS = {
+    "lz4f_mi355x_debug_e1_merge": (ctypes.c_int, [ctypes.c_int, c_void_p, c_void_p, c_void_p, _U32, _U64, _U32, _U32, _U32, _U32, _U32, c_void_p, c_void_p, c_void_p]),
+}
 
 _LIB = None
 
@@ -155,5 +160,9 @@ def lib():
         for name, (res, args) in _SIGS.items():
             f = getattr(L, name)          # AttributeError = a declared symbol is not exported
             f.restype, f.argtypes = res, args
+        for name, (res, args) in DEV_SIGS.items():
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = res, args
         _LIB = L
     return _LIB

@@ -189,5 +189,15 @@ __device__ __forceinline__ uint32_t dpp_excl_scan_max(uint32_t v)
     const uint32_t incl = dpp_incl_scan_max(v);
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
 }
+// exclusive sum: what the lanes below me add up to; total: all 64 (the inclusive scan's last lane, one v_readlane)
+__device__ __forceinline__ uint32_t dpp_excl_scan_add(uint32_t v, uint32_t& total)
+{
+    const uint32_t incl = dpp_incl_scan_add(v);
+    total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    return incl - v;
+}
+// the wave's sum / maximum, the same value to every lane (a scalar)
+__device__ __forceinline__ uint32_t dpp_wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)dpp_incl_scan_add(v), 63); }
+__device__ __forceinline__ uint32_t dpp_wave_max(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)dpp_incl_scan_max(v), 63); }
 
 }  // namespace lz4f

@@ -402,48 +402,41 @@ struct E1Walk {
         }
         return true;
     }
+    // the same without a branch, for records that are in registers already: `valid` false (no such record) leaves the walk where it is
+    __device__ __forceinline__ bool step_if(bool valid, uint64_t x, uint32_t& start, uint32_t& mlen)
+    {
+        const uint32_t s0 = pos + (uint32_t)(x & 0xFFFFFFu), end = s0 + (uint32_t)((x >> 24) & 0xFFFFFFu);
+        const bool strad = s0 < cov;
+        start = strad ? cov : s0; mlen = end - start;
+        pos = valid ? end : pos;
+        return valid & (end > cov) & (!strad | ((mlen >= MINMATCH) & (cov + MFLIMIT <= bend)));
+    }
 };
 
-__global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* __restrict__ src, EncGeom g, ChunkInfo* __restrict__ info,
-                                                                uint64_t* __restrict__ recs, uint64_t* __restrict__ scratch)
+// ---- a tile's slice lists -> its record list.  One wave does it (the last one), on its own, while the others are already
+// ---- searching the next tile: the lists and the per-slice words are double-buffered by tile parity.
+// s_end, s_n: the tile's per-slice words in LDS; spc: its slice lists as found; mode: the workgroup's mode word.  (A function of its
+// arguments, so that k_e1_merge_probe can run it on lists of a test's making.)
+// Round 7, FORM 1 (E1_V9; 0: the form before).  The merge is one wave's chain of waits - per-slice words read one LDS round trip at a time,
+// five wave-wide scans of six dependent ds_bpermute each on an LDS that fifteen searching waves keep busy, a returning atomic on the
+// pool's one bump pointer between the two walks - and the wave that merges is one of the sixteen that barrier 1 waits for.  Here: the
+// lane's eight words and eight counts are three wide reads asked for together, the bound `nslice` applied to the values; the scans
+// are DPP (no LDS); the pool is reserved for the records FOUND - an upper bound of the ones kept, known before the first walk - so
+// that the atomic's round trip lies under the list loads and the first walk (the few records the walk drops stay as a gap in the pool:
+// pass E2 finds a list by rec_offs[chunk] and ChunkInfo::nrec alone); and where no list of the tile has more than two records (one
+// ballot) both walks are straight-line code over the pairs already loaded.
+#ifndef E1_V9
+#define E1_V9 1
+#endif
+typedef uint32_t e1_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t e1_u32x2 __attribute__((ext_vector_type(2)));
+template <int FORM>
+__device__ __forceinline__ void e1_merge(const lds_u32* s_end, const lds_u8* s_n, const uint64_t* __restrict__ spc, const uint32_t c, const uint32_t ts, const uint32_t te,
+                                         const uint32_t bend, const uint32_t nslice, uint64_t* __restrict__ recs, ChunkInfo* __restrict__ info, const EncGeom& g, lds_u32* mode)
 {
-    __shared__ E1Shared sh;
-    constexpr uint32_t NT = 64 * E1_WAVES;
-    const uint32_t tid = threadIdx.x, lane = lane_id(), wave = uni(tid >> 6);
-    uint64_t* spec = scratch + (uint64_t)blockIdx.x * (2 * E1_NSLICE * E1_REC_PER_SLICE);      // this workgroup's slice lists (as found), for two tiles
-    const uint32_t c0 = blockIdx.x * g.tiles_per_wg;
-    const uint32_t c1 = (c0 + g.tiles_per_wg < g.n_chunks) ? c0 + g.tiles_per_wg : g.n_chunks;
-    // The chunks tile the stream: chunk c starts at first_off + c * 64 KiB.  Positions: the run's first tile starts at 65536,
-    // tile k at 65536 * (k + 1); up to 64 KiB of history sit in front of the first.  abs = org + pos.
-    const uint64_t s0 = g.first_off + (uint64_t)c0 * E1_TILE;
-    const uint64_t org = s0 - E1_TILE;                                   // (may wrap below zero: only ever used with pos >= the history's start)
-    uint32_t hist = 0, len0 = 0;
-    if (s0 < g.src_size) {
-        const uint64_t bstart0 = g.first_off + (uint64_t)(c0 / g.chunks_per_block) * g.block_size;
-        const uint64_t bend0 = (bstart0 + g.block_size < g.src_size) ? bstart0 + g.block_size : g.src_size;
-        const uint64_t low_abs = g.linked ? 0 : bstart0;
-        hist = (uint32_t)((s0 - low_abs < E1_TILE) ? s0 - low_abs : E1_TILE);
-        len0 = (uint32_t)((bend0 - s0 < E1_TILE) ? bend0 - s0 : E1_TILE);
-    }
-    const uint32_t hist0 = E1_TILE - hist;                               // first valid position
-    for (uint32_t i = tid; i < (1u << E1_HASH_LOG) / 2; i += NT) ((uint32_t*)sh.table)[i] = 0;
-    for (uint32_t i = tid; i < (1u << E1_HASH_LOG) / 4; i += NT) ((uint32_t*)sh.tags)[i] = 0;
-    e1_fill(sh, src, org, hist0, E1_TILE + len0, tid);                   // history + first tile
-    __syncthreads();
-    // the history's positions into the table, every seed_stride-th, in position order (later ones win)
-    // (deterministic parse: by one wave, so that which of two positions with one slot stays is a matter of order, not of timing)
-    const uint32_t nt_seed = (g.e1_solo & 1u) ? WAVE : NT;
-    if (tid < nt_seed) for (uint32_t p = hist0 + tid * g.seed_stride; p < E1_TILE; p += nt_seed * g.seed_stride)
-        if (p + 4 <= E1_TILE + len0) { const uint32_t hv = e1_mix(e1_ld32(sh.ring, p)); sh.table[e1_slot(hv)] = (uint16_t)p; sh.tags[e1_slot(hv)] = (uint8_t)e1_tag(hv); }
-
-    // ---- a tile's slice lists -> its record list.  One wave does it (the last one), on its own, while the others are already
-    // ---- searching the next tile: the lists and the per-slice words are double-buffered by tile parity.
-    auto merge = [&](uint32_t c, uint32_t par, uint32_t ts, uint32_t te, uint32_t bend, uint32_t nslice) {
-        constexpr uint32_t SP = E1_NSLICE / WAVE;                        // consecutive slices per lane
-        const uint32_t* s_end = sh.s_end[par];
-        const uint8_t* s_n = sh.s_n[par];
-        const uint64_t* spc = spec + (size_t)par * (E1_NSLICE * E1_REC_PER_SLICE);
-        const uint32_t s_lo = lane * SP;
+    constexpr uint32_t SP = E1_NSLICE / WAVE;                            // consecutive slices per lane
+    const uint32_t lane = lane_id(), s_lo = lane * SP;
+    if constexpr (FORM == 0) {
         // what the slices in front of a slice have covered = the maximum of their last match ends
         uint32_t lmax = 0;
 #pragma unroll
@@ -535,9 +528,188 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
         if (lane == 0) {
             if (room) { ci->nrec = ktot; ci->first_lit = tile_first; ci->tail_lit = te - kmax; ci->body_size = btot; }
             else      { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = te - ts; ci->body_size = 0; }      // no room for the list: the tile goes out as literals
-            sh.mode = (uint64_t)ktot * 64 > (uint64_t)(te - ts) ? 2u : 1u;      // how the next tiles hand out their slices
+            *mode = (uint64_t)ktot * 64 > (uint64_t)(te - ts) ? 2u : 1u;      // how the next tiles hand out their slices
         }
-    };
+    } else {
+        static_assert(SP == 8, "a lane's words are two 16-byte reads, its counts one 8-byte read");
+        // the lane's eight match ends and eight counts: three reads of consecutive addresses, asked for together, no branch in front
+        // (every lane reads its eight - the arrays hold E1_NSLICE entries whatever nslice is - and what lies at or behind nslice, stale
+        // words of an earlier tile, is zeroed in the registers)
+        typedef const __attribute__((address_space(3))) e1_u32x4 lds_x4;
+        typedef const __attribute__((address_space(3))) e1_u32x2 lds_x2;
+        const e1_u32x4 ea = *(lds_x4*)(s_end + s_lo), eb = *(lds_x4*)(s_end + s_lo + 4);
+        const e1_u32x2 nb = *(lds_x2*)(s_n + s_lo);
+        uint32_t e[SP] = {ea.x, ea.y, ea.z, ea.w, eb.x, eb.y, eb.z, eb.w}, nn[SP];
+        uint32_t lmax = 0, found = 0, nmax = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SP; j++) {
+            const bool in = s_lo + j < nslice;
+            e[j] = in ? e[j] : 0u;
+            nn[j] = in ? ((j < 4 ? nb.x : nb.y) >> (8u * (j & 3u))) & 0xFFu : 0u;
+            lmax = e[j] > lmax ? e[j] : lmax; found += nn[j]; nmax = nn[j] > nmax ? nn[j] : nmax;
+        }
+        // (all of a lane's lists are requested at once - the first two records of each, which is all that most lists have)
+        // (a list's address: the tile's uniform base + a 32-bit byte offset that the compiler takes as made here - left to itself hipcc
+        // computes eight 64-bit pointers and eight positions per lane once, in front of the tile loop, and keeps them in scratch while
+        // the search runs: 17 more spilled registers for values that cost a shift each)
+        constexpr uint32_t LIST_BYTES = E1_REC_PER_SLICE * 8u;
+        const uint8_t* spcb = (const uint8_t*)spc;
+        uint32_t lo8 = s_lo * LIST_BYTES, p0 = ts + s_lo * E1_SLICE;
+        asm volatile("" : "+v"(lo8), "+v"(p0));
+        ulonglong2 x01[SP];
+#pragma unroll
+        for (uint32_t j = 0; j < SP; j++) x01[j] = *(const ulonglong2*)(spcb + (nn[j] ? lo8 + j * LIST_BYTES : 0u));
+        __builtin_amdgcn_sched_barrier(0);
+        // the list's place in the pool, for the records found: asked for behind the list loads, needed by the second walk's first store
+        const uint32_t rsv = dpp_wave_sum(found);
+        unsigned long long base = 0;
+        if (lane == 0 && rsv) base = atomicAdd(rec_ctl(recs), (unsigned long long)rsv);
+        __builtin_amdgcn_sched_barrier(0);
+        const bool longl = __ballot(nmax > 2u) != 0ull;                  // (wave-uniform) some list goes on behind its first pair
+        // what the slices in front of a slice have covered = the maximum of their last match ends
+        uint32_t cov0 = dpp_excl_scan_max(lmax);
+        if (cov0 < ts) cov0 = ts;
+        // One walk over the lane's lists, in order; sink(kept, start, length, record) sees every record where the lists are short -
+        // straight-line code over the sixteen records in x01[], `kept` false for one that is dropped or is not there - and the kept ones
+        // where a list is longer (dense tiles: the loop with its pair prefetch).
+        auto walk = [&](auto&& sink) __attribute__((always_inline)) {
+            uint32_t cov = cov0;
+            if (!longl) {
+#pragma unroll
+                for (uint32_t j = 0; j < SP; j++) {
+                    // (a record that no lane has is jumped over on the scalar unit: on rows of 1 KiB a helping is a lane's eight slices and
+                    // finds one record, so fifteen of the sixteen are nobody's - and an instruction of this wave is issued every five cycles or
+                    // so beside fifteen searching ones: all sixteen looked at in all lanes made the merge longer than the waits it replaced)
+                    E1Walk w{p0 + j * E1_SLICE, cov, bend};
+#pragma unroll
+                    for (uint32_t h = 0; h < 2; h++) {
+                        if (__ballot(h < nn[j]) == 0ull) break;
+                        const uint64_t x = h ? x01[j].y : x01[j].x;
+                        uint32_t st, ml;
+                        const bool k = w.step_if(h < nn[j], x, st, ml);
+                        sink(k, st, ml, x);
+                    }
+                    cov = e[j] > cov ? e[j] : cov;
+                }
+            } else {
+#pragma unroll
+                for (uint32_t j = 0; j < SP; j++) {
+                    const uint32_t n = nn[j];
+                    E1Walk w{p0 + j * E1_SLICE, cov, bend};
+                    // (two records per load, the next pair on its way while this one is looked at: a dense tile has ~10 records per list,
+                    // and one at a time that was 130 dependent memory round trips per lane and merge - as long as the parse of the tile)
+                    ulonglong2 cur = x01[j];
+                    for (uint32_t r = 0; r < n; r += 2) {
+                        ulonglong2 nx2 = cur;
+                        if (r + 2 < n) nx2 = *(const ulonglong2*)(spcb + (lo8 + j * LIST_BYTES + (r + 2) * 8u));
+#pragma unroll
+                        for (uint32_t h = 0; h < 2; h++) {
+                            if (r + h >= n) break;
+                            const uint64_t x = h ? cur.y : cur.x;
+                            uint32_t st, ml;
+                            if (!w.step(x, st, ml)) continue;
+                            sink(true, st, ml, x);
+                        }
+                        cur = nx2;
+                    }
+                    cov = e[j] > cov ? e[j] : cov;
+                }
+            }
+        };
+        // first walk: how many records are kept, where the lane's first kept one starts, the encoded size of its others
+        uint32_t kept = 0, f_start = 0, f_mlen = 0, last_end = 0, body = 0;
+        walk([&](const bool k, const uint32_t st, const uint32_t ml, const uint64_t) __attribute__((always_inline)) {
+            const bool first = k && kept == 0;
+            f_start = first ? st : f_start; f_mlen = first ? ml : f_mlen;
+            body += (k && kept != 0) ? seq_size(st - last_end, ml) : 0u;
+            last_end = k ? st + ml : last_end; kept += k ? 1u : 0u;
+        });
+        const uint32_t incl_end = dpp_incl_scan_max(last_end);
+        uint32_t prev_end = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl_end, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);      // end of the last kept match in front of this lane's slices
+        uint32_t kmax = (uint32_t)__builtin_amdgcn_readlane((int)incl_end, 63);
+        uint32_t ktot;
+        const uint32_t off = dpp_excl_scan_add(kept, ktot);              // my place in the list
+        if (prev_end < ts) prev_end = ts;
+        if (kmax < ts) kmax = ts;
+        const uint32_t f_lit = kept ? f_start - prev_end : 0u;
+        body += kept ? seq_size(f_lit, f_mlen) : 0u;
+        const uint32_t btot = dpp_wave_sum(body);
+        const uint64_t has = __ballot(kept != 0);
+        const uint32_t tile_first = has ? (uint32_t)__builtin_amdgcn_readlane(f_lit, (int)__builtin_ctzll(has)) : 0u;
+        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)base);
+        const bool room = base + rsv <= g.rec_pool;                      // (wave-uniform; on what was reserved: nothing is written behind it)
+        if (!room && lane == 0) atomicAdd(rec_ctl(recs) + 1, 1ull);
+        // second walk: the kept records, literal runs counted from the kept match in front
+        if (room) {
+            if (lane == 0) rec_offs(recs)[c] = (uint32_t)base;
+            uint64_t* out = rec_pool_of(recs, g) + base + off;
+            uint32_t jn = 0, le = prev_end;
+            walk([&](const bool k, const uint32_t st, const uint32_t ml, const uint64_t x) __attribute__((always_inline)) {
+                if (k) out[jn] = pack_rec(st - le, ml, (uint32_t)(x >> 48));
+                jn += k ? 1u : 0u; le = k ? st + ml : le;
+            });
+        }
+        ChunkInfo* ci = info + c;
+        if (lane == 0) {
+            if (room) { ci->nrec = ktot; ci->first_lit = tile_first; ci->tail_lit = te - kmax; ci->body_size = btot; }
+            else      { ci->nrec = 0; ci->first_lit = 0; ci->tail_lit = te - ts; ci->body_size = 0; }      // no room for the list: the tile goes out as literals
+            *mode = (uint64_t)ktot * 64 > (uint64_t)(te - ts) ? 2u : 1u;      // how the next tiles hand out their slices
+        }
+    }
+}
+
+// (development, tests/test_gpu_e1_merge.py) one wave: caller-given per-slice words into LDS, then the merge of either form on caller-given lists
+template <int FORM>
+__global__ __launch_bounds__(64) void k_e1_merge_probe(const uint32_t* __restrict__ s_end_in, const uint8_t* __restrict__ s_n_in, const uint64_t* __restrict__ lists, EncGeom g,
+                                                       uint32_t c, uint32_t ts, uint32_t te, uint32_t bend, uint32_t nslice, ChunkInfo* __restrict__ info,
+                                                       uint64_t* __restrict__ recs, uint32_t* __restrict__ mode_out)
+{
+    __shared__ alignas(16) uint32_t s_end[E1_NSLICE];
+    __shared__ alignas(16) uint8_t s_n[E1_NSLICE];
+    __shared__ uint32_t mode;
+    for (uint32_t i = threadIdx.x; i < E1_NSLICE; i += 64) {
+        s_end[i] = s_end_in[i];
+        // (a helping's list runs on into the next slices' slots; capped where the lists end, so that nothing is read behind them)
+        const uint32_t n = s_n_in[i], cap = (E1_NSLICE - i) * E1_REC_PER_SLICE; s_n[i] = (uint8_t)(n < cap ? n : cap);
+    }
+    if (threadIdx.x == 0) mode = 0;
+    __syncthreads();
+    e1_merge<FORM>((const lds_u32*)s_end, (const lds_u8*)s_n, lists, c, ts, te, bend, nslice, recs, info, g, (lds_u32*)&mode);
+    __syncthreads();
+    if (threadIdx.x == 0) *mode_out = mode;
+}
+
+__global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* __restrict__ src, EncGeom g, ChunkInfo* __restrict__ info,
+                                                                uint64_t* __restrict__ recs, uint64_t* __restrict__ scratch)
+{
+    __shared__ E1Shared sh;
+    constexpr uint32_t NT = 64 * E1_WAVES;
+    const uint32_t tid = threadIdx.x, lane = lane_id(), wave = uni(tid >> 6);
+    uint64_t* spec = scratch + (uint64_t)blockIdx.x * (2 * E1_NSLICE * E1_REC_PER_SLICE);      // this workgroup's slice lists (as found), for two tiles
+    const uint32_t c0 = blockIdx.x * g.tiles_per_wg;
+    const uint32_t c1 = (c0 + g.tiles_per_wg < g.n_chunks) ? c0 + g.tiles_per_wg : g.n_chunks;
+    // The chunks tile the stream: chunk c starts at first_off + c * 64 KiB.  Positions: the run's first tile starts at 65536,
+    // tile k at 65536 * (k + 1); up to 64 KiB of history sit in front of the first.  abs = org + pos.
+    const uint64_t s0 = g.first_off + (uint64_t)c0 * E1_TILE;
+    const uint64_t org = s0 - E1_TILE;                                   // (may wrap below zero: only ever used with pos >= the history's start)
+    uint32_t hist = 0, len0 = 0;
+    if (s0 < g.src_size) {
+        const uint64_t bstart0 = g.first_off + (uint64_t)(c0 / g.chunks_per_block) * g.block_size;
+        const uint64_t bend0 = (bstart0 + g.block_size < g.src_size) ? bstart0 + g.block_size : g.src_size;
+        const uint64_t low_abs = g.linked ? 0 : bstart0;
+        hist = (uint32_t)((s0 - low_abs < E1_TILE) ? s0 - low_abs : E1_TILE);
+        len0 = (uint32_t)((bend0 - s0 < E1_TILE) ? bend0 - s0 : E1_TILE);
+    }
+    const uint32_t hist0 = E1_TILE - hist;                               // first valid position
+    for (uint32_t i = tid; i < (1u << E1_HASH_LOG) / 2; i += NT) ((uint32_t*)sh.table)[i] = 0;
+    for (uint32_t i = tid; i < (1u << E1_HASH_LOG) / 4; i += NT) ((uint32_t*)sh.tags)[i] = 0;
+    e1_fill(sh, src, org, hist0, E1_TILE + len0, tid);                   // history + first tile
+    __syncthreads();
+    // the history's positions into the table, every seed_stride-th, in position order (later ones win)
+    // (deterministic parse: by one wave, so that which of two positions with one slot stays is a matter of order, not of timing)
+    const uint32_t nt_seed = (g.e1_solo & 1u) ? WAVE : NT;
+    if (tid < nt_seed) for (uint32_t p = hist0 + tid * g.seed_stride; p < E1_TILE; p += nt_seed * g.seed_stride)
+        if (p + 4 <= E1_TILE + len0) { const uint32_t hv = e1_mix(e1_ld32(sh.ring, p)); sh.table[e1_slot(hv)] = (uint16_t)p; sh.tags[e1_slot(hv)] = (uint8_t)e1_tag(hv); }
 
     if (tid == 0) { sh.mode = 0; sh.cov = E1_TILE; sh.hits = 0; sh.first = 0; sh.next = E1_ALIGN ? 0 : 1; sh.pieces[0] = 0; sh.pieces[1] = 0; sh.tail_d[0] = 0; sh.tail_d[1] = 0; }
     if (tid < 16) sh.cur[tid] = 0;
@@ -546,7 +718,18 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
     bool pend = false;                                                   // a tile whose lists are not merged yet
     uint32_t p_c = 0, p_par = 0, p_ts = 0, p_te = 0, p_bend = 0, p_ns = 0;
     __syncthreads();                                                     // the first tile is in the ring, the table is seeded, counters are set
-    for (uint32_t c = c0; c < c1; c++) {
+    for (uint32_t c = c0; ; c++) {
+        // ---- the tile before: its slice lists -> its record list.  One wave does it (the last one), on its own, while the others are already
+        // ---- searching this tile; behind the run's last tile the loop comes here once more, so that the merge is in the kernel once
+        E1DBG(const unsigned long long q0 = clock64();)
+        if (pend && wave == E1_WAVES - 1) {
+            *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = 0xFFFFFFFFu;     // (holds no slice meanwhile; the one it takes afterwards lies beyond all that are held)
+            e1_merge<E1_V9>((const lds_u32*)sh.s_end[p_par], (const lds_u8*)sh.s_n[p_par], spec + (size_t)p_par * (E1_NSLICE * E1_REC_PER_SLICE), p_c, p_ts, p_te, p_bend, p_ns,
+                            recs, info, g, (lds_u32*)&sh.mode);
+        }
+        pend = false;
+        if (c >= c1) break;
+        E1DBG(const unsigned long long q1 = clock64();)
         const uint32_t k = c - c0;
         const uint32_t ts = E1_TILE * (k + 1), par = k & 1u;
         const uint32_t blk = c / g.chunks_per_block;
@@ -578,13 +761,6 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
         }
         const bool nlen_full = nlen == E1_TILE;
 
-        E1DBG(const unsigned long long q0 = clock64();)
-        if (pend && wave == E1_WAVES - 1) {                              // (the others are searching already)
-            *(lane == 0 ? &sh.cur[wave] : &sh.idle[lane]) = 0xFFFFFFFFu;     // (holds no slice meanwhile; the one it takes afterwards lies beyond all that are held)
-            merge(p_c, p_par, p_ts, p_te, p_bend, p_ns);
-        }
-
-        E1DBG(const unsigned long long q1 = clock64();)
         // ---- slices, in order, to whichever wave is free ----
         // a match may start at p iff p + 4 <= te and p + MFLIMIT <= bend; it may end at min(te, bend - LASTLIT).
         // Blocks shorter than MFLIMIT + 1 bytes are literals only (Appendix A.2).
@@ -1001,7 +1177,6 @@ __global__ __launch_bounds__(64 * E1_WAVES) void k_find_matches(const uint8_t* _
         }
         E1DBG(if (blockIdx.x == 0 && lane == 0) { unsigned long long* d = (unsigned long long*)&scratch[E1_DBG_AT + 16 + wave * 8]; d[0] += q1 - q0; d[1] += q2 - q1; d[2] += q3 - q2; d[3] += q4 - q3; d[4] += q5 - q4; d[5] += clock64() - q5; d[6] += 1; unsigned long long* f = (unsigned long long*)&scratch[E1_DBG_AT + 160 + wave * 6]; f[0] += a_deq; f[1] += a_probe; f[2] += a_hit; f[3] += n_deq; f[4] += n_step; f[5] += n_hit; })
     }
-    if (pend && wave == E1_WAVES - 1) merge(p_c, p_par, p_ts, p_te, p_bend, p_ns);
 }
 
 // ------------------------------- pass S --------------------------------------------------------

@@ -1780,4 +1780,20 @@ size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const ui
     return 0;
 }
 
+// developer aid (tests/test_gpu_e1_merge.py; not in the header): pass E1's merge of one tile, either form (0: before round 7, 1: E1_V9), on
+// caller-given device buffers - s_end[512] and s_n[512] (the per-slice words), lists (512 x 32 records, as the search leaves them), a
+// record workspace for n_chunks chunks and a pool of rec_pool records (8 * (rec_pool_at(n_chunks) + rec_pool) bytes), n_chunks ChunkInfo
+// and the mode word.  Runs on the device's null stream and waits.  0: done; 1: an argument is out of range; 2: a HIP error
+__attribute__((visibility("default"))) int lz4f_mi355x_debug_e1_merge(int form, const uint32_t* d_s_end, const uint8_t* d_s_n, const uint64_t* d_lists, uint32_t n_chunks,
+                                                                      uint64_t rec_pool, uint32_t c, uint32_t ts, uint32_t te, uint32_t bend, uint32_t nslice, void* d_info,
+                                                                      uint64_t* d_recs, uint32_t* d_mode)
+{
+    if ((form != 0 && form != 1) || !d_s_end || !d_s_n || !d_lists || !d_info || !d_recs || !d_mode) return 1;
+    if (c >= n_chunks || nslice > E1_NSLICE || te < ts || te - ts > E1_TILE || (uint64_t)nslice * E1_SLICE < te - ts || bend < te || ts > 0x7FFF0000u) return 1;
+    EncGeom g{}; g.n_chunks = n_chunks; g.rec_pool = rec_pool;
+    if (form) hipLaunchKernelGGL((k_e1_merge_probe<1>), dim3(1), dim3(64), 0, 0, d_s_end, d_s_n, d_lists, g, c, ts, te, bend, nslice, (ChunkInfo*)d_info, d_recs, d_mode);
+    else      hipLaunchKernelGGL((k_e1_merge_probe<0>), dim3(1), dim3(64), 0, 0, d_s_end, d_s_n, d_lists, g, c, ts, te, bend, nslice, (ChunkInfo*)d_info, d_recs, d_mode);
+    return (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess) ? 0 : 2;
+}
+
 }  // extern "C"
