@@ -2,7 +2,8 @@
 
 Sizes are held to liblz4's at the same level, as recorded in tests/golden/hc_sizes.json (tools/mint_hc_sizes.py); liblz4 itself is never
 called here.  Every frame must decode byte-exact through the oracle and this library's decoders, and the bytes must be a function of
-the input, its framing and the level alone, whichever entry point, engine, switch or device count made them."""
+the input, its framing and the level alone, whichever entry point, engine, switch or device count made them.
+Which bytes they are - the parse itself, match for match - is tests/test_gpu_hc_model.py's, against the model of tests/hc_model.py."""
 import ctypes
 import hashlib
 import json
