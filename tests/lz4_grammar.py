@@ -27,6 +27,9 @@ Families (the name's first word):
             above planted as a block's first sequence, at its end, straddling 64-byte payload windows and spread over the
             block so that the stretch starts of the stretch-parallel self-index fall on them
 Frames are rebuilt identically from the case name on any machine (numpy's PCG64 seeded by the name's CRC32).
+
+This corpus aims at parsers and bounds checks.  Copy DEPENDENCIES - when a match may be copied and where its bytes come from, in
+every decoder - live in match_dep_cases.py, which builds on Frame / Block / lz4_seq of this module.
 """
 from __future__ import annotations
 
