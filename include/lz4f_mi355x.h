@@ -800,6 +800,65 @@ LZ4F_MI355X_API size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e,
 LZ4F_MI355X_API size_t lz4f_mi355x_splitFrames(const void* src, size_t srcBytes, uint32_t max_frames, uint64_t* src_off,
                                                lz4f_mi355x_result* split);
 
+/* BATCH TRAIN: a dictionary made from a batch of samples on the device - the one step of the dictionary's life that liblz4 leaves to
+ * `zstd --train` on a host.  The samples are spans of one device buffer, as the inputs of lz4f_mi355x_dev_compressFrames are; the
+ * result goes straight into lz4f_mi355x_dev_createCDict[HC] on the same stream.  Conventions as for the other batch calls: sample i is
+ * d_src[src_off[i] .. src_off[i+1]); d_src and d_dict in DEVICE memory at any byte address; d_src_off (n_samples + 1 uint64) in DEVICE
+ * memory, 8-byte aligned; d_result (one record, DEVICE memory) may be NULL; srcBytes and dictSize are host values; asynchronous on the
+ * engine's stream, no host synchronisation, no device->host copy.  Spans that overlap are legal.  Nothing is written but
+ * d_dict[0 .. dictSize), the record and the engine's workspace; nothing is read outside the valid spans and the offsets.
+ *   - params (NULL: all defaults; a field that is 0: its default): k, the segment length in bytes, d <= k <= 4096
+ *     (LZ4F_MI355X_TRAIN_K); d, the bytes hashed at a position, 4, 6 or 8 (LZ4F_MI355X_TRAIN_D); f, the bits of the hash,
+ *     16 <= f <= 22 (LZ4F_MI355X_TRAIN_F); rounds, 1 <= rounds <= 64 (LZ4F_MI355X_TRAIN_ROUNDS); reserved stays 0.
+ *   - THE DEFINITION.  The device's bytes are this sequential statement's, byte for byte:
+ *     1. The corpus C is the valid samples back to back, in index order; N its length.  A span with src_off[i] > src_off[i+1] or an end
+ *        past srcBytes contributes nothing.  A sample is taken only while the running total stays <= srcBytes: the first that does not
+ *        fit, and all behind it, are dropped (only overlapping spans get there).  Dmers and segments may cross the samples' seams.
+ *     2. M = N - d + 1 dmers (N < d: the dictionary is all zeros, used = 0, no round is run).  For j < M,
+ *            h(j) = ((the d bytes at C[j] as a little-endian u64) * 0x9E3779B185EBCA87 mod 2^64) >> (64 - f)
+ *        and freq[x] is the number of j with h(j) == x.
+ *     3. m = min(k - d + 1, M) dmers make a window; the window starts are p in [0, W), W = M - m + 1.  prev(j) is the largest j' < j
+ *        with h(j') == h(j), or -1.  score(p; F) = the sum of F[h(j)] over the j in [p, p + m) with prev(j) < p: F over the window's
+ *        DISTINCT hashes.
+ *     4. E = max(1, min(dictSize / k, W)) epochs; epoch e holds the starts [e * W / E, (e + 1) * W / E), by integer division.
+ *     5. tail = dictSize.  For each of up to `rounds` rounds: S = a snapshot of freq; every epoch picks p_e, the lowest p of the epoch
+ *        that maximises score(p; S); then, for e = 0 .. E - 1 in order: the epoch is skipped if score(p_e; S) == 0, and skipped as
+ *        STALE if 2 * score(p_e; freq) < score(p_e; S) (it picks afresh in the next round); otherwise the window is trimmed to
+ *        [s0, s1], its first and last j with freq[h(j)] > 0, the segment is C[s0 .. s1 + d), take = min(its length, tail), its
+ *        first `take` bytes are copied to d_dict[tail - take .. tail), tail -= take, and freq[h(j)] = 0 for every j in [s0, s1];
+ *        the commits stop when tail reaches 0.  The rounds end when tail == 0 or when a round appended nothing.
+ *     Picking every segment in parallel against one snapshot would fill the dictionary with the same hot content once per epoch; the
+ *     exact serial order needs a launch per segment.  Scores only fall as counts are zeroed, so the snapshot score bounds the live
+ *     one from above: deferring the picks that lost half of theirs keeps the result within a few per cent of the serial order's.
+ *   - Output: exactly dictSize bytes.  The trained content is right-aligned, d_dict[dictSize - used .. dictSize), the best segments
+ *     last - where an encoder's offsets are shortest - and the front is zero-filled: (d_dict, dictSize) go into
+ *     lz4f_mi355x_dev_createCDict[HC] as they are, no size read back.
+ *   - d_result: size = used; consumed = N; n_blocks = the segments appended; first_bad_block = the first sample whose span is invalid
+ *     (0xFFFFFFFF: none); status = 0; flags = LZ4F_MI355X_PATH_BATCH << 12, and in the low 8 bits the rounds that were run.
+ *   - The workspace, from the arguments alone, grown as needed: 7 bytes per byte of srcBytes (the corpus, 4 bytes of hash and 2 of
+ *     look-back per position), 8 per sample, 4 << f for the counts, 8 * max(1, dictSize / k) for the picks, and less than 1 KiB.
+ *   - Launches: one fill, 4 to set up, and 2 * rounds - a function of `rounds` alone, never of n_samples, the bytes or dictSize / k;
+ *     the kernels of a round that is no longer needed return at once.  No kernel waits on another workgroup.  The look-back costs up
+ *     to k compares per position, once; a round is O(N), and its commit one workgroup's walk over the epochs.
+ *   - The call itself fails, and enqueues nothing, on: a null engine; parameters out of range (ERROR_GENERIC, lz4f_mi355x_last_error
+ *     names the field); dictSize > 65536 (ERROR_GENERIC: LZ4 never reads further back); srcBytes >= 2^31 (ERROR_srcSize_tooLarge);
+ *     then, with n_samples > 0 and dictSize > 0, a null d_src, d_src_off or d_dict, or a failed allocation.  n_samples == 0 or
+ *     dictSize == 0 returns 0 and enqueues nothing.
+ *   - NOT COVERED: samples in host memory (copy them up: there is no host-pointer form); entropy tables (LZ4 has none: the dictionary
+ *     is raw content); a dictID - the caller's to choose, in prefs.frameInfo.dictID or a dictionary set's. */
+#define LZ4F_MI355X_TRAIN_K      64u        /* the defaults: segment bytes */
+#define LZ4F_MI355X_TRAIN_D      8u         /*   bytes hashed at a position */
+#define LZ4F_MI355X_TRAIN_F      18u        /*   bits of the hash */
+#define LZ4F_MI355X_TRAIN_ROUNDS 16u        /*   rounds at most */
+#define LZ4F_MI355X_TRAIN_TILE      4096u   /* informational: the corpus positions a workgroup of the training kernels takes at a time */
+#define LZ4F_MI355X_TRAIN_SCAN_TILE 1024u   /* informational: the samples a step of the offsets' scan takes */
+typedef struct { uint32_t k, d, f, rounds; uint32_t reserved[4]; } lz4f_mi355x_train_params;   /* 0 = default, each field */
+LZ4F_MI355X_API size_t lz4f_mi355x_dev_trainDict(lz4f_mi355x_engine* e, uint32_t n_samples,
+                                                 const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                                 void* d_dict, size_t dictSize,
+                                                 const lz4f_mi355x_train_params* params /* NULL: defaults */,
+                                                 lz4f_mi355x_result* d_result /* may be NULL */);
+
 /* Per-block XXH32 of n_blocks byte ranges: d_out[i] = XXH32(d_base + off[i], len[i], 0) (row a5). */
 LZ4F_MI355X_API size_t lz4f_mi355x_dev_xxh32(lz4f_mi355x_engine* e, const void* d_base, const uint64_t* d_off,
                                              const uint32_t* d_len, uint32_t n_blocks, uint32_t* d_out);

@@ -36,6 +36,10 @@ class Block(ctypes.Structure):              # lz4f_mi355x_block
     _fields_ = [("src_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64), ("word", ctypes.c_uint32), ("dst_size", ctypes.c_uint32)]
 
 
+class TrainParams(ctypes.Structure):        # lz4f_mi355x_train_params: 0 = the default, each field
+    _fields_ = [("k", ctypes.c_uint32), ("d", ctypes.c_uint32), ("f", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
 AWAIT_FN = ctypes.CFUNCTYPE(c_size_t, c_void_p, ctypes.POINTER(c_void_p))
 YIELD_FN = ctypes.CFUNCTYPE(None, c_void_p, c_void_p, c_size_t)
 
@@ -103,6 +107,7 @@ _SIGS = {
     "lz4f_mi355x_dev_readPackDirectory": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p]),
     "lz4f_mi355x_dev_splitFrames": (c_size_t, [c_void_p, c_void_p, c_size_t, ctypes.c_uint32, c_void_p, c_void_p]),
     "lz4f_mi355x_splitFrames": (c_size_t, [c_void_p, c_size_t, ctypes.c_uint32, c_void_p, c_void_p]),
+    "lz4f_mi355x_dev_trainDict": (c_size_t, [c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, ctypes.POINTER(TrainParams), c_void_p]),
     "lz4f_mi355x_conduit_compress": (ctypes.c_int, [c_size_t, PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_compress_yield_immediately": (ctypes.c_int, [PP, AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),
     "lz4f_mi355x_conduit_decompress": (ctypes.c_int, [AWAIT_FN, YIELD_FN, c_void_p, ctypes.c_char_p, c_size_t]),

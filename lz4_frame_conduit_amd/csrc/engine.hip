@@ -18,6 +18,7 @@
 #include "measure_batch.cuh"
 #include "pack_batch.cuh"
 #include "split_batch.cuh"
+#include "train_dict.cuh"
 
 using namespace lz4f;
 
@@ -180,7 +181,7 @@ lz4f_mi355x_engine::~lz4f_mi355x_engine()
     (void)hipStreamSynchronize((hipStream_t)stream);
     desc.release(); seqcnt.release(); spx.release(); selfix.release(); selfcnt.release(); postab.release(); pdbuf.release(); tight.release();
     info.release(); recs.release(); e1_scratch.release(); walkbuf.release(); density.release(); ixtmp.release(); table.release(); blk_bytes.release(); res.release(); bad.release();
-    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); pctl.release(); split.release(); cframes.release(); cblocks.release(); cchunks.release();
+    d_in.release(); d_out.release(); bframes.release(); btable.release(); mframes.release(); mtable.release(); pctl.release(); split.release(); train.release(); cframes.release(); cblocks.release(); cchunks.release();
     h_in.release(); h_out.release(); h_small.release();
     for (int i = 0; i < 24; i++) if (ev[i]) (void)hipEventDestroy((hipEvent_t)ev[i]);
     if (aux_stream) { (void)hipStreamSynchronize((hipStream_t)aux_stream); (void)hipStreamDestroy((hipStream_t)aux_stream); }
@@ -1462,6 +1463,57 @@ size_t lz4f_mi355x_dev_splitFrames(lz4f_mi355x_engine* e, const void* d_src, siz
                        max_frames, d_src_off, (ResultRec*)d_split);
     hipLaunchKernelGGL(k_split_serial, dim3(1), dim3(256), 0, st, src, (uint64_t)srcBytes, (const SpCtl*)ctl, 0u, max_frames, d_src_off, (ResultRec*)d_split);
     return batch_end("dev_splitFrames");
+}
+
+// a dictionary trained from the samples of a batch (train_dict.cuh): the corpus gathered, hashed and counted, the look-back, then
+// `rounds` times the picks and their commit - the ladder is the parameters', never the samples'
+size_t lz4f_mi355x_dev_trainDict(lz4f_mi355x_engine* e, uint32_t n_samples, const void* d_src, size_t srcBytes, const uint64_t* d_src_off,
+                                 void* d_dict, size_t dictSize, const lz4f_mi355x_train_params* params, lz4f_mi355x_result* d_result)
+{
+    if (!e) return make_err(LZ4F_ERROR_GENERIC);
+    TdArgs a{LZ4F_MI355X_TRAIN_K, LZ4F_MI355X_TRAIN_D, LZ4F_MI355X_TRAIN_F, LZ4F_MI355X_TRAIN_ROUNDS};
+    if (params) {
+        if (params->k) a.k = params->k;
+        if (params->d) a.d = params->d;
+        if (params->f) a.f = params->f;
+        if (params->rounds) a.rounds = params->rounds;
+    }
+    auto refuse = [](const char* what) { set_last_error("dev_trainDict: %s", what); return make_err(LZ4F_ERROR_GENERIC); };
+    if (a.d != 4 && a.d != 6 && a.d != 8) return refuse("d must be 4, 6 or 8");
+    if (a.k < a.d || a.k > TD_MAX_K) return refuse("k must be in [d, 4096]");
+    if (a.f < 16 || a.f > 22) return refuse("f must be in [16, 22]");
+    if (a.rounds < 1 || a.rounds > 64) return refuse("rounds must be in [1, 64]");
+    if (dictSize > 65536) return refuse("dictSize above 64 KiB (LZ4 never reads further back)");
+    if ((uint64_t)srcBytes >= (1ull << 31)) { set_last_error("dev_trainDict: srcBytes too large"); return make_err(LZ4F_ERROR_srcSize_tooLarge); }
+    if (n_samples == 0 || dictSize == 0) return 0;
+    if (const size_t r = batch_begin(e, "dev_trainDict", d_src && d_src_off && d_dict)) return r;
+    hipStream_t st = (hipStream_t)e->stream;
+    const uint32_t dict_size = (uint32_t)dictSize, epochs = std::max<uint32_t>(dict_size / a.k, 1);
+    Carve ws{e->train};
+    const size_t ctl_at = ws.take(256, 256), at_at = ws.take(((size_t)n_samples + 1) * 8, 16), c_at = ws.take(srcBytes + 32, 16),
+                 hv_at = ws.take(srcBytes * 4 + 16, 16), back_at = ws.take(srcBytes * 2 + 16, 16), freq_at = ws.take((size_t)4 << a.f, 16),
+                 best_at = ws.take((size_t)epochs * 8, 16);                              // (the counts and the picks lie together: one fill clears both)
+    if (ws.ensure()) return make_err(LZ4F_ERROR_allocation_failed);
+    TdCtl* ctl = ws.at<TdCtl>(ctl_at);
+    uint64_t* at = ws.at<uint64_t>(at_at);
+    uint8_t* C = ws.at<uint8_t>(c_at);
+    uint32_t* hv = ws.at<uint32_t>(hv_at);
+    uint16_t* back = ws.at<uint16_t>(back_at);
+    uint32_t* freq = ws.at<uint32_t>(freq_at);
+    unsigned long long* best = ws.at<unsigned long long>(best_at);
+    const uint8_t* src = (const uint8_t*)d_src; uint8_t* dict = (uint8_t*)d_dict;
+    HIP_TRY(hipMemsetAsync(freq, 0, ws.end - freq_at, st));
+    const dim3 g_tiles = batch_grid((uint64_t)srcBytes + 1, TD_TILE);
+    hipLaunchKernelGGL(k_td_scan, dim3(1), dim3(1024), 0, st, d_src_off, (uint64_t)srcBytes, n_samples, a, dict, dict_size, at, ctl, (ResultRec*)d_result);
+    hipLaunchKernelGGL(k_td_gather, g_tiles, dim3(TD_THREADS), 0, st, src, d_src_off, n_samples, (const uint64_t*)at, (const TdCtl*)ctl, C);
+    hipLaunchKernelGGL(k_td_hash, g_tiles, dim3(TD_THREADS), 0, st, (const uint8_t*)C, (const TdCtl*)ctl, a, hv, freq);
+    hipLaunchKernelGGL(k_td_back, g_tiles, dim3(TD_THREADS), 0, st, (const uint32_t*)hv, (const TdCtl*)ctl, back);
+    for (uint32_t r = 0; r < a.rounds; r++) {
+        hipLaunchKernelGGL(k_td_pick, g_tiles, dim3(TD_THREADS), 0, st, (const uint32_t*)hv, (const uint16_t*)back, (const uint32_t*)freq, (const TdCtl*)ctl, best);
+        hipLaunchKernelGGL(k_td_commit, dim3(1), dim3(TD_THREADS), 0, st, (const uint8_t*)C, (const uint32_t*)hv, (const uint16_t*)back, freq, ctl, best, a,
+                           r + 1 == a.rounds ? 1u : 0u, dict, dict_size, (ResultRec*)d_result);
+    }
+    return batch_end("dev_trainDict");
 }
 
 // `dict`: the call's dictionary - none, one (a raw one's tail, or a prepared one's with its digests), or a set, frame i with the

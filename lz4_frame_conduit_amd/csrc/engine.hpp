@@ -80,6 +80,7 @@ struct lz4f_mi355x_engine {
     lz4f::DevBuf mframes, mtable;                          // dev_measureFrames: per-frame records, windows, counts + control words, the batch's block table
     lz4f::DevBuf pctl;                                     // dev_packFrames: the control block (the scan's verdict, for the copy)
     lz4f::DevBuf split;                                    // dev_splitFrames: the position bits and chunk counts, the control block, the node list and its links (split_batch.cuh)
+    lz4f::DevBuf train;                                    // dev_trainDict: the control block, the samples' places, the corpus, its hashes and look-backs, the counts and the picks (train_dict.cuh)
     lz4f::DevBuf cframes, cblocks, cchunks;                // dev_compressFrames: per-frame records + control words, the batch's block and chunk tables (ChunkInfo: `info`, records: `recs`)
     lz4f::PinBuf h_in, h_out, h_small;
     // A-B and development switches: read from the environment ONCE, when the engine is made (engines of the host-pointer calls

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _ffi
-from ._ffi import Block, FrameInfo, Preferences, Result
+from ._ffi import Block, FrameInfo, Preferences, Result, TrainParams
 
 
 class DeviceCodecError(Exception):
@@ -141,6 +141,29 @@ def _check_split_args(src, max_frames, src_off, record, rec_bytes: int) -> int:
     return max_frames
 
 
+def _check_train_args(src, src_off, dict_out, params, record, rec_bytes: int) -> int:
+    """The arguments of Engine.train_dict_async -> the number of samples; ValueError for what is wrong with them."""
+    named = [("src", src, torch.uint8), ("src_off", src_off, torch.int64), ("dict_out", dict_out, torch.uint8)]
+    if record is not None:
+        named.append(("record", record, torch.uint8))
+    _check_tensors(named, "a training call")
+    if src_off.numel() < 1:
+        raise ValueError("src_off must hold n+1 offsets (got %d)" % src_off.numel())
+    n = src_off.numel() - 1
+    if n >= 1 << 32:
+        raise ValueError("too many samples for one call")
+    if params is not None and not isinstance(params, TrainParams):
+        raise ValueError("params must be a TrainParams (or None for the defaults)")
+    if dict_out.numel() > 65536:
+        raise ValueError("dict_out must hold at most 65536 bytes (got %d): LZ4 never reads further back" % dict_out.numel())
+    if record is not None and record.numel() < rec_bytes:
+        raise ValueError("record must hold %d bytes (got %d)" % (rec_bytes, record.numel()))
+    return n
+
+
+TRAIN_TILE = 4096       # LZ4F_MI355X_TRAIN_TILE: the corpus positions a workgroup of the training kernels takes at a time (for tests and tools)
+TRAIN_SCAN_TILE = 1024  # LZ4F_MI355X_TRAIN_SCAN_TILE: the samples a step of the offsets' scan takes
+TRAIN_DEFAULTS = {"k": 64, "d": 8, "f": 18, "rounds": 16}      # LZ4F_MI355X_TRAIN_K, _D, _F, _ROUNDS
 PACK_TILE = 16384       # LZ4F_MI355X_PACK_TILE: the output bytes a workgroup of the pack's copy kernel takes at a time (for tests and tools)
 PACK_DIRECTORY = 0x1    # LZ4F_MI355X_PACK_DIRECTORY
 
@@ -581,6 +604,29 @@ class Engine:
         n = _check_split_args(src, max_frames, src_off, record, self.RESULT_BYTES)
         _chk(self.L, self.L.lz4f_mi355x_dev_splitFrames(self.h, src.data_ptr(), src.numel(), n, src_off.data_ptr(),
                                                        record.data_ptr() if record is not None else None))
+
+    def train_dict_async(self, src: torch.Tensor, src_off: torch.Tensor, dict_out: torch.Tensor, params: "TrainParams | None" = None,
+                         record: "torch.Tensor | None" = None):
+        """Enqueue the training of a dictionary from a batch of samples: sample i is src[src_off[i]:src_off[i+1]] (src: a uint8 device
+        tensor; src_off: an int64 device tensor of n+1 offsets; overlapping spans are legal, a span that runs backwards or past src
+        gives nothing), and dict_out (a uint8 device tensor of at most 65 536 bytes) receives the dictionary - all of it is written:
+        the trained content right-aligned, the best segments last, zeros in front - so that create_cdict(dict_out) follows on the
+        same stream with no size read back.  The segments are those of the samples whose params.d-byte substrings are the most
+        frequent in the batch, params.k bytes each at most, chosen in up to params.rounds rounds (TrainParams; None and every field
+        left 0: the defaults, TRAIN_DEFAULTS); the bytes are those of the sequential definition in include/lz4f_mi355x.h, whatever
+        the device does in parallel.
+        record (uint8 device tensor of 32 bytes, optional) receives one Result: size = the trained bytes, consumed = the sample
+        bytes taken, n_blocks = the segments, first_bad_block = the first sample whose span is invalid (0xFFFFFFFF: none), status 0,
+        flags & 0xFF = the rounds run.  The call raises only for what is wrong with the call itself (DeviceCodecError for a
+        parameter out of range).  Nothing is read back: no synchronisation.  On one stream:
+
+            eng.train_dict_async(samples, samples_off, d)
+            cd = eng.create_cdict(d)
+            eng.compress_frames_async(inp, inp_off, win, win_off, prefs, results, cdict=cd)"""
+        n = _check_train_args(src, src_off, dict_out, params, record, self.RESULT_BYTES)
+        _chk(self.L, self.L.lz4f_mi355x_dev_trainDict(self.h, n, src.data_ptr(), src.numel(), src_off.data_ptr(), dict_out.data_ptr(), dict_out.numel(),
+                                                     ctypes.byref(params) if params is not None else None,
+                                                     record.data_ptr() if record is not None else None))
 
     def frame_results(self, results: torch.Tensor) -> "list[Result]":
         """Wait for the stream, then the records of a batch (status 0 = ok; otherwise the LZ4F error code of that frame)."""
