@@ -125,6 +125,7 @@ DECLARED_SYMBOLS = tuple(_SIGS)
 _U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
 DEV_SIGS = {
     "lz4f_mi355x_debug_e1_merge": (ctypes.c_int, [ctypes.c_int, c_void_p, c_void_p, c_void_p, _U32, _U64, _U32, _U32, _U32, _U32, _U32, c_void_p, c_void_p, c_void_p]),
+    "lz4f_mi355x_debug_spx_index": (ctypes.c_int, [c_void_p, _U64, _U32, c_void_p, c_void_p, c_void_p, c_void_p, _U32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _LIB = None

@@ -193,13 +193,16 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
             spx_begin(in, readable, c);
             // (a lane that started without a pair to go by - none in SPX_SCAN bytes - may stand in a literal run longer than that, where its
             // chain crawls ~20 bytes per hop: if it makes less than an eighth of the way per hop that the probe saw sequences make in this
-            // frame, it gives up after 64 hops and the stitching thread walks the stretch)
+            // frame, it gives up after 64 hops.  A lane that gives up has no landing.  If no true chain lands on its start - a wrong guess -
+            // the stitching thread skips it and walks the stretch itself; if it was a TRUE lane, the stitch finds a true lane without a
+            // landing and declines the whole frame, a valid one, to the generic decoder: see the stitch below, tests/spx_cases.py `exits`)
             // A lane that started at a pair may crawl as well: a wrong guess that looked like a token - a handful per 4 GiB - makes 900 hops
             // through its 32 KiB before it falls into step, and in most frames the whole kernel waited 0.6 ms for that one lane.  (The probe
             // cannot say what a hop should make where every block begins with a long literal run: it then has nothing to count.)  Such a
             // lane's premise was a token that announces a long literal run, in a stretch made of them; a chain through random bytes finds
-            // one token in sixteen like that.  After 64 hops with fewer than half of them: it gives up, and the stitching thread walks
-            // the stretch.
+            // one token in sixteen like that.  After 64 hops with fewer than half of them: it gives up - a wrong guess's stretch is then
+            // walked by the stitching thread; a true lane that started at a pair and meets 63 tokens with fewer than 32 literal nibbles
+            // of 15 among them declines the frame, as above.
             const uint32_t slow = (u && s_g[u] == u * SPX_SEG && only_if) ? only_if[1] / 8u : 0u;
             const bool by_pair = u && s_g[u] != u * SPX_SEG;
             uint32_t longs = 0, sub_stride = SPX_SUB_STRIDE;
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
 #ifdef SPX_PROF
                 if (hops > SPX_LANE_HOPS) atomicAdd(&ctl->spx_prof.hop_cap, 1u);
 #endif
-                if (hops > SPX_LANE_HOPS) break;                             // (a chain that crawls is a wrong guess: the stitching thread walks this stretch)
+                if (hops > SPX_LANE_HOPS) break;                             // (a chain that crawls is taken for a wrong guess, whose stretch the stitching thread walks; a TRUE lane with more than SPX_LANE_HOPS + 1 sequences to the next start declines the frame)
                 const int r = spx_step(in, csize, readable, c);
                 if (r == 1) { pb = SpxPoint{c.pos, c.seq, c.out}; ended = 1; break; }      // the payload's end (for a guessed chain: what looks like it)
                 if (r == 2) break;                                           // (a guessed chain may run into anything)
@@ -256,7 +259,7 @@ __global__ __launch_bounds__(SPX_MAXSEG) void k_spx_index(const uint8_t* __restr
             tpos += 1u + s_nsub[k];
             SpxPoint nx{SPX_NONE, 0, 0}; uint32_t ended = 0;
             if (s_b[k].pos != SPX_NONE) { nx = SpxPoint{s_b[k].pos, cur.seq + s_b[k].seq, cur.out + s_b[k].out}; ended = s_end[k]; }
-            else { bad = true; break; }                                      // (a true chain that runs into something: malformed payload)
+            else { bad = true; break; }                                      // (a true lane without a landing: its chain ran into something - a malformed payload - or it gave up by the slow, by_pair or hop-cap rule on a valid one; either way the frame is declined)
             uint32_t kn = k + 1;
             while (!ended && !(kn < nl && s_g[kn] == nx.pos)) {
                 // the true chain did not land on the next lane's start (or there is none): walk on from where it stands, to the start of

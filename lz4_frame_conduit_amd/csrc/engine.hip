@@ -1848,4 +1848,43 @@ __attribute__((visibility("default"))) int lz4f_mi355x_debug_e1_merge(int form, 
     return (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess) ? 0 : 2;
 }
 
+// developer aid (tests/test_gpu_spx_index.py; not in the header): the unchanged k_spx_index on caller-given device bytes - d_frame[0, frame_cap)
+// with n blocks (src_off, word) in it, the size word's top bit a stored block as in the frame.  not_dense / bytes_per_seq: the two words of
+// k_density_probe the kernel reads (both null: no only_if, as under LZ4F_MI355X_NO_DENSITY_PROBE).  pt_fill: the word every point of the
+// workspace holds before the launch.  Copied back to the host: cnt, osz, nr (n words each), points (n rows of SPX_MAXPT + 1 points of three
+// words: a block's nr + 1 points lead its row, the rest keeps pt_fill), ctl[0] = IxCtl::gave_up, ctl[1] = IxCtl::spx_stitched.  Runs on the
+// device's null stream and waits.  0: done; 1: an argument is out of range; 2: a HIP error
+__attribute__((visibility("default"))) int lz4f_mi355x_debug_spx_index(const uint8_t* d_frame, uint64_t frame_cap, uint32_t n, const uint64_t* src_off, const uint32_t* word,
+                                                                      const uint32_t* not_dense, const uint32_t* bytes_per_seq, uint32_t pt_fill, uint32_t* cnt, uint32_t* osz,
+                                                                      uint32_t* nr, uint32_t* points, uint32_t* ctl)
+{
+    if (!d_frame || !src_off || !word || !cnt || !osz || !nr || !points || !ctl || n == 0 || n > 4096 || frame_cap > (1ull << 40)) return 1;
+    if ((not_dense == nullptr) != (bytes_per_seq == nullptr)) return 1;
+    for (uint32_t b = 0; b < n; b++) if (src_off[b] > frame_cap) return 1;
+    const size_t row = (size_t)(SPX_MAXPT + 1) * sizeof(SpxPoint), at_tbl = sizeof(IxCtl), at_res = at_tbl + (size_t)n * sizeof(BlockOut), at_dens = at_res + 64,
+                 at_cnt = at_dens + 64, at_T = at_cnt + (((size_t)n * 12 + 63) & ~(size_t)63), total = at_T + (size_t)n * row;
+    std::vector<uint8_t> h(at_T, 0);
+    for (uint32_t b = 0; b < n; b++) { BlockOut e{src_off[b], 0, word[b], 0}; memcpy(&h[at_tbl + (size_t)b * sizeof(BlockOut)], &e, sizeof(e)); }
+    ResultRec r{}; r.status = ST_OK; r.n_blocks = n; memcpy(&h[at_res], &r, sizeof(r));
+    if (not_dense) { Density d{0, *not_dense, *bytes_per_seq}; memcpy(&h[at_dens], &d, sizeof(d)); }
+    for (size_t i = at_cnt; i < at_T; i += 4) memcpy(&h[i], &pt_fill, 4);
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, total) != hipSuccess) return 2;
+    bool ok = hipMemcpy(d, h.data(), at_T, hipMemcpyHostToDevice) == hipSuccess && hipMemsetD32((hipDeviceptr_t)(d + at_T), (int)pt_fill, (size_t)n * row / 4) == hipSuccess;
+    if (ok) {
+        uint32_t* dc = (uint32_t*)(d + at_cnt);
+        hipLaunchKernelGGL(k_spx_index, dim3(n), dim3(SPX_MAXSEG), 0, 0, d_frame, frame_cap, (const BlockOut*)(d + at_tbl), (const ResultRec*)(d + at_res), n, dc, dc + n,
+                           (SpxPoint*)(d + at_T), dc + 2 * (size_t)n, (IxCtl*)d, not_dense ? (const uint32_t*)&((const Density*)(d + at_dens))->not_dense : (const uint32_t*)nullptr);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    }
+    IxCtl c{};
+    ok = ok && hipMemcpy(&c, d, offsetof(IxCtl, chain_total), hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cnt, d + at_cnt, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(osz, d + at_cnt + (size_t)n * 4, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(nr, d + at_cnt + (size_t)n * 8, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+         hipMemcpy(points, d + at_T, (size_t)n * row, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d);
+    if (!ok) return 2;
+    ctl[0] = c.gave_up; ctl[1] = c.spx_stitched;
+    return 0;
+}
+
 }  // extern "C"
